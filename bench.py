@@ -9,10 +9,18 @@ One "step" = one pass of the whole hot path over one batch of synthetic images r
   348-403 and :424-481), i.e. two blur+CRF passes per image like the reference.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config voc|psc59|coco80|ade768] [--dtype bf16x3|f32|bf16]
+                  [--dump-outputs DIR] [--full]
 
-The headline (`value`, `dtype`, `roofline`) is measured in a mode that reproduces the reference's fp32 results
-(`bf16x3`, split-bf16: tests/test_hip_parity.py hold it to maps < 1e-4 and identical patch picks); plain `bf16` is
-reported as a nested `throughput_mode` record together with how far its label maps are from the headline's.
+A plain run does only what the headline needs: set-up, `--warmup` untimed and `--steps` timed steps of the pass the headline
+is read from (P batches in flight, or one batch at a time with `--pipelines 1`), the outputs of the last step if
+`--dump-outputs` is given, and the result line (`value` images/s, `ms_per_step`, `dtype`, ...).  `--full` adds everything
+else, as separate runs after the headline: the one-batch-at-a-time pass with the per-kernel records (`roofline`, `crf`),
+the label comparison against the reference's fixtures, the other image-noise operating points, the other compute modes,
+the other BASELINE configs and the CPU baseline (each can be switched off with its `--no-...` option).
+
+The headline (`value`, `dtype`; `roofline` with `--full`) is measured in a mode that reproduces the reference's fp32 results
+(`bf16x3`, split-bf16: tests/test_hip_parity.py hold it to maps < 1e-4 and identical patch picks); with `--full`, plain `bf16`
+is reported as a nested `throughput_mode` record together with how far its label maps are from the headline's.
 
 Multi-GPU (`--gpus N`, N > 1): one process per GPU.  Launched under torch.distributed.run (RANK in the
 environment) this process IS a rank; launched bare, this process only starts N rank processes of itself
@@ -111,6 +119,13 @@ def parse_args(argv=None):
     ap.add_argument("--overlap", action="store_true",
                     help="software-pipeline batches over two HIP streams (drop loop of batch i+1 beside the post-process "
                          "of batch i); off by default so the per-kernel event timing stays undisturbed")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the one-batch-at-a-time pass with the per-kernel roofline / DenseCRF records, the "
+                         "fixture label check, the noise-12 and photograph-like operating points, the other compute modes, the other "
+                         "configs and the CPU baseline (the --no-... options switch single legs off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (label maps and GradCAM maps of both "
+                         "branches, as float32) to DIR/<name>.npy; at most 64 MB in all (a fixed, seeded sample beyond that)")
     return ap.parse_args(argv)
 
 
@@ -226,6 +241,39 @@ def cpu_baseline(cfg, seed_w, n_images=20, noise=NOISE, cores=None, W=None):
                 "sample": "the reference's own compute_gradcam_ensemble (forward + full autograd backward + 144 gathers) 9.07 s per "
                           "call x 4 drop iterations + threshold/upsample 0.38 s + scipy blur 1.23 s, one 336x336 image, 25-token "
                           "caption; DenseCRF not included (pydensecrf cannot be installed there): BASELINE.md section 2"}}
+
+
+# ------------------------------------------------------------------------------------------ output dump
+
+DUMP_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(d, arrays, budget=DUMP_BYTES):
+    """Write every array as d/<name>.npy, float64 kept, anything else as float32.  If they hold more than `budget` bytes in all,
+    each is cut to the same fraction of its elements: a fixed, seeded sample of its flat indices, in ascending order.
+    Returns {name: {"shape": computed shape, "saved": element count written}}."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    arrs = {k: np.asarray(v) for k, v in arrays.items()}
+    arrs = {k: v.astype(np.float64 if v.dtype == np.float64 else np.float32, copy=False) for k, v in arrs.items()}
+    room = budget - 4096 * len(arrs)                      # the .npy headers
+    frac = min(1.0, room / max(1, sum(v.nbytes for v in arrs.values())))
+    info = {}
+    for k, v in arrs.items():
+        shape = list(v.shape)
+        if frac < 1.0:
+            idx = np.sort(np.random.default_rng(0).choice(v.size, int(v.size * frac), replace=False))
+            v = v.reshape(-1)[idx]
+        np.save(os.path.join(d, k + ".npy"), v)
+        info[k] = {"shape": shape, "saved": int(v.size)}
+    return info
+
+
+def step_outputs(st):
+    """What one step of the timed path hands its caller: the label maps of the branches it ran and the two GradCAM maps."""
+    g0, agg = st["keep"] if "keep" in st else st["keepall"][-1]
+    out = {"labels_1drop": st.get("l1"), "labels_ndrop": st["ln"], "gradcam_1drop": g0, "gradcam_ndrop": agg}
+    return {k: v.detach().cpu().numpy() for k, v in out.items() if v is not None}
 
 
 # ------------------------------------------------------------------------------------------ one rank
@@ -699,26 +747,36 @@ def run_rank(a):
                 return sum(k["traffic_bytes_per_launch"] * k["launches_profiled"] for k in ks) / max(n, 1)
         return None
 
-    def record(wl, P, noise, steps, warmup, headline=False):
+    def record(wl, P, noise, steps, warmup, headline=False, full=True):
         """One workload in one compute mode: a one-batch-at-a-time pass with the per-kernel records, then (P > 1) the same
-        steps with P batches in flight.  Returns (line fields, final state)."""
-        dt, state, gemm, crf, ppp = wl.timed_run(noise, steps, warmup, a.overlap if headline else False, a.separate_crf if headline else False)
-        seq = {"value": world * wl.B * steps / dt, "ms_per_step": 1e3 * dt / steps}
+        steps with P batches in flight.  full=False (a plain run): only the pass the value is read from -- P batches in
+        flight, or the one-batch-at-a-time pass when P = 1 -- and no per-kernel records.  Returns (line fields, final state);
+        state["last"] is the state of the pipeline that took the last timed step."""
+        seq = None
+        if full or P == 1:
+            dt, state, gemm, crf, ppp = wl.timed_run(noise, steps, warmup, a.overlap if headline else False, a.separate_crf if headline else False)
+            seq = {"value": world * wl.B * steps / dt, "ms_per_step": 1e3 * dt / steps}
+            last = state
         if P > 1:
             dt, states = wl.timed_run_pipelined(P, noise, steps, warmup)
+            last = states[(steps - 1) % P]                # the steps are dealt round-robin
             for st in states[1:]:
                 states[0]["histn"] += st["histn"]
                 states[0]["hist1"] += st["hist1"]
             state = {k: states[0][k] for k in ("histn", "hist1")}
             state["ln"] = next(st["ln"] for st in states if "ln" in st)
-        roof = roofline_gemm(wl.dtype, gemm)
+        state["last"] = last
+        pipe = {"batches_in_flight": P,
+                "note": "P engines / HIP streams / host threads take the timed steps round-robin; every step is "
+                        "the whole path over one batch; the engines share one weight copy"}
+        if full:
+            pipe["one_batch_at_a_time"] = seq
+        pipe["engine_device_bytes"] = [int(e.allocated_bytes()) for e in wl.engines[:max(P, 1)]]
         rec = {"value": world * wl.B * steps / dt, "unit": "images/sec", "ms_per_step": 1e3 * dt / steps, "steps": steps, "warmup": warmup,
-               "dtype": wl.dtype,
-               "pipelines": {"batches_in_flight": P,
-                             "note": "P engines / HIP streams / host threads take the timed steps round-robin; every step is "
-                                     "the whole path over one batch; the engines share one weight copy", "one_batch_at_a_time": seq,
-                             "engine_device_bytes": [int(e.allocated_bytes()) for e in wl.engines[:max(P, 1)]]},
-               "roofline": roof, "crf": roofline_crf(crf, steps, ppp, wl.name, noise)}
+               "dtype": wl.dtype, "pipelines": pipe}
+        if full:
+            rec["roofline"] = roofline_gemm(wl.dtype, gemm)
+            rec["crf"] = roofline_crf(crf, steps, ppp, wl.name, noise)
         if wl.dtype == "bf16x3":
             # the stream-K tail of the split-bf16 GEMM (csrc/gemm_x3.hip): launches that took it, and the give-up word of its bounded
             # spins -- an owner that gave up waiting for a partial tile produced garbage, so anything but 0 fails the run loudly
@@ -726,8 +784,9 @@ def run_rank(a):
             rec["streamk"] = {"launches": int(sum(n for n, _ in sk)), "gave_up": int(max(t for _, t in sk))}
             if rec["streamk"]["gave_up"]:
                 raise SystemExit(f"bench.py: a stream-K owner gave up waiting for a partial tile (word {rec['streamk']['gave_up']}): results invalid")
-        rec["roofline"]["measured_in"] = rec["crf"]["measured_in"] = (
-            "one-batch-at-a-time pass of the same workload in this run (%d timed steps, %.1f ms per step)" % (steps, seq["ms_per_step"]))
+        if full:
+            rec["roofline"]["measured_in"] = rec["crf"]["measured_in"] = (
+                "one-batch-at-a-time pass of the same workload in this run (%d timed steps, %.1f ms per step)" % (steps, seq["ms_per_step"]))
         return rec, state
 
     def workload_cfg(wl, noise):
@@ -744,8 +803,10 @@ def run_rank(a):
     if free_b / 2 ** 30 < budget["device_GiB_per_rank"] and not a.share_gpu:
         raise SystemExit(f"bench.py: rank {rank} sees {free_b / 2 ** 30:.0f} GiB free on cuda:{local}, {budget['device_GiB_per_rank']} needed for {P} engines")
     wl = Workload(a.config, a.dtype, a.batch, a.crf_chunk, True if a.skip_1drop else None)
-    head, state = record(wl, P, a.noise, a.steps, a.warmup, headline=True)
+    head, state = record(wl, P, a.noise, a.steps, a.warmup, headline=True, full=a.full)
     torch.cuda.synchronize()
+    dumped = dump_outputs(a.dump_outputs, step_outputs(state["last"])) if a.dump_outputs and rank == 0 else None
+    del state["last"]
     t0 = time.perf_counter()
     gathered = coll.reduce_results([state["histn"], state["hist1"]], state["ln"])
     torch.cuda.synchronize()
@@ -754,8 +815,9 @@ def run_rank(a):
     seen = coll.ranks_seen(dev, rank)
 
     if rank == 0:
-        head["roofline"]["traffic"] = traffic_for(a.dtype)
-        head["roofline"]["traffic_unit"] = "HBM-side bytes per launch (rocprofv3 PMC, offline pass; profiles/)"
+        if a.full:
+            head["roofline"]["traffic"] = traffic_for(a.dtype)
+            head["roofline"]["traffic_unit"] = "HBM-side bytes per launch (rocprofv3 PMC, offline pass; profiles/)"
         out = {
             "metric": "images/sec (336^2, drop_iter=4, blur+CRF)" if wl.img == 336 else f"images/sec ({wl.img}^2, drop_iter=4, blur+CRF)",
             "value": head["value"], "unit": "images/sec",
@@ -769,15 +831,19 @@ def run_rank(a):
                        "f32": "the reference's arithmetic (exact fp32 MFMA)",
                        "bf16": "does NOT reproduce the reference's patch picks"}[a.dtype],
             "config": workload_cfg(wl, a.noise),
-            "pipelines": head["pipelines"], "roofline": head["roofline"], "crf": head["crf"], "streamk": head.get("streamk"),
+            "pipelines": head["pipelines"], "roofline": head.get("roofline"), "crf": head.get("crf"), "streamk": head.get("streamk"),
             "collectives": dict(weights_for(wl.cfg)[2], hist_allreduce_and_label_gather_ms=1e3 * t_reduce,
                                 per_rank_images_per_sec=per_rank,
                                 hist_ndrop_total=int(state["histn"].sum().item()),       # all-reduced: pixels counted by ALL ranks
                                 gathered_label_bytes=[int(g.numel()) for g in gathered],
                                 note="outside the timed region (start-up broadcast, end-of-run reduce); RCCL when n_ranks > 1"),
         }
-        single = world == 1
-        if a.dtype != "bf16" and not a.no_fixture_check:
+        if not a.full:
+            del out["roofline"], out["crf"]
+        if dumped is not None:
+            out["outputs_dumped"] = {"dir": a.dump_outputs, "arrays": dumped}
+        single = world == 1 and a.full            # every other record is a leg of --full
+        if a.full and a.dtype != "bf16" and not a.no_fixture_check:
             # the benchmarked mode against the REFERENCE's own label maps (committed fixtures, small geometry): fraction of
             # label pixels that differ, both branches, blur and no post-process (asserted with the near-tie rule in
             # tests/test_hip_parity.py::test_end_to_end_labels_vs_reference_run)

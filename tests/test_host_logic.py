@@ -141,12 +141,14 @@ dist.init_process_group("gloo", rank=rank, world_size=world)
 args = argparse.Namespace(weights_sync="broadcast" if mode != "checksum_bad" else "checksum")
 sync, info = cli.make_weights_sync(args, rank, world)
 flat = torch.arange(1000, dtype=torch.float32) * (1.0 if rank == 0 else 3.0)     # rank 1 starts with other weights
+def emit(rec):                   # both ranks share one stdout pipe: one write per line, so the lines never interleave
+    os.write(1, (json.dumps(rec) + "\n").encode())
 if mode == "checksum_bad":
     try:
         sync(flat)
-        print(json.dumps({"rank": rank, "raised": False}))
+        emit({"rank": rank, "raised": False})
     except SystemExit as ex:
-        print(json.dumps({"rank": rank, "raised": True, "msg": str(ex)[:80]}))
+        emit({"rank": rank, "raised": True, "msg": str(ex)[:80]})
     dist.destroy_process_group()
     sys.exit(0)
 sync(flat)
@@ -243,6 +245,44 @@ def test_bench_budget_refuses_engines_that_do_not_fit():
     assert bench.resource_budget(8, "coco80", 3)["device_GiB_per_rank"] > 150
     with pytest.raises(AssertionError):
         bench.resource_budget(8, "coco80", 5)
+
+
+def test_bench_plain_run_is_lean_by_default():
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse_args(["--steps", "7", "--warmup", "3"])
+    assert a.steps == 7 and a.warmup == 3 and not a.full and a.dump_outputs is None
+    a = bench.parse_args(["--full", "--dump-outputs", "d"])
+    assert a.full and a.dump_outputs == "d"
+
+
+def test_bench_dump_outputs_writes_float32_and_a_seeded_sample_over_budget(tmp_path):
+    """`bench.py --dump-outputs`: every array as <name>.npy (float64 kept, the rest float32, values exact); over the byte
+    budget each array is cut to the same fraction of its elements, the same seeded indices on every run."""
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(3)
+    arrays = {"labels_ndrop": rng.integers(0, 21, size=(4, 50, 60)).astype(np.uint8),
+              "gradcam_ndrop": rng.standard_normal((4, 24, 21, 21)).astype(np.float32),
+              "hist": rng.standard_normal(441)}
+    info = bench.dump_outputs(str(tmp_path / "all"), arrays)
+    for k, v in arrays.items():
+        got = np.load(tmp_path / "all" / f"{k}.npy")
+        assert got.dtype == (np.float64 if v.dtype == np.float64 else np.float32) and got.shape == v.shape
+        np.testing.assert_array_equal(got, v.astype(got.dtype))
+        assert info[k] == {"shape": list(v.shape), "saved": v.size}
+    budget = 4096 * 3 + 40_000
+    runs = []
+    for r in ("s0", "s1"):
+        info = bench.dump_outputs(str(tmp_path / r), arrays, budget=budget)
+        files = {k: np.load(tmp_path / r / f"{k}.npy") for k in arrays}
+        assert sum(os.path.getsize(tmp_path / r / f"{k}.npy") for k in arrays) <= budget
+        for k, v in arrays.items():
+            assert files[k].ndim == 1 and 0 < files[k].size < v.size and info[k]["saved"] == files[k].size
+            assert np.isin(files[k], v.astype(files[k].dtype).reshape(-1)).all()
+        runs.append(files)
+    for k in arrays:
+        np.testing.assert_array_equal(runs[0][k], runs[1][k])
 
 
 def test_bench_launcher_propagates_a_failed_rank():

@@ -1,5 +1,5 @@
 R=$PWD; OUT=$R/gpurun_out/ade_sweep.txt; : > $OUT
-A="--config ade768 --steps 4 --warmup 1 --no-cpu-baseline --no-other-modes --no-other-configs --no-noise12 --no-fixture-check"
+A="--full --config ade768 --steps 4 --warmup 1 --no-cpu-baseline --no-other-modes --no-other-configs --no-noise12 --no-fixture-check"
 line() { tag=$1; shift; python3 $R/bench.py "$@" 2> /tmp/bs_err.txt | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); p=d['pipelines']

@@ -3,7 +3,7 @@
 # size on the ade768 config.  One compact line per run into gpurun_out/batch_sweep.txt.
 #   bash tools/batch_sweep.sh
 R=$PWD; OUT=$R/gpurun_out/batch_sweep.txt; : > $OUT
-Q="--steps 12 --warmup 2 --no-cpu-baseline --no-other-modes --no-other-configs --no-noise12 --no-fixture-check"
+Q="--full --steps 12 --warmup 2 --no-cpu-baseline --no-other-modes --no-other-configs --no-noise12 --no-fixture-check"
 line() {  # tag, bench args...
   tag=$1; shift
   python3 $R/bench.py "$@" 2> /tmp/bs_err.txt | python3 -c "
@@ -22,7 +22,7 @@ line "voc B=105 P=2" $Q --batch 105 --pipelines 2 --steps 4
 if [ "$1" = "all" ]; then
 line "voc B=35 P=2" $Q --pipelines 2
 line "voc B=35 P=1" $Q --pipelines 1
-A="--config ade768 --steps 4 --warmup 1 --no-cpu-baseline --no-other-modes --no-other-configs --no-noise12 --no-fixture-check"
+A="--full --config ade768 --steps 4 --warmup 1 --no-cpu-baseline --no-other-modes --no-other-configs --no-noise12 --no-fixture-check"
 for c in 1 2 4 8; do line "ade768 crf_chunk=$c" $A --crf-chunk $c; done
 fi
 cat $OUT

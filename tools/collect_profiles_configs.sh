@@ -13,8 +13,8 @@ R=$PWD
 OUT=$R/gpurun_out
 mkdir -p $OUT
 cd /tmp
-BARGS="--steps 2 --warmup 1 --pipelines 1 --no-cpu-baseline --no-other-modes --no-other-configs --no-noise12 --no-fixture-check"
-B1="--steps 1 --warmup 1 --pipelines 1 --no-cpu-baseline --no-other-modes --no-other-configs --no-noise12 --no-fixture-check"
+BARGS="--full --steps 2 --warmup 1 --pipelines 1 --no-cpu-baseline --no-other-modes --no-other-configs --no-noise12 --no-fixture-check"
+B1="--full --steps 1 --warmup 1 --pipelines 1 --no-cpu-baseline --no-other-modes --no-other-configs --no-noise12 --no-fixture-check"
 for cfg in $CFGS; do
   rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_trace_$cfg -o prof --output-format csv -- python3 $R/bench.py --config $cfg $BARGS > $OUT/${TAG}_trace_$cfg.log 2>&1
   echo "trace $cfg rc=$?"

@@ -4,7 +4,7 @@ export TMPDIR=/tmp
 R=$PWD
 cd /tmp
 for c in 1 2 0; do
-  rocprofv3 --kernel-trace --stats -d /tmp/cp$c -o prof --output-format csv -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-parity-mode --no-noise12 --crf-chunk $c > /tmp/cp$c.log 2>&1
+  rocprofv3 --kernel-trace --stats -d /tmp/cp$c -o prof --output-format csv -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-parity-mode --no-noise12 --crf-chunk $c > /tmp/cp$c.log 2>&1
   echo "== chunk $c: $(tail -1 /tmp/cp$c.log | python3 -c 'import sys,json; d=json.loads(sys.stdin.read()); print(d["value"], d["crf"])')"
   f=$(find /tmp/cp$c -name "*kernel_stats.csv" | head -1)
   python3 - "$f" <<'PY'

@@ -2,7 +2,7 @@
 # GPU box: A/B of the non-temporal streaming accesses in the DenseCRF splat / update kernels (round 5; they are the default:
 # `base` builds with -DPNP_CRF_NO_NT, which turns ld_stream / st_stream in csrc/crf.hip into plain accesses).  gpurun_out/crf_nt_ab.txt
 R=$PWD; OUT=$R/gpurun_out/crf_nt_ab.txt; : > $OUT
-Q="--steps 6 --warmup 2 --pipelines 1 --no-cpu-baseline --no-other-modes --no-other-configs --no-noise12 --no-fixture-check"
+Q="--full --steps 6 --warmup 2 --pipelines 1 --no-cpu-baseline --no-other-modes --no-other-configs --no-noise12 --no-fixture-check"
 line() { tag=$1; shift; python3 $R/bench.py "$@" 2> /tmp/ab_err.txt | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])

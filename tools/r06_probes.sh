@@ -1,5 +1,5 @@
 set -u
-Q="--steps 4 --warmup 1 --pipelines 1 --no-cpu-baseline --no-other-modes --no-other-configs --no-noise12 --no-fixture-check"
+Q="--full --steps 4 --warmup 1 --pipelines 1 --no-cpu-baseline --no-other-modes --no-other-configs --no-noise12 --no-fixture-check"
 crf() { python3 -c "
 import json,sys
 d=json.loads(open('$1').read().strip().splitlines()[-1])

@@ -4,7 +4,7 @@ export TMPDIR=/tmp
 R=$PWD
 cd /tmp; rm -rf /tmp/tp
 mkdir -p $R/gpurun_out
-rocprofv3 --kernel-trace -d /tmp/tp -o tr --output-format csv -- python3 $R/bench.py --steps 9 --warmup 1 --no-cpu-baseline --no-other-modes --no-other-configs --no-noise12 > /tmp/tp.log 2>&1
+rocprofv3 --kernel-trace -d /tmp/tp -o tr --output-format csv -- python3 $R/bench.py --full --steps 9 --warmup 1 --no-cpu-baseline --no-other-modes --no-other-configs --no-noise12 > /tmp/tp.log 2>&1
 f=$(find /tmp/tp -name "*kernel_trace.csv" | head -1)
 python3 - "$f" > $R/gpurun_out/trace_pipelined.txt <<'PY'
 import csv, sys
