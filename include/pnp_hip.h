@@ -111,6 +111,32 @@ int pnp_compute_gradcam_layer(pnp_engine* e, const float* d_images, const uint8_
                               const int64_t* d_mask, int32_t ld, int32_t B, int32_t L, int32_t layer, int32_t head,
                               float* d_out, float* d_logits, void* stream);
 
+/* ---- ITC head and feature extraction: replaces BlipITM.forward(match_head="itc") and BlipITM.extract_features
+ * (B/blip_image_text_matching.py:253-266, 59-189).  They need the optional weights vision_proj.weight / .bias (E, vit_dim) and
+ * text_proj.weight / .bias (E, txt_hidden), E = the weight's first dimension (256 in every BLIP config, a multiple of 64):
+ * pnp_finalize_weights succeeds without them, pnp_project_normalize then returns PNP_ERR_STATE naming the missing tensor.
+ * Engines made by pnp_create_shared use the donor's copy. */
+/* BertModel.forward(mode="text") (B/med.py:565-568, 473): the text stack with self-attention and feed-forward only -- no
+ * cross-attention, token 0 kept as given (no [ENC] substitution) -- for T texts of L tokens, 2 <= L <= max_text_len, that need
+ * no image: T may exceed max_batch (e.g. 150 class prompts), the call then works through max_batch rows of text at a time, and
+ * a row's result does not depend on T.  d_ids / d_mask: (T, ld) int64, the first L columns are used.  d_hidden: (T, L, H)
+ * fp32 last_hidden_state, or NULL (the last max_batch-row piece stays readable as "text_hidden").  Runs in the activation
+ * buffers of pnp_text_forward_xattn: afterwards pnp_xattn_grad* / pnp_gradcam_gather fail (PNP_ERR_STATE) until the next
+ * multimodal forward; image_embeds and the cross-attention keys / values of the last pnp_vit_forward stay as they are. */
+int pnp_text_forward_text(pnp_engine* e, const int64_t* d_ids, const int64_t* d_mask, int32_t ld, int32_t T, int32_t L,
+                          float* d_hidden, void* stream);
+/* F.normalize(proj(x), dim=-1), proj = vision_proj (which = 0, K = vit_dim) or text_proj (which = 1, K = txt_hidden)
+ * (B/blip_image_text_matching.py:137-138, 158-159, 260-263): d_out[r, :] = y / max(||y||_2, 1e-12), y = W . x_r + b.
+ * d_x: fp32, row r at d_x + r * row_stride (row_stride >= K elements, a multiple of 4; rows * row_stride * 4 < 4 GiB) -- the CLS
+ * rows of a (B, N, D) tensor are row_stride = N * D, rows = B, no gather.  d_out: (rows, E) fp32.  The Linear runs in the
+ * engine's compute mode (exact fp32 MFMA | split-bf16 | bf16), the normalisation in fp32. */
+int pnp_project_normalize(pnp_engine* e, int32_t which, const float* d_x, int64_t row_stride, int32_t rows, float* d_out,
+                          void* stream);
+/* sim = image_feat @ text_feat.t() (B/blip_image_text_matching.py:265): d_sim[b, t] = sum_e d_img_feat[b, e] * d_txt_feat[t, e],
+ * plain fp32 FMA in a fixed order (independent of the compute mode).  E a multiple of 4.  Stateless. */
+int pnp_itc_similarity(const float* d_img_feat, const float* d_txt_feat, int32_t B, int32_t T, int32_t E, float* d_sim,
+                       void* stream);
+
 /* ---- salience-drop loop: replaces Inference_BLIP_filteredcaption (PnP.py:564-722) -------- */
 /* One bookkeeping step (PnP.py:619-647 + the running sum of :716-721) on a gathered map. */
 int pnp_drop_step(pnp_engine* e, const float* d_gradcam, float* d_g0, float* d_agg, uint8_t* d_dropped,
@@ -239,8 +265,9 @@ int pnp_jpeg_decode(const uint8_t* d_data, const pnp_jpeg_image* d_images, const
                     int32_t max_pixels_per_image, int32_t* d_err, void* stream);
 
 /* ---- introspection (tests / profiling) --------------------------------------------------- */
-/* Named internal device buffers: "image_embeds" (fp32 B*N*D), "maps" (fp32 post-process maps),
- * "crf_q", "P", "dP", "crf_M" (int32 [2][B+1] lattice id bases), ... */
+/* Named internal device buffers: "image_embeds" (fp32 B*N*D), "text_hidden" (fp32 B*L*H: last_hidden_state of the most recent
+ * text pass, multimodal or text-only), "maps" (fp32 post-process maps), "crf_q", "P", "dP", "crf_M" (int32 [2][B+1] lattice id
+ * bases), ... */
 int pnp_get_buffer(pnp_engine* e, const char* name, void** d_ptr, size_t* bytes);
 /* Live kernel timing for bench.py's roofline line: while enabled, every launch of the dominant
  * kernel family (the dense NT GEMMs with M = B*N rows: gemm_nt_x3_kernel<EPI> in the benchmarked split-bf16 mode

@@ -119,8 +119,9 @@ def make_weights_sync(args, rank, world_size):
         dist.all_gather(every, dg)
         if flat.is_cuda:
             torch.cuda.synchronize()
-        info.update(mode=args.weights_sync, bytes=int(flat.numel()) * 4, ms=1e3 * (time.perf_counter() - t0),
-                    digest=[int(v) for v in dg.cpu()])
+        # (build_model calls this twice: the weights of the GradCAM path, then the small buffer of the optional ITC projections)
+        info.update(mode=args.weights_sync, bytes=info.get("bytes", 0) + int(flat.numel()) * 4,
+                    ms=info.get("ms", 0.0) + 1e3 * (time.perf_counter() - t0), digest=info.get("digest", [int(v) for v in dg.cpu()]))
         bad = [r for r, d in enumerate(every) if not torch.equal(d, every[0])]
         if bad:
             raise SystemExit(f"rank {rank}: weights differ from rank 0's on rank(s) {bad} after --weights_sync {args.weights_sync} "

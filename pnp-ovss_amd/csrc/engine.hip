@@ -88,6 +88,11 @@ struct pnp_engine {
     std::vector<VitLayerW> vit;
     float *word = nullptr, *tpos = nullptr, *eln_w = nullptr, *eln_b = nullptr, *itm_w = nullptr, *itm_b = nullptr;
     std::vector<TextLayerW> txt;
+    // optional ITC projections, [0] vision_proj (D -> E), [1] text_proj (H -> E) (B/blip_image_text_matching.py:54-55): present when
+    // the state dict carried weight and bias; E is read from the weight's first dimension
+    void* proj_w[2] = {nullptr, nullptr};
+    float* proj_b[2] = {nullptr, nullptr};
+    int proj_E[2] = {0, 0};
     void *ck_w = nullptr, *cv_w = nullptr;     // cross K / V weights of all layers: [TL*H, D]
     float *ck_b = nullptr, *cv_b = nullptr;    // [TL*H]
     std::vector<Buf> staging;                  // fp32 staging of GEMM weights until finalize
@@ -113,6 +118,7 @@ struct pnp_engine {
     void *d_preT = nullptr, *dg = nullptr, *d_cpreT = nullptr, *dctxc = nullptr, *dqc = nullptr, *d_apreT = nullptr,
          *dqkv = nullptr;
     int grad_layer = -1;       // text layer whose dL/dP the dPc buffer currently holds (-1: none)
+    bool acts_text_only = false;   // the text activations in place are those of pnp_text_forward_text (no cross-attention: no backward)
     // drop loop
     float* G = nullptr;
     uint8_t* dropped = nullptr;
@@ -350,7 +356,7 @@ extern "C" size_t pnp_workspace_bytes(const pnp_config* c) {
                  I = c->txt_inter, TL = c->txt_layers, B = c->max_batch, L = c->max_text_len;
     const size_t M = B * N, R = B * L;
     size_t w = (size_t)c->vit_depth * (12 * D * D) * es + TL * (4 * H * H + 2 * H * D + 2 * H * I) * es * 2 +
-               ((size_t)c->vocab + c->max_pos) * H * 4;
+               ((size_t)c->vocab + c->max_pos) * H * 4 + 256 * (D + H) * es + 2 * 256 * 4;      // (incl. the optional ITC projections)
     size_t a = M * (768 + D * 2 + 3 * D + 64 + D + 4 * D) * es + M * D * 12 + D * B * Npad * es + M * TL * H * es * 2 +
                2 * TL * H * B * Npad * es;            // (incl. the padded q|k|v rows and the drop loop's copy of the token embeddings)
     size_t t = TL * (R * (3 * H + 2 * H) * es + R * (H * 8 + I) * 4 + B * (H / 64) * L * (L + Npad) * 4) + R * I * (4 + es) * 2 +
@@ -521,6 +527,7 @@ static int create_impl(const pnp_config* cfg, pnp_engine* donor, pnp_engine** ou
         e->patch_w = donor->patch_w; e->ck_w = donor->ck_w; e->cv_w = donor->cv_w;
         e->vit = donor->vit;
         e->txt = donor->txt;
+        for (int i = 0; i < 2; i++) { e->proj_w[i] = donor->proj_w[i]; e->proj_b[i] = donor->proj_b[i]; e->proj_E[i] = donor->proj_E[i]; }
         e->finalized = true;
         return PNP_OK;
     }
@@ -635,6 +642,30 @@ bool resolve(pnp_engine* e, const std::string& n, Slot& s) {
     return false;
 }
 
+// the optional ITC projections: 1 = `name` is one of the four tensors (staged like a GEMM weight until finalize), 0 = it is
+// not, < 0 = its shape contradicts the model.  The embedding width E is the weight's first dimension.
+int resolve_proj(pnp_engine* e, const std::string& n, const int64_t* shape, int ndim, Slot& s) {
+    int which = -1;
+    bool bias = false;
+    if (n == "vision_proj.weight") which = 0;
+    else if (n == "vision_proj.bias") which = 0, bias = true;
+    else if (n == "text_proj.weight") which = 1;
+    else if (n == "text_proj.bias") which = 1, bias = true;
+    else return 0;
+    const int K = which == 0 ? e->D : e->H;
+    if (ndim != (bias ? 1 : 2) || (!bias && shape[1] != K))
+        return fail(e, PNP_ERR_ARG, "%s: expected %s, second dimension %d", n.c_str(), bias ? "a vector" : "a matrix", K);
+    const int64_t E = shape[0];
+    if (E <= 0 || E > 1024 || E % 64) return fail(e, PNP_ERR_ARG, "%s: embedding width %lld must be a multiple of 64 up to 1024", n.c_str(), (long long)E);
+    if (e->proj_E[which] && e->proj_E[which] != (int)E)
+        return fail(e, PNP_ERR_ARG, "%s: %lld rows, but the other tensor of this projection has %d", n.c_str(), (long long)E, e->proj_E[which]);
+    e->proj_E[which] = (int)E;
+    s.gemm = true;
+    s.rows = (int)E;
+    s.cols = bias ? 1 : K;
+    return 1;
+}
+
 }  // namespace
 
 extern "C" int pnp_load_weight(pnp_engine* e, const char* name, const float* data, const int64_t* shape, int32_t ndim,
@@ -644,7 +675,9 @@ extern "C" int pnp_load_weight(pnp_engine* e, const char* name, const float* dat
     if (e->finalized) return fail(e, PNP_ERR_STATE, "weights already finalized");
     HIPCHK(e, hipSetDevice(e->c.device));
     Slot s;
-    if (!resolve(e, name, s)) return PNP_OK;          // strict=False: not a tensor of this path
+    const int pj = resolve_proj(e, name, shape, ndim, s);
+    if (pj < 0) return pj;
+    if (!pj && !resolve(e, name, s)) return PNP_OK;   // strict=False: not a tensor of this path
     size_t count = 1;
     for (int i = 0; i < ndim; i++) count *= (size_t)shape[i];
     if (count != (size_t)s.rows * s.cols) return fail(e, PNP_ERR_ARG, "%s: expected %d elements, got %zu", name, s.rows * s.cols, count);
@@ -763,6 +796,18 @@ extern "C" int pnp_finalize_weights(pnp_engine* e) {
         }
     }
 #undef NEED
+    // the optional ITC projections: converted like every other Linear weight when weight and bias both arrived
+    for (int i = 0; i < 2; i++) {
+        const std::string b = i == 0 ? "vision_proj." : "text_proj.";
+        const float *w = stage(b + "weight"), *bs = stage(b + "bias");
+        if (!w || !bs) {
+            e->proj_E[i] = 0;
+            continue;
+        }
+        KCHK(e, make_weight(e, w, e->proj_E[i], i == 0 ? D : H, false, &e->proj_w[i], e->x3));
+        KCHK(e, dalloc(e, &e->proj_b[i], (size_t)e->proj_E[i]));
+        HIPCHK(e, hipMemcpy(e->proj_b[i], bs, (size_t)e->proj_E[i] * 4, hipMemcpyDeviceToDevice));
+    }
     HIPCHK(e, hipDeviceSynchronize());
     for (auto& b : e->staging) if (b.p) (void)hipFree(b.p);
     e->staging.clear();
@@ -981,6 +1026,7 @@ static int text_forward_impl(pnp_engine* e, const int64_t* d_ids, const int64_t*
     const int H = e->H, I = e->I, TL = e->TL, R = B * L, bf = e->bf, N = e->N, D = e->D;
     const int ldv = e->c.max_batch * e->Npad;
     (void)D;
+    e->acts_text_only = false;
     if (reuse_prefix && !(e->reuse.text && e->reuse.ids == d_ids && e->reuse.mask == d_mask && e->reuse.B == B && e->reuse.L == L &&
                           e->reuse.ld == ld))
         reuse_prefix = false;                    // not the captions whose prefix is in place: compute it
@@ -1040,6 +1086,112 @@ static int text_forward_impl(pnp_engine* e, const int64_t* d_ids, const int64_t*
     return PNP_OK;
 }
 
+// BertModel.forward(mode="text") (B/med.py:565-568, 473): the text stack without its cross-attention sub-layers and without the
+// [ENC] substitution, for T texts that need no image.  Runs in the multimodal pass's activation buffers (temb, h0, tmp, ctx_s, g and
+// each layer's qkv / a_out / h_out with their compute-type copies; no stash is written), max_batch rows of text at a time, so what
+// those buffers held for a GradCAM backward is gone: the reuse record, the kept layer and the backward are invalidated.  image_embeds
+// and the cross K / V of the last pnp_vit_forward are not touched.
+extern "C" int pnp_text_forward_text(pnp_engine* e, const int64_t* d_ids, const int64_t* d_mask, int32_t ld, int32_t T, int32_t L,
+                                     float* d_hidden, void* stream) {
+    if (!e || !d_ids || !d_mask) return PNP_ERR_ARG;
+    if (T <= 0 || L < 2 || L > e->c.max_text_len || ld < L)
+        return fail(e, PNP_ERR_ARG, "text batch %d x %d (ld %d) out of range (2 <= L <= %d, T > 0)", T, L, ld, e->c.max_text_len);
+    if (!e->finalized) return fail(e, PNP_ERR_STATE, "weights not finalized");
+    hipStream_t s = (hipStream_t)stream;
+    const int H = e->H, I = e->I, TL = e->TL, bf = e->bf;
+    e->reuse.text = false;
+    e->grad_layer = -1;
+    e->acts_text_only = true;
+    for (int t0 = 0; t0 < T; t0 += e->c.max_batch) {
+        const int B = T - t0 < e->c.max_batch ? T - t0 : e->c.max_batch, R = B * L;
+        const int64_t* ids = d_ids + (size_t)t0 * ld;
+        const int64_t* mask = d_mask + (size_t)t0 * ld;
+        KCHK(e, text_embed(ids, ld, e->word, e->tpos, e->temb, B, L, H, -1, e->c.vocab, s));
+        KCHK(e, layernorm(bf, e->temb, e->eln_w, e->eln_b, e->c.txt_ln_eps, R, H, e->h0, e->h0T, nullptr, nullptr, s));
+        const float* h = e->h0;
+        const void* hT = e->h0T;
+        for (int i = 0; i < TL; i++) {
+            const TextLayerW& w = e->txt[i];
+            TextLayerA& a = e->ta[i];
+            {
+                GemmArgs g = G_(hT, H, w.qkv_w, H, R, 3 * H, H);
+                g.bias = w.qkv_b; g.out_t = a.qkv; g.ldo_t = 3 * H;
+                KCHK(e, tgemm(e, g, s));
+            }
+            KCHK(e, text_self_attn(bf, a.qkv, mask, ld, e->ctx_s, nullptr, e->dS, B, L, H, s));
+            {
+                GemmArgs g = G_(e->ctx_s, H, w.so_w, H, R, H, H);
+                g.bias = w.so_b; g.resid = h; g.ldr = H; g.out_f32 = e->tmp; g.ldo = H;
+                KCHK(e, tgemm(e, g, s));
+            }
+            KCHK(e, layernorm(bf, e->tmp, w.sln_w, w.sln_b, e->c.txt_ln_eps, R, H, a.a_out, a.a_outT, nullptr, nullptr, s));
+            {
+                GemmArgs g = G_(a.a_outT, H, w.i_w, H, R, I, H);
+                g.bias = w.i_b; g.mode = GEMM_EPI_GELU; g.out_t = e->g; g.ldo_t = I;
+                KCHK(e, tgemm(e, g, s));
+            }
+            {
+                GemmArgs g = G_(e->g, I, w.o_w, I, R, H, I);
+                g.bias = w.o_b; g.resid = a.a_out; g.ldr = H; g.out_f32 = e->tmp; g.ldo = H;
+                KCHK(e, tgemm(e, g, s));
+            }
+            KCHK(e, layernorm(bf, e->tmp, w.oln_w, w.oln_b, e->c.txt_ln_eps, R, H, a.h_out, a.h_outT, nullptr, nullptr, s));
+            h = a.h_out;
+            hT = a.h_outT;
+        }
+        if (d_hidden)
+            HIPCHK(e, hipMemcpyAsync(d_hidden + (size_t)t0 * L * H, h, (size_t)R * H * sizeof(float), hipMemcpyDeviceToDevice, s));
+    }
+    return PNP_OK;
+}
+
+// F.normalize(Linear(x), dim=-1) with vision_proj (which = 0) or text_proj (which = 1) (B/blip_image_text_matching.py:137-138,
+// 158-159, 260-263): the Linear is one launch of the mode's GEMM (exact fp32 MFMA | split-bf16 with the fp32 rows split by the
+// kernel | bf16 after a cast of the rows into the ViT's LayerNorm scratch) with fp32 output, then l2_normalize_rows in place.
+extern "C" int pnp_project_normalize(pnp_engine* e, int32_t which, const float* d_x, int64_t row_stride, int32_t rows, float* d_out,
+                                     void* stream) {
+    if (!e || !d_x || !d_out) return PNP_ERR_ARG;
+    if (which < 0 || which > 1) return fail(e, PNP_ERR_ARG, "which = %d: 0 (vision_proj) or 1 (text_proj)", which);
+    if (rows <= 0) return fail(e, PNP_ERR_ARG, "rows = %d", rows);
+    const int K = which == 0 ? e->D : e->H;
+    if (row_stride < K || row_stride % 4 || row_stride > (int64_t)1 << 30)
+        return fail(e, PNP_ERR_ARG, "row_stride %lld: a multiple of 4 elements, at least %d", (long long)row_stride, K);
+    // the GEMM kernels address an operand by 32-bit byte offsets from its base
+    if ((int64_t)rows * row_stride * 4 >= (int64_t)1 << 32)
+        return fail(e, PNP_ERR_ARG, "rows %d x row_stride %lld: the input must span less than 4 GiB", rows, (long long)row_stride);
+    if (!e->finalized) return fail(e, PNP_ERR_STATE, "weights not finalized");
+    if (!e->proj_w[which] || !e->proj_b[which])
+        return fail(e, PNP_ERR_STATE, "missing weight %s (the state dict held no %s.weight / .bias)", which == 0 ? "vision_proj.weight" : "text_proj.weight",
+                    which == 0 ? "vision_proj" : "text_proj");
+    hipStream_t s = (hipStream_t)stream;
+    const int E = e->proj_E[which];
+    if (e->bf) {
+        // bf16 operands: rows are cast into xn (free between ViT forwards), as many at a time as it holds
+        size_t cap = (size_t)e->c.max_batch * e->N * e->D / K;
+        cap = cap < 16384 ? cap : 16384;           // (and few enough for the generic tiles: the wide bf16 kernel has no such epilogue)
+        for (size_t r0 = 0; r0 < (size_t)rows; r0 += cap) {
+            const int n = (int)((size_t)rows - r0 < cap ? (size_t)rows - r0 : cap);
+            KCHK(e, cast_rows_bf16(d_x + r0 * row_stride, (int)row_stride, e->xn, n, K, s));
+            GemmArgs g = G_(e->xn, K, e->proj_w[which], K, n, E, K);
+            g.bias = e->proj_b[which]; g.out_f32 = d_out + r0 * E; g.ldo = E;
+            KCHK(e, egemm(e, 1, g, s));
+        }
+    } else {
+        GemmArgs g = G_(d_x, (int)row_stride, e->proj_w[which], K, rows, E, K);
+        g.bias = e->proj_b[which]; g.out_f32 = d_out; g.ldo = E;
+        KCHK(e, tgemm(e, g, s));
+    }
+    KCHK(e, l2_normalize_rows(d_out, rows, E, 1e-12f, s));
+    return PNP_OK;
+}
+
+// sim = image_feat @ text_feat.t() (B/blip_image_text_matching.py:265).  Stateless.
+extern "C" int pnp_itc_similarity(const float* d_img_feat, const float* d_txt_feat, int32_t B, int32_t T, int32_t E, float* d_sim,
+                                  void* stream) {
+    if (!d_img_feat || !d_txt_feat || !d_sim || B <= 0 || T <= 0 || E <= 0 || E % 4) return PNP_ERR_ARG;
+    return itc_similarity(d_img_feat, d_txt_feat, d_sim, B, T, E, (hipStream_t)stream);
+}
+
 extern "C" int pnp_xattn_grad(pnp_engine* e, int32_t B, int32_t L, void* stream) {
     return pnp_xattn_grad_layer(e, B, L, e ? e->SL : 0, stream);
 }
@@ -1050,6 +1202,8 @@ extern "C" int pnp_xattn_grad_layer(pnp_engine* e, int32_t B, int32_t L, int32_t
     if (B <= 0 || B > e->c.max_batch || L < 5 || L > e->c.max_text_len) return fail(e, PNP_ERR_ARG, "bad B/L");
     if (layer < e->SL || layer >= e->TL)
         return fail(e, PNP_ERR_ARG, "layer %d: cross-attention maps are kept for text layers %d..%d (stash_layer)", layer, e->SL, e->TL - 1);
+    if (e->acts_text_only)
+        return fail(e, PNP_ERR_STATE, "the text activations in place are those of pnp_text_forward_text: run pnp_text_forward_xattn first");
     hipStream_t s = (hipStream_t)stream;
     const int H = e->H, I = e->I, TL = e->TL, R = B * L, bf = e->bf, N = e->N, SL = e->SL;
     const int ldv = e->c.max_batch * e->Npad, nVn = TL - SL;
@@ -1627,6 +1781,7 @@ extern "C" int pnp_get_buffer(pnp_engine* e, const char* name, void** d_ptr, siz
     if (n == "x") return set(e->x, B * e->N * (size_t)e->D * 4);
     if (n == "P") return set(e->ta[e->grad_layer >= 0 ? e->grad_layer : e->SL].Pc, B * e->nh * L * (size_t)e->Nst * 4);
     if (n == "dP") return set(e->dPc, B * e->nh * L * (size_t)e->Nst * 4);
+    if (n == "text_hidden") return set(e->ta[e->TL - 1].h_out, B * L * (size_t)e->H * 4);
     if (n == "h_last") return set(e->ta[e->TL - 1].h_out, B * L * (size_t)e->H * 4);
     if (n == "dropped") return set(e->dropped, B * (size_t)e->PP);
     if (n == "P_last" && e->ta[e->TL - 1].Pc) return set(e->ta[e->TL - 1].Pc, B * e->nh * L * (size_t)e->Nst * 4);

@@ -70,6 +70,7 @@ int vit_attention_x3(const void* qkv_hi, const void* qkv_lo, int ld_qk, int D, v
                      float scale, hipStream_t s);
 
 // text_kernels.hip
+// enc_id >= 0: column 0 of every row is replaced by that id ([ENC], the multimodal pass); enc_id < 0: column 0 kept as given
 int text_embed(const int64_t* ids, int ld_ids, const float* word, const float* pos, float* out, int B, int L, int H,
                int enc_id, int vocab, hipStream_t s);
 // scratch: [B, heads, L, L] floats, used when L > 192 and probs is null (the long-caption form passes a row's probabilities
@@ -86,6 +87,11 @@ int itm_head(const float* hlast, const float* w, const float* bias, float* logit
 int itm_grad_seed(const float* w, float* dh, int B, int L, int H, hipStream_t s);
 int cast_f32(int bf, const float* in, void* out, size_t n, hipStream_t s);
 int split_f32(const float* in, void* hi, void* lo, size_t n, hipStream_t s);     // x ~ hi + lo, both bf16 (round to nearest even)
+
+// itc_kernels.hip
+int l2_normalize_rows(float* x, int rows, int E, float eps, hipStream_t s);                  // in place: x / max(||x||_2, eps)
+int itc_similarity(const float* img, const float* txt, float* sim, int B, int T, int E, hipStream_t s);   // sim = img . txt^T, fp32 FMA
+int cast_rows_bf16(const float* in, int ld_in, void* out, int rows, int K, hipStream_t s);   // strided fp32 rows -> contiguous bf16
 
 // pipeline_kernels.hip
 int gradcam_gather(const float* P, const float* dP, const int64_t* mask, int ld_mask, float* out, int B, int nheads,

@@ -13,7 +13,8 @@
 namespace pnp {
 
 // ------------------------------------------------------------------------------------------
-// word + position embeddings (token 0 of every caption is replaced by [ENC]).
+// word + position embeddings (token 0 of every caption is replaced by [ENC]; enc_id < 0 keeps it: the text-only pass of
+// med.py:565-568 mode="text").
 __global__ void text_embed_kernel(const int64_t* __restrict__ ids, int ld_ids, const float* __restrict__ word,
                                   const float* __restrict__ pos, float* __restrict__ out, int B, int L, int H,
                                   int enc_id, int vocab) {
@@ -22,7 +23,7 @@ __global__ void text_embed_kernel(const int64_t* __restrict__ ids, int ld_ids, c
     if (idx >= B * L * hv) return;
     const int c = idx % hv, row = idx / hv;
     const int b = row / L, l = row - b * L;
-    int64_t id = l == 0 ? (int64_t)enc_id : ids[(size_t)b * ld_ids + l];
+    int64_t id = (l == 0 && enc_id >= 0) ? (int64_t)enc_id : ids[(size_t)b * ld_ids + l];
     id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
     const f32x4 w = reinterpret_cast<const f32x4*>(word + (size_t)id * H)[c];
     const f32x4 p = reinterpret_cast<const f32x4*>(pos + (size_t)l * H)[c];

@@ -1,3 +1,3 @@
-"""`compute_gradcam_ensemble` under its reference import path
-(Files to replace for BLIP/blip_image_text_matching.py:386)."""
-from pnp_ovss.model import BlipITM, compute_gradcam_ensemble  # noqa: F401
+"""`BlipITM`, `compute_gradcam_ensemble` and `BlipOutputFeatures` (the return type of BlipITM.extract_features) under their
+reference import path (Files to replace for BLIP/blip_image_text_matching.py:386, :183)."""
+from pnp_ovss.model import BlipITM, BlipOutputFeatures, compute_gradcam_ensemble  # noqa: F401

@@ -59,6 +59,9 @@ def load_library():
         "pnp_vit_forward": (i32, [vp, vp, vp, i32, vp]),
         "pnp_cross_kv": (i32, [vp, i32, vp]),
         "pnp_text_forward_xattn": (i32, [vp, vp, vp, i32, i32, i32, vp, vp]),
+        "pnp_text_forward_text": (i32, [vp, vp, vp, i32, i32, i32, vp, vp]),
+        "pnp_project_normalize": (i32, [vp, i32, vp, i64, i32, vp, vp]),
+        "pnp_itc_similarity": (i32, [vp, vp, i32, i32, i32, vp, vp]),
         "pnp_xattn_grad": (i32, [vp, i32, i32, vp]),
         "pnp_xattn_grad_layer": (i32, [vp, i32, i32, i32, vp]),
         "pnp_compute_gradcam_layer": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]),
@@ -115,7 +118,10 @@ EXPORTED = ["pnp_create", "pnp_create_shared", "pnp_destroy", "pnp_last_error", 
             "pnp_cross_kv", "pnp_profile_read_stage", "pnp_op_split", "pnp_op_gemm_x3", "pnp_op_gemm_x3a",
             "pnp_xattn_grad_layer", "pnp_compute_gradcam_layer", "pnp_drop_loop_layer", "pnp_allocated_bytes",
             "pnp_op_vit_attention_x3", "pnp_jpeg_decode", "pnp_op_sort_pairs", "pnp_op_scan_i32", "pnp_set_tuning",
-            "pnp_streamk_status"]
+            "pnp_streamk_status", "pnp_text_forward_text", "pnp_project_normalize", "pnp_itc_similarity"]
+
+
+PROJ_NAMES = ("vision_proj.weight", "vision_proj.bias", "text_proj.weight", "text_proj.bias")      # the optional ITC projections
 
 
 class _DevView:
@@ -317,6 +323,8 @@ class Engine:
             raise RuntimeError(f"pnp_create{'_shared' if share_weights_with is not None else ''} failed ({r}): {msg}")
         self.shares_weights = share_weights_with is not None
         self._keep = []
+        # ITC projections this engine holds: name -> embedding width (load_state_dict fills it; a sharing engine has the donor's)
+        self.proj_loaded = dict(share_weights_with.proj_loaded) if share_weights_with is not None else {}
 
     # ------------------------------------------------------------------ plumbing
     def _chk(self, r, what):
@@ -356,6 +364,8 @@ class Engine:
                 shape = (C.c_int64 * a.ndim)(*a.shape)
                 r = self.lib.pnp_load_weight(self.h, name.encode(), C.c_void_p(a.ctypes.data), shape, a.ndim, 0)
             self._chk(r, f"pnp_load_weight({name})")
+            if name in PROJ_NAMES:
+                self.proj_loaded[name] = int(w.shape[0])
         if finalize:
             self._chk(self.lib.pnp_finalize_weights(self.h), "pnp_finalize_weights")
 
@@ -373,6 +383,43 @@ class Engine:
         self._chk(self.lib.pnp_text_forward_xattn(self.h, _ptr(ids), _ptr(mask), ld, B, L, _ptr(logits), _stream()),
                   "pnp_text_forward_xattn")
         return logits
+
+    # ------------------------------------------------------------------ ITC head / feature extraction
+    def missing_proj(self, which=(0, 1)):
+        """Names of the projection tensors the entry points below need and this engine was not given."""
+        need = [n for w in which for n in PROJ_NAMES[2 * w: 2 * w + 2]]
+        return [n for n in need if n not in self.proj_loaded]
+
+    def text_forward_text(self, ids, mask, L, want_hidden=True):
+        """BertModel.forward(mode="text"): ids / mask (T, ld) int64, T may exceed max_batch -> last_hidden_state (T, L, H)."""
+        T, ld = ids.shape
+        hid = torch.empty(T, L, self.cfg.txt_hidden, device=self.device, dtype=torch.float32) if want_hidden else None
+        self._chk(self.lib.pnp_text_forward_text(self.h, _ptr(ids), _ptr(mask), ld, T, L, _ptr(hid), _stream()),
+                  "pnp_text_forward_text")
+        return hid
+
+    def project_normalize(self, which, x, row_stride=None, rows=None):
+        """F.normalize(vision_proj | text_proj (x), dim=-1): which = 0 / 1 or "vision" / "text"; x a contiguous fp32 device
+        tensor whose rows are row_stride elements apart (default: its last dimension, every row) -> (rows, E)."""
+        which = {"vision": 0, "text": 1}.get(which, which)
+        K = self.cfg.vit_dim if which == 0 else self.cfg.txt_hidden
+        row_stride = K if row_stride is None else int(row_stride)
+        rows = x.numel() // row_stride if rows is None else int(rows)
+        assert x.dtype == torch.float32 and (rows - 1) * row_stride + K <= x.numel(), "rows reach past the tensor"
+        E = self.proj_loaded.get(PROJ_NAMES[2 * which], 256) if which in (0, 1) else 256
+        out = torch.empty(max(rows, 0), E, device=self.device, dtype=torch.float32)
+        self._chk(self.lib.pnp_project_normalize(self.h, which, _ptr(x), row_stride, rows, _ptr(out), _stream()),
+                  "pnp_project_normalize")
+        return out
+
+    def itc_similarity(self, img_feat, txt_feat):
+        """image_feat @ text_feat.t() in fp32: (B, E), (T, E) -> (B, T)."""
+        B, E = img_feat.shape
+        T = txt_feat.shape[0]
+        assert txt_feat.shape[1] == E and img_feat.dtype == txt_feat.dtype == torch.float32
+        sim = torch.empty(B, T, device=self.device, dtype=torch.float32)
+        self._chk(self.lib.pnp_itc_similarity(_ptr(img_feat), _ptr(txt_feat), B, T, E, _ptr(sim), _stream()), "pnp_itc_similarity")
+        return sim
 
     def xattn_grad(self, B, L, layer=None):
         """Backward down to `layer` (default: stash_layer); gradcam_gather / buffer("P") / buffer("dP") then refer to it."""

@@ -13,8 +13,10 @@ Reference surface kept:
     save_img_union_attention's device work                          (PnP.py:290-521, 564-722)
 There is no eager / CPU fallback: every tensor op below is plumbing around pnp_ovss.hip.Engine.
 """
+import dataclasses
 import os
 import warnings
+from typing import Optional
 
 import numpy as np
 import torch
@@ -51,6 +53,18 @@ class _CrossSelf:
 
 class _Obj:
     pass
+
+
+@dataclasses.dataclass
+class BlipOutputFeatures:
+    """Return value of BlipITM.extract_features: the five LAVIS field names (lavis/models/blip_models/blip_outputs.py).  The
+    reference's file uses the name without importing it (blip_image_text_matching.py:183 against :1-16), so this is the class
+    its users get from the lavis shim."""
+    image_embeds: Optional[torch.Tensor] = None
+    image_embeds_proj: Optional[torch.Tensor] = None
+    text_embeds: Optional[torch.Tensor] = None
+    text_embeds_proj: Optional[torch.Tensor] = None
+    multimodal_embeds: Optional[torch.Tensor] = None
 
 
 MAX_TEXT_TOKENS = 512        # longest caption the text kernels take (csrc/text_kernels.hip TXT_LONG_L = BERT's max_position_embeddings;
@@ -150,7 +164,7 @@ class BlipITM(torch.nn.Module):
                      stash_layer=int(stash_layer), mode=lz["mode"], device=self._device.index or 0)
         flat = self.weights_flat
         sd = {}
-        for n, (o, shp) in lz["index"].items():
+        for n, (o, shp) in lz["index"].items():                    # (the ITC projections, when the model has them, are in the index too)
             sd[n] = flat[o:o + int(np.prod(shp))].view(*shp)
         sd["visual_encoder.pos_embed"] = _resize_pos_embed(self.pos_embed_raw.cpu(), cfg.grid).to(flat.device)   # base_model.py:108-110
         eng.load_state_dict(sd)
@@ -171,34 +185,105 @@ class BlipITM(torch.nn.Module):
         return self.tokenizer(captions, padding="longest", truncation=True, max_length=self.max_txt_len,
                               return_tensors="pt")
 
+    def _need_multimodal(self):
+        if self._last is None:
+            raise RuntimeError("no multimodal forward is in place (none was run, or a text-only pass -- forward(match_head=\"itc\"), "
+                               "extract_features(mode=\"text\") -- has since used the engine's text activations): run forward / "
+                               "compute_gradcam_ensemble first")
+
     def _grad_to(self, layer):
         """Make P / dP / gradcam_gather refer to `layer`: the analytic backward re-run down to it when the last one
         stopped elsewhere (activations of the forward are still in the engine)."""
+        self._need_multimodal()
         if self._grad_layer != layer:
             B, L = self._last
             self.engine.xattn_grad(B, L, layer)
             self._grad_layer = layer
 
     def _stash(self, name):
+        self._need_multimodal()
         B, L = self._last
         N, nst = self.cfg.n_img_tokens, (self.cfg.n_img_tokens + 63) // 64 * 64
         flat = self.engine.buffer(name)
         return flat[: B * self.cfg.txt_heads * L * nst].view(B, self.cfg.txt_heads, L, nst)[..., :N]
 
     def forward(self, samples, match_head="itm"):
-        """BlipITM.forward(match_head="itm") (blip_image_text_matching.py:217-249) -> logits (B,2)."""
-        if match_head != "itm":
-            raise NotImplementedError("only the ITM head is on the hot path")
+        """BlipITM.forward (blip_image_text_matching.py:217-266): match_head="itm" -> logits (B, 2); match_head="itc" -> the
+        cosine similarities image_feat @ text_feat.t() (B, B) of the projected, normalised CLS rows (:253-266)."""
+        if match_head not in ("itm", "itc"):
+            raise ValueError(f"match_head must be \"itm\" or \"itc\", got {match_head!r}")
         text = self._tok_longest(samples["text_input"])
         L = text.input_ids.shape[1]
         eng = self.ensure_engine(img_size=int(samples["image"].shape[-1]), batch=int(samples["image"].shape[0]), text_len=L)
+        if match_head == "itc":
+            self._need_proj(eng, (0, 1))
         image = samples["image"].to(self.device, torch.float32).contiguous()
         text = text.to(self.device)
+        B = image.shape[0]
         eng.vit_forward(image)
+        if match_head == "itc":
+            self._last = self._grad_layer = None                   # the text-only pass runs in the multimodal pass's buffers
+            hid = eng.text_forward_text(text.input_ids.contiguous(), text.attention_mask.contiguous(), L)
+            N, D = self.cfg.n_img_tokens, self.cfg.vit_dim
+            img_feat = eng.project_normalize(0, eng.buffer("image_embeds"), row_stride=N * D, rows=B)       # image_embeds[:, 0, :]
+            txt_feat = eng.project_normalize(1, hid, row_stride=L * self.cfg.txt_hidden, rows=hid.shape[0])  # last_hidden_state[:, 0, :]
+            return eng.itc_similarity(img_feat, txt_feat)
         logits = eng.text_forward(text.input_ids.contiguous(), text.attention_mask.contiguous(), L)
-        self._last = (image.shape[0], L)
+        self._last = (B, L)
         self._grad_layer = None
         return logits
+
+    @staticmethod
+    def _need_proj(eng, which):
+        missing = eng.missing_proj(which)
+        if missing:
+            raise RuntimeError(f"the engine was given no {', '.join(missing)}: the checkpoint / seed this model was built from "
+                               f"provided no ITC projection weights")
+
+    @torch.no_grad()
+    def extract_features(self, samples, mode="multimodal"):
+        """BlipITM.extract_features (blip_image_text_matching.py:59-189) -> BlipOutputFeatures.
+        "image": image_embeds (B, N, D) and the normalised vision_proj features of ALL tokens (B, N, 256); "text": the text-only
+        pass's last_hidden_state (B, L, H) and its text_proj features (B, L, 256); "multimodal": image_embeds and the multimodal
+        pass's last_hidden_state ([ENC] at column 0).  The reference's tokenizer call: padding=True, no truncation."""
+        if mode not in ("image", "text", "multimodal"):
+            raise ValueError("mode must be one of 'image', 'text', 'multimodal'")
+        image, caption = samples.get("image"), samples.get("text_input")
+        if mode != "text" and image is None:
+            raise ValueError("Image is not provided for mode 'image' or 'multimodal'")
+        if mode != "image" and caption is None:
+            raise ValueError("text input is None for mode 'text' or 'multimodal'")
+        text, L = None, None
+        if mode != "image":
+            text = self.tokenizer(caption, return_tensors="pt", padding=True)
+            L = text.input_ids.shape[1]
+        eng = self.ensure_engine(img_size=int(image.shape[-1]) if mode != "text" else None,
+                                 batch=int(image.shape[0]) if mode != "text" else None, text_len=L)
+        out = BlipOutputFeatures()
+        N, D, H = self.cfg.n_img_tokens, self.cfg.vit_dim, self.cfg.txt_hidden
+        if mode == "text":
+            self._need_proj(eng, (1,))
+            text = text.to(self.device)
+            self._last = self._grad_layer = None
+            hid = eng.text_forward_text(text.input_ids.contiguous(), text.attention_mask.contiguous(), L)
+            out.text_embeds = hid
+            out.text_embeds_proj = eng.project_normalize(1, hid).view(hid.shape[0], L, -1)
+            return out
+        if mode == "image":
+            self._need_proj(eng, (0,))
+        image = image.to(self.device, torch.float32).contiguous()
+        B = image.shape[0]
+        eng.vit_forward(image)
+        out.image_embeds = eng.buffer("image_embeds")[: B * N * D].view(B, N, D).clone()
+        if mode == "image":
+            out.image_embeds_proj = eng.project_normalize(0, out.image_embeds).view(B, N, -1)
+            return out
+        text = text.to(self.device)
+        eng.text_forward(text.input_ids.contiguous(), text.attention_mask.contiguous(), L)       # puts [ENC] at column 0 itself
+        self._last = (B, L)
+        self._grad_layer = None
+        out.multimodal_embeds = eng.buffer("text_hidden")[: B * L * H].view(B, L, H).clone()
+        return out
 
 
 def _call_geometry(args, m, image, L):
@@ -323,6 +408,56 @@ def merge_checkpoint(cfg, ckpt_state, init_state):
     return state, dropped, missing
 
 
+def select_itc_weights(cfg, ckpt_state, seed):
+    """The optional ITC projections (synth.itc_param_shapes) a model is built with, as a pure host function -> (tensors, note).
+    With a checkpoint: each projection (weight + bias) whose two tensors are present with the model's shapes is taken from it,
+    any other is left out and named in `note` (the engine then refuses the ITC entry points by name; nothing is invented next to
+    trained weights).  Without a checkpoint: the seeded tensors, like every other weight."""
+    shapes = synth.itc_param_shapes(cfg)
+    if ckpt_state is None:
+        return synth.itc_state_dict(cfg, seed), None
+    out, left = {}, []
+    for proj in ("vision_proj", "text_proj"):
+        names = [proj + ".weight", proj + ".bias"]
+        ok = all(n in ckpt_state and tuple(ckpt_state[n].shape) == tuple(shapes[n]) for n in names)
+        if ok:
+            out.update((n, ckpt_state[n]) for n in names)
+        else:
+            left += [f"{n} ({'shape ' + str(tuple(ckpt_state[n].shape)) if n in ckpt_state else 'not provided'})" for n in names
+                     if not (n in ckpt_state and tuple(ckpt_state[n].shape) == tuple(shapes[n]))]
+    return out, (", ".join(left) if left else None)
+
+
+def _itc_flat(cfg, itc, device):
+    """The second, small flat buffer of a multi-rank start-up: [has vision_proj, has text_proj, the four tensors in
+    itc_param_shapes order (zeros where absent)].  Travels through the same `sync` callable after the main buffer, whose layout
+    and digest it leaves alone."""
+    shapes = synth.itc_param_shapes(cfg)
+    flat = torch.zeros(2 + sum(int(np.prod(s)) for s in shapes.values()), dtype=torch.float32, device=device)
+    if itc is not None:
+        o = 2
+        for n, shp in shapes.items():
+            k = int(np.prod(shp))
+            if n in itc:
+                t = itc[n]
+                flat[o:o + k].copy_(torch.as_tensor(np.asarray(t) if not isinstance(t, torch.Tensor) else t, dtype=torch.float32).reshape(-1))
+            o += k
+        flat[0] = float("vision_proj.weight" in itc)
+        flat[1] = float("text_proj.weight" in itc)
+    return flat
+
+
+def _itc_unflat(cfg, flat):
+    has = flat[:2].cpu().tolist()
+    out, o = {}, 2
+    for n, shp in synth.itc_param_shapes(cfg).items():
+        k = int(np.prod(shp))
+        if has[0 if n.startswith("vision_proj") else 1] != 0:
+            out[n] = flat[o:o + k].view(*shp)
+        o += k
+    return out
+
+
 def _model_config(model_type, img_size):
     """The model yaml of the reference (B/blip_itm_large.yaml + med_large_config.json) as this build reads it: the
     built-in BLIP-ITM-large geometry, or a JSON file of ModelCfg fields named by PNP_OVSS_MODEL_CONFIG (tests: the
@@ -397,12 +532,15 @@ def build_model(model_type="large", img_size=None, device=0, max_batch=None, max
         torch.cuda.set_device(dev)
         flat = torch.empty(sum(int(np.prod(s)) for s in shapes.values()), dtype=torch.float32, device=torch.device("cuda", dev))
         sync(flat)
+        flat_itc = _itc_flat(cfg, None, flat.device)
+        sync(flat_itc)
         eng = Engine(cfg, max_batch=max_batch, max_text_len=max_text_len or 64, stash_layer=stash_layer, device=dev, mode=mode)
         sd, o = {}, 0
         for n, shp in shapes.items():
             k = int(np.prod(shp))
             sd[n] = flat[o:o + k].view(*shp)
             o += k
+        sd.update(_itc_unflat(cfg, flat_itc))
         eng.load_state_dict(sd)
         return BlipITM(cfg, eng, tok)
     init = synth.synth_state_dict(cfg, seed)                      # stands in for the module's initialisation
@@ -417,6 +555,10 @@ def build_model(model_type="large", img_size=None, device=0, max_batch=None, max
     else:
         warnings.warn("no BLIP checkpoint given (PNP_OVSS_CHECKPOINT): using seeded synthetic weights")
         state, raw_pos = init, None
+    itc, itc_note = select_itc_weights(cfg, sd if checkpoint else None, seed)
+    if itc_note:
+        warnings.warn(f"checkpoint {checkpoint}: no usable ITC projection in {itc_note}: forward(match_head=\"itc\") / "
+                      f"extract_features will refuse the calls that need it")
     if eager:
         if sync is not None:
             # one flat device buffer in param_shapes order (what receive_only ranks allocate): the driver's collective runs on it
@@ -432,11 +574,18 @@ def build_model(model_type="large", img_size=None, device=0, max_batch=None, max
                 o += k
             sync(flat)
             state = sd
+            flat_itc = _itc_flat(cfg, itc, flat.device)
+            sync(flat_itc)
+            itc = _itc_unflat(cfg, flat_itc)
         eng = Engine(cfg, max_batch=max_batch, max_text_len=max_text_len or 64, stash_layer=stash_layer, device=dev, mode=mode)
+        state = dict(state)
+        state.update(itc)
         eng.load_state_dict(state)
         return BlipITM(cfg, eng, tok)
     # lazy: fp32 weights in device buffers (what DDP broadcasts), the checkpoint's own pos_embed grid kept for re-tiling
     torch.cuda.set_device(dev)
+    state = dict(state)
+    state.update(itc)
     index, total = {}, 0
     for n, t in state.items():
         if n == "visual_encoder.pos_embed":

@@ -104,6 +104,25 @@ def synth_state_dict(cfg: ModelCfg, seed: int = 0, names=None) -> "OrderedDict[s
     return out
 
 
+ITC_EMBED_DIM = 256          # embed_dim of every BLIP config (blip_image_text_matching.py:39, 302)
+
+
+def itc_param_shapes(cfg: ModelCfg, embed_dim: int = ITC_EMBED_DIM) -> "OrderedDict[str, tuple]":
+    """The ITC projections (blip_image_text_matching.py:54-55).  Kept apart from param_shapes: they are optional (the GradCAM
+    path never reads them), and the flat weight buffer / digest of a multi-rank start-up follow param_shapes."""
+    s = OrderedDict()
+    s["vision_proj.weight"] = (embed_dim, cfg.vit_dim)
+    s["vision_proj.bias"] = (embed_dim,)
+    s["text_proj.weight"] = (embed_dim, cfg.txt_hidden)
+    s["text_proj.bias"] = (embed_dim,)
+    return s
+
+
+def itc_state_dict(cfg: ModelCfg, seed: int = 0, embed_dim: int = ITC_EMBED_DIM) -> "OrderedDict[str, np.ndarray]":
+    """Seeded projections from the same (seed, crc32(name)) generators as synth_state_dict, whose tensors they leave untouched."""
+    return OrderedDict((n, synth_tensor(n, shp, seed)) for n, shp in itc_param_shapes(cfg, embed_dim).items())
+
+
 def synth_checkpoint(cfg_model: ModelCfg, cfg_ckpt: ModelCfg, seed: int = 7) -> "OrderedDict[str, np.ndarray]":
     """A synthetic BLIP checkpoint state dict fine-tuned at another resolution (pos_embed of cfg_ckpt's grid, like the
     384-px flickr checkpoint of blip_itm_large.yaml:10), with the extra heads a real one carries and ONE
