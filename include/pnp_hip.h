@@ -86,7 +86,8 @@ int pnp_vit_forward(pnp_engine* e, const float* d_images, const uint8_t* d_dropp
 int pnp_cross_kv(pnp_engine* e, int32_t B, void* stream);
 /* BertModel.forward(mode="multimodal") + itm_head (B/med.py:854-1024, B/blip_image_text_matching.py:
  * 238-249); stashes the cross-attention probabilities of layers >= stash_layer (B/med.py:280-283).
- * d_ids / d_mask: (B, ld) int64, the first L columns are used (padding="longest"). */
+ * d_ids / d_mask: (B, ld) int64, the first L columns are used (padding="longest").  Ids outside [0, vocab) are clamped to
+ * the nearest valid id; a caption whose mask is all zeros gives finite results (see pnp_op_text_self_attn). */
 int pnp_text_forward_xattn(pnp_engine* e, const int64_t* d_ids, const int64_t* d_mask, int32_t ld, int32_t B,
                            int32_t L, float* d_logits, void* stream);
 /* loss = logits[:,1].sum(); loss.backward() restricted to what reaches attention_probs of
@@ -293,7 +294,12 @@ int pnp_profile_read_stage(pnp_engine* e, int32_t stage, int64_t* launches, doub
  *              model says it pays, 2 = whenever a launch has a partial last round.  Results are deterministic in every
  *              mode (fixed-order fix-up, no atomics) and differ between modes only by fp32 summation order.  Launches on a
  *              stream that is being captured into a hipGraph always take whole tiles (the tail's one-launch-at-a-time event
- *              chain reaches across streams). */
+ *              chain reaches across streams).
+ *   "text_rows": workgroups per (head, image) of the text self-attention launches for captions of 65..192 tokens (B/med.py:
+ *              229-283 self-attention forward and its backward): 0 (default) = chosen per launch from B * heads, L and the CU
+ *              count, 1..4 = that many wherever the choice is made.  The split decides which workgroup computes a row, not one
+ *              operation of its arithmetic: results are bit-identical for every value.  In the fp32 backward 1 selects the
+ *              one-launch form and 2..4 the two-launch form (query-row phase, then key-row phase). */
 int pnp_set_tuning(const char* key, int32_t value);
 /* Launches that used the engine's (e = NULL: the op-level entry points') stream-K workspace, and the give-up word of its
  * bounded spins (0 = no owner ever gave up waiting for a partial tile; anything else is a bug report).  Synchronises. */
@@ -369,6 +375,42 @@ int pnp_op_cast(int32_t to_bf16, const float* d_in, void* d_out, int64_t n, void
 int pnp_op_sort_pairs(uint64_t* d_keys_in, uint64_t* d_keys_out, uint32_t* d_vals_in, uint32_t* d_vals_out, int64_t n,
                       int32_t begin_bit, int32_t end_bit, const size_t* h_seg_off, int32_t n_seg, void* stream);
 int pnp_op_scan_i32(const int32_t* d_in, int32_t* d_out, int64_t n, int32_t inclusive, void* stream);
+/* The text-side kernels as operators (head_dim 64: H = 64 * heads; compute type T = bf16 or fp32 by the first argument).
+ * Non-positive sizes and missing mandatory pointers return PNP_ERR_ARG before any HIP call; nothing is allocated or synchronised.
+ * BertSelfAttention without cross-attention (B/med.py:229-283): d_qkv [B*L, 3H] T (q | k | v), d_mask (B, ld_mask) int64 with
+ * 1 = attend, added as (1 - mask) * -10000 (B/med.py:851); d_ctx [B*L, H] T; d_probs fp32 [B, heads, L, L] or NULL.  L <= 512.
+ * For L > 192 the probabilities pass through global memory: d_probs, else d_scratch (same shape; may be NULL otherwise).
+ * A masked key of an image with a live key gets probability exactly 0; an image whose mask is all zeros gets the softmax of
+ * its scores shifted by -10000 (fp32: only 2^-10 of a score survives the shift), never NaN. */
+int pnp_op_text_self_attn(int32_t bf16, const void* d_qkv, const int64_t* d_mask, int32_t ld_mask, void* d_ctx, float* d_probs,
+                          float* d_scratch, int32_t B, int32_t L, int32_t H, void* stream);
+/* Its backward: d_dctx fp32 [B*L, H], d_probs as stashed by the forward, d_ds_scratch fp32 [B, heads, L, L] (receives dS =
+ * P (dP - rowsum(dP P))), d_dqkv [B*L, 3H] T = dq | dk | dv. */
+int pnp_op_text_self_attn_bwd(int32_t bf16, const void* d_qkv, const float* d_dctx, const float* d_probs, float* d_ds_scratch,
+                              void* d_dqkv, int32_t B, int32_t L, int32_t H, void* stream);
+/* LayerNorm with every output of the kernel, each optional: d_y fp32, d_yt T, d_yt_lo bf16 (= bf16(y - yt), bf16 != 0 and d_yt
+ * required: the split-bf16 pair), d_xhat fp32 [rows, D], d_rstd fp32 [rows].  D <= 1024, D % 4 == 0. */
+int pnp_op_layernorm_ex(int32_t bf16, const float* d_x, const float* d_w, const float* d_b, float eps, int32_t rows, int32_t D,
+                        float* d_y, void* d_yt, void* d_yt_lo, float* d_xhat, float* d_rstd, void* stream);
+/* dx = rstd (g - mean(g) - xhat mean(g xhat)), g = dy * w; d_dx fp32 and / or d_dxt T. */
+int pnp_op_layernorm_bwd(int32_t bf16, const float* d_dy, const float* d_w, const float* d_xhat, const float* d_rstd, int32_t rows,
+                         int32_t D, float* d_dx, void* d_dxt, void* stream);
+/* BertEmbeddings before its LayerNorm (B/med.py:88-123): d_out[b, l, :] = d_word[id] + d_pos[l], id = d_ids[b, l] (d_ids (B,
+ * ld_ids) int64, the first L columns are read), clamped to [0, vocab - 1]; enc_id >= 0 replaces the id of column 0
+ * (B/blip_image_text_matching.py:238), enc_id < 0 keeps it.  H % 4 == 0, enc_id < vocab, ld_ids >= L. */
+int pnp_op_text_embed(const int64_t* d_ids, int32_t ld_ids, const float* d_word, const float* d_pos, float* d_out, int32_t B,
+                      int32_t L, int32_t H, int32_t enc_id, int32_t vocab, void* stream);
+/* itm_head on token 0 (B/blip_image_text_matching.py:248): d_logits[b, c] = d_hlast[b, 0, :] . d_w[c, :] + d_bias[c], c < 2;
+ * and the seed of the backward of sum_b logits[b, 1]: d_dh[b, l, :] = d_w[1, :] at l = 0, else 0. */
+int pnp_op_itm_head(const float* d_hlast, const float* d_w, const float* d_bias, float* d_logits, int32_t B, int32_t L, int32_t H,
+                    void* stream);
+int pnp_op_itm_grad_seed(const float* d_w, float* d_dh, int32_t B, int32_t L, int32_t H, void* stream);
+/* The ViT input kernels (B/vit.py:274-283).  pnp_op_patchify: d_img (B, 3, S, S) fp32, S = 16 P -> d_out [B*P*P, 768] T, column
+ * c * 256 + i * 16 + j = pixel (c, 16 py + i, 16 px + j); patches flagged in d_dropped ((B, P*P) uint8, may be NULL) are zeros.
+ * pnp_op_cls_rows: d_x[b, 0, :] = d_cls + d_pos[0, :] for d_x (B, N, D) fp32; the other rows are not touched. */
+int pnp_op_patchify(int32_t bf16, const float* d_img, const uint8_t* d_dropped, void* d_out, int32_t B, int32_t S, int32_t P,
+                    void* stream);
+int pnp_op_cls_rows(const float* d_cls, const float* d_pos, float* d_x, int32_t B, int32_t N, int32_t D, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1917,6 +1917,11 @@ extern "C" int pnp_set_tuning(const char* key, int32_t value) {
         set_streamk_mode(value);
         return PNP_OK;
     }
+    if (!strcmp(key, "text_rows")) {
+        if (value < 0 || value > 4) return PNP_ERR_ARG;
+        set_text_rows(value);
+        return PNP_OK;
+    }
     return PNP_ERR_ARG;
 }
 
@@ -1975,6 +1980,59 @@ extern "C" int pnp_op_xattn(int32_t bf16, int32_t mode, const void* d_nat, int32
     if (B <= 0 || L <= 0 || N <= 0 || heads <= 0) return PNP_ERR_ARG;
     return xattn(bf16, mode, d_nat, ld_nat, d_tr, ld_tr, n_pad, d_x, ldx, d_out, ldo, d_probs, n_stride, B, L, N, heads,
                  (hipStream_t)stream);
+}
+
+extern "C" int pnp_op_text_self_attn(int32_t bf16, const void* d_qkv, const int64_t* d_mask, int32_t ld_mask, void* d_ctx,
+                                     float* d_probs, float* d_scratch, int32_t B, int32_t L, int32_t H, void* stream) {
+    if (!d_qkv || !d_mask || !d_ctx || B <= 0 || L <= 0 || H <= 0 || ld_mask < L) return PNP_ERR_ARG;
+    return text_self_attn(bf16, d_qkv, d_mask, ld_mask, d_ctx, d_probs, d_scratch, B, L, H, (hipStream_t)stream);
+}
+
+extern "C" int pnp_op_text_self_attn_bwd(int32_t bf16, const void* d_qkv, const float* d_dctx, const float* d_probs,
+                                         float* d_ds_scratch, void* d_dqkv, int32_t B, int32_t L, int32_t H, void* stream) {
+    if (!d_qkv || !d_dctx || !d_probs || !d_ds_scratch || !d_dqkv || B <= 0 || L <= 0 || H <= 0) return PNP_ERR_ARG;
+    return text_self_attn_bwd(bf16, d_qkv, d_dctx, d_probs, d_ds_scratch, d_dqkv, B, L, H, (hipStream_t)stream);
+}
+
+extern "C" int pnp_op_layernorm_ex(int32_t bf16, const float* d_x, const float* d_w, const float* d_b, float eps, int32_t rows,
+                                   int32_t D, float* d_y, void* d_yt, void* d_yt_lo, float* d_xhat, float* d_rstd, void* stream) {
+    if (!d_x || !d_w || !d_b || rows <= 0 || D <= 0 || (d_yt_lo && !d_yt)) return PNP_ERR_ARG;
+    return layernorm(bf16, d_x, d_w, d_b, eps, rows, D, d_y, d_yt, d_xhat, d_rstd, (hipStream_t)stream, d_yt_lo);
+}
+
+extern "C" int pnp_op_layernorm_bwd(int32_t bf16, const float* d_dy, const float* d_w, const float* d_xhat, const float* d_rstd,
+                                    int32_t rows, int32_t D, float* d_dx, void* d_dxt, void* stream) {
+    if (!d_dy || !d_w || !d_xhat || !d_rstd || rows <= 0 || D <= 0) return PNP_ERR_ARG;
+    return layernorm_bwd(bf16, d_dy, d_w, d_xhat, d_rstd, rows, D, d_dx, d_dxt, (hipStream_t)stream);
+}
+
+extern "C" int pnp_op_text_embed(const int64_t* d_ids, int32_t ld_ids, const float* d_word, const float* d_pos, float* d_out,
+                                 int32_t B, int32_t L, int32_t H, int32_t enc_id, int32_t vocab, void* stream) {
+    if (!d_ids || !d_word || !d_pos || !d_out || B <= 0 || L <= 0 || H <= 0 || H % 4 || vocab <= 0 || ld_ids < L || enc_id >= vocab)
+        return PNP_ERR_ARG;
+    return text_embed(d_ids, ld_ids, d_word, d_pos, d_out, B, L, H, enc_id, vocab, (hipStream_t)stream);
+}
+
+extern "C" int pnp_op_itm_head(const float* d_hlast, const float* d_w, const float* d_bias, float* d_logits, int32_t B, int32_t L,
+                               int32_t H, void* stream) {
+    if (!d_hlast || !d_w || !d_bias || !d_logits || B <= 0 || L <= 0 || H <= 0) return PNP_ERR_ARG;
+    return itm_head(d_hlast, d_w, d_bias, d_logits, B, L, H, (hipStream_t)stream);
+}
+
+extern "C" int pnp_op_itm_grad_seed(const float* d_w, float* d_dh, int32_t B, int32_t L, int32_t H, void* stream) {
+    if (!d_w || !d_dh || B <= 0 || L <= 0 || H <= 0) return PNP_ERR_ARG;
+    return itm_grad_seed(d_w, d_dh, B, L, H, (hipStream_t)stream);
+}
+
+extern "C" int pnp_op_patchify(int32_t bf16, const float* d_img, const uint8_t* d_dropped, void* d_out, int32_t B, int32_t S,
+                               int32_t P, void* stream) {
+    if (!d_img || !d_out || B <= 0 || P <= 0 || S != P * 16) return PNP_ERR_ARG;
+    return patchify(bf16, d_img, d_dropped, d_out, B, S, P, (hipStream_t)stream);
+}
+
+extern "C" int pnp_op_cls_rows(const float* d_cls, const float* d_pos, float* d_x, int32_t B, int32_t N, int32_t D, void* stream) {
+    if (!d_cls || !d_pos || !d_x || B <= 0 || N <= 0 || D <= 0) return PNP_ERR_ARG;
+    return cls_rows(d_cls, d_pos, d_x, B, N, D, (hipStream_t)stream);
 }
 
 extern "C" int pnp_dbg_gemm_stamps(uint64_t* host_out, int32_t max_blocks) {

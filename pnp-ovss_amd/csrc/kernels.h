@@ -77,6 +77,7 @@ int text_embed(const int64_t* ids, int ld_ids, const float* word, const float* p
 // through global memory)
 int text_self_attn(int bf, const void* qkv, const int64_t* mask, int ld_mask, void* ctx, float* probs, float* scratch, int B, int L,
                    int H, hipStream_t s);
+void set_text_rows(int n);   // 0 = cost model, 1..4 = workgroups per (head, image) of the row-split self-attention launches
 int text_self_attn_bwd(int bf, const void* qkv, const float* dctx, const float* probs, float* ds_scratch, void* dqkv,
                        int B, int L, int H, hipStream_t s);
 int xattn(int bf, int mode, const void* a1, int ld1, const void* a2t, int ld2, int Npad, const void* x, int ldx,

@@ -733,10 +733,14 @@ int text_embed(const int64_t* ids, int ld_ids, const float* word, const float* p
 }
 
 static size_t self_attn_smem(int L, int nw = 4) { return (size_t)(2 * L * 65 + (nw + 1) * TXT_MAX_L + nw * 64) * sizeof(float); }
+static std::atomic<int> g_text_rows{0};               // pnp_set_tuning("text_rows"): 0 = the cost model below, 1..4 = forced
+void set_text_rows(int n) { g_text_rows.store(n, std::memory_order_relaxed); }
 // workgroups per (head, image) for the row-split launches: the nz in [1, 4] that minimises rounds(pairs * nz) / nz, a round being
 // what is RESIDENT at once: CUs x workgroups per CU at this caption length's LDS use (about 100 KB at L = 155: one per CU, 96 pairs
 // -> nz = 2, one round of half the rows; 49 KB at L = 85: three per CU, 420 pairs -> nz = 3, two rounds of a third)
 static int row_split(int pairs, size_t smem) {
+    const int forced = g_text_rows.load(std::memory_order_relaxed);
+    if (forced > 0) return forced;
     const int cus = device_cu_count() > 0 ? device_cu_count() : 256;
     int per_cu = (int)(160 * 1024 / (smem ? smem : 1));
     per_cu = per_cu < 1 ? 1 : per_cu > 8 ? 8 : per_cu;

@@ -100,6 +100,15 @@ def load_library():
         "pnp_op_sort_pairs": (i32, [vp, vp, vp, vp, i64, i32, i32, vp, i32, vp]),
         "pnp_op_scan_i32": (i32, [vp, vp, i64, i32, vp]),
         "pnp_set_tuning": (i32, [C.c_char_p, i32]),
+        "pnp_op_text_self_attn": (i32, [i32, vp, vp, i32, vp, vp, vp, i32, i32, i32, vp]),
+        "pnp_op_text_self_attn_bwd": (i32, [i32, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
+        "pnp_op_layernorm_ex": (i32, [i32, vp, vp, vp, f32, i32, i32, vp, vp, vp, vp, vp, vp]),
+        "pnp_op_layernorm_bwd": (i32, [i32, vp, vp, vp, vp, i32, i32, vp, vp, vp]),
+        "pnp_op_text_embed": (i32, [vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+        "pnp_op_itm_head": (i32, [vp, vp, vp, vp, i32, i32, i32, vp]),
+        "pnp_op_itm_grad_seed": (i32, [vp, vp, i32, i32, i32, vp]),
+        "pnp_op_patchify": (i32, [i32, vp, vp, vp, i32, i32, i32, vp]),
+        "pnp_op_cls_rows": (i32, [vp, vp, vp, i32, i32, i32, vp]),
         "pnp_streamk_status": (i32, [vp, C.POINTER(i64), C.POINTER(C.c_uint32)]),
     }
     for name, (res, args) in sig.items():
@@ -118,7 +127,9 @@ EXPORTED = ["pnp_create", "pnp_create_shared", "pnp_destroy", "pnp_last_error", 
             "pnp_cross_kv", "pnp_profile_read_stage", "pnp_op_split", "pnp_op_gemm_x3", "pnp_op_gemm_x3a",
             "pnp_xattn_grad_layer", "pnp_compute_gradcam_layer", "pnp_drop_loop_layer", "pnp_allocated_bytes",
             "pnp_op_vit_attention_x3", "pnp_jpeg_decode", "pnp_op_sort_pairs", "pnp_op_scan_i32", "pnp_set_tuning",
-            "pnp_streamk_status", "pnp_text_forward_text", "pnp_project_normalize", "pnp_itc_similarity"]
+            "pnp_streamk_status", "pnp_text_forward_text", "pnp_project_normalize", "pnp_itc_similarity",
+            "pnp_op_text_self_attn", "pnp_op_text_self_attn_bwd", "pnp_op_layernorm_ex", "pnp_op_layernorm_bwd",
+            "pnp_op_text_embed", "pnp_op_itm_head", "pnp_op_itm_grad_seed", "pnp_op_patchify", "pnp_op_cls_rows"]
 
 
 PROJ_NAMES = ("vision_proj.weight", "vision_proj.bias", "text_proj.weight", "text_proj.bias")      # the optional ITC projections
