@@ -318,11 +318,29 @@ int pnp_op_gemm_ex(int32_t bf16, const void* d_A, int32_t lda, const void* d_B, 
 int pnp_op_gemm_tokcols(int32_t bf16, const void* d_A, int32_t lda, const void* d_B, int32_t ldb, int32_t M, int32_t N,
                         int32_t K, const float* d_bias_rows, void* d_out_t, int32_t ldo_t, int32_t col_div,
                         int32_t col_pad, void* stream);
+/* Every field of a non-split launch (fp32 or bf16 operands) that the entry points above hide:
+ *   out[row(m), col(n)] = act(A[m,:] . B[n,:] + bias) (+ resid), written to d_out_f32 and / or d_out_t (compute type), at
+ *   least one of them;  mode 0 linear | 1 GELU (pre-activation stashed to d_aux[row(m), n] when given) | 2 multiply by
+ *   GELU'(d_aux[row(m), n]) (d_aux required);  bias[n], or bias[m] with bias_on_rows;
+ *   row_div > 0: row(m) = (m / row_div) * (row_div + 1) + 1 + m % row_div and resid = pos_embed [row_div + 1, ldr], read at
+ *   row 1 + m % row_div (the patch-embed form, B/vit.py:274-283: token row 0 of every image is not written);
+ *   col_div > 0: col(n) = (n / col_div) * col_pad + n % col_div (col_pad >= col_div), as pnp_op_gemm_tokcols.
+ * Null operands, no output, non-positive sizes, lda / ldb < K, mode outside 0..2, mode 2 without d_aux, negative row_div /
+ * col_div and col_pad < col_div return PNP_ERR_ARG before any HIP call.
+ * Every non-split GEMM entry point (this one, pnp_op_gemm, pnp_op_gemm_ex, pnp_op_gemm_tokcols) returns PNP_ERR_ARG for
+ * N % 4 != 0 together with a per-column bias, a residual or d_aux: the kernels read those four columns at a time, and the
+ * last group would reach past column N.  N % 4 != 0 with bias_on_rows (or no bias) and no residual / d_aux is accepted. */
+int pnp_op_gemm_args(int32_t bf16, const void* d_A, int32_t lda, const void* d_B, int32_t ldb, int32_t M, int32_t N, int32_t K,
+                     const float* d_bias, int32_t bias_on_rows, const float* d_resid, int32_t ldr, float* d_out_f32, int32_t ldo,
+                     void* d_out_t, int32_t ldo_t, int32_t mode, float* d_aux, int32_t ld_aux, int32_t row_div, int32_t col_div,
+                     int32_t col_pad, void* stream);
 /* Split-bf16 ("bf16x3") form of the Linear (compute mode 2): operands are bf16 pairs x = hi + lo (pnp_op_split),
  * out = A.B^T accumulated as A_hi.B_hi + A_hi.B_lo + A_lo.B_hi in fp32, then one of the fp32-facing epilogues:
  *   d_out_f32, no col_div / bias_on_rows : + bias[n] (+ resid)            -> fp32 [M, ldo]
  *   d_out_f32, bias_on_rows / col_div    : + bias[m], token-column remap  -> fp32 [M, ldo]   (as pnp_op_gemm_tokcols)
- *   gelu, d_out_hi + d_out_lo            : + bias[n], erf GELU            -> split bf16 pair [M, ldo_t] */
+ *   gelu, d_out_hi + d_out_lo            : + bias[n], erf GELU            -> split bf16 pair [M, ldo_t]
+ * The first and third need N % 4 == 0; the token-column form with an even col_div (or col_div = 0) needs an even N (token
+ * pairs are stored together): PNP_ERR_ARG otherwise.  pnp_op_gemm_tokcols has no such limit. */
 int pnp_op_split(const float* d_in, void* d_hi, void* d_lo, int64_t n, void* stream);
 int pnp_op_gemm_x3(const void* d_A_hi, const void* d_A_lo, int32_t lda, const void* d_B_hi, const void* d_B_lo, int32_t ldb,
                    int32_t M, int32_t N, int32_t K, const float* d_bias, int32_t bias_on_rows, const float* d_resid, int32_t ldr,

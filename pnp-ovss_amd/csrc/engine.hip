@@ -1956,6 +1956,20 @@ extern "C" int pnp_op_gemm_tokcols(int32_t bf, const void* d_A, int32_t lda, con
     return gemm_nt(bf, g, (hipStream_t)stream);
 }
 
+extern "C" int pnp_op_gemm_args(int32_t bf, const void* d_A, int32_t lda, const void* d_B, int32_t ldb, int32_t M, int32_t N,
+                                int32_t K, const float* d_bias, int32_t bias_on_rows, const float* d_resid, int32_t ldr,
+                                float* d_out_f32, int32_t ldo, void* d_out_t, int32_t ldo_t, int32_t mode, float* d_aux,
+                                int32_t ld_aux, int32_t row_div, int32_t col_div, int32_t col_pad, void* stream) {
+    if (!d_A || !d_B || (!d_out_f32 && !d_out_t) || M <= 0 || N <= 0 || K <= 0 || lda < K || ldb < K) return PNP_ERR_ARG;
+    if (mode < 0 || mode > 2 || (mode == GEMM_EPI_GELU_GRAD && !d_aux)) return PNP_ERR_ARG;
+    if (row_div < 0 || col_div < 0 || (col_div > 0 && col_pad < col_div)) return PNP_ERR_ARG;
+    GemmArgs g = G_(d_A, lda, d_B, ldb, M, N, K);
+    g.bias = d_bias; g.bias_on_rows = bias_on_rows ? 1 : 0; g.resid = d_resid; g.ldr = ldr;
+    g.out_f32 = d_out_f32; g.ldo = ldo; g.out_t = d_out_t; g.ldo_t = ldo_t;
+    g.mode = mode; g.aux = d_aux; g.ld_aux = ld_aux; g.row_div = row_div; g.col_div = col_div; g.col_pad = col_pad;
+    return gemm_nt(bf ? 1 : 0, g, (hipStream_t)stream);
+}
+
 extern "C" int pnp_op_vit_attention(int32_t bf, const void* d_qk, int32_t ld_qk, int32_t D, const void* d_vt, int32_t ld_vt,
                                     int32_t n_pad, void* d_ctx, int32_t B, int32_t heads, int32_t N, float scale, void* stream) {
     if (!d_qk || !d_vt || !d_ctx || B <= 0 || heads <= 0 || N <= 0) return PNP_ERR_ARG;

@@ -605,7 +605,7 @@ __global__ __launch_bounds__(512) void gemm_nt_wide_kernel(const GemmArgs g) {
                 ocol = (size_t)b * g.col_pad + tl;
             }
             bf16* const ocolp = reinterpret_cast<bf16*>(g.out_t) + ocol;
-            const bool tv = tok < g.Nvalid;         // Nvalid is even whenever col_div is (whole images)
+            const bool tv = tok < g.Nvalid;         // Nvalid is even whenever col_div is (wide_epilogue_kind: pair_ok)
 #pragma unroll
             for (int half = 0; half < 2; half++) {
                 const int mbase = em0 + wm * 128 + half * 64;
@@ -737,9 +737,13 @@ __global__ __launch_bounds__(512) void gemm_nt_wide_kernel(const GemmArgs g) {
 // remaps, per-row bias, stashes, dual outputs) stays on the generic kernels
 static int wide_epilogue_kind(const GemmArgs& g) {
     if (g.aux || g.row_div) return -1;
+    // the token-column epilogues store token PAIRS when col_div is even (pairs then never straddle an image): N has to be even
+    // too, or the last pair would write column N.  Otherwise the generic kernels take the launch (no split-bf16 form: refused)
+    const bool pair_ok = (g.col_div & 1) || !(g.Nvalid & 1);
     if (g.A_lo || g.B_lo) {                         // split-bf16 operands: the fp32-facing epilogues
         if (!g.A_lo || !g.B_lo) return -1;
-        if (g.mode == GEMM_EPI_LINEAR && !g.resid && g.out_f32 && !g.out_t && (g.bias_on_rows || !g.bias) && (g.col_div > 0 || g.bias_on_rows))
+        if (g.mode == GEMM_EPI_LINEAR && !g.resid && g.out_f32 && !g.out_t && (g.bias_on_rows || !g.bias) && (g.col_div > 0 || g.bias_on_rows) &&
+            pair_ok)
             return WIDE_TOKCOLS_F32;
         if (g.col_div || g.bias_on_rows || (g.Nvalid & 3)) return -1;
         if (g.mode == GEMM_EPI_LINEAR && g.resid && g.out_f32 && !g.out_t) return WIDE_RESID_F32;
@@ -748,7 +752,8 @@ static int wide_epilogue_kind(const GemmArgs& g) {
         if (g.mode == GEMM_EPI_LINEAR && !g.resid && g.out_t && g.out_lo && !g.out_f32) return WIDE_SPLIT;
         return -1;
     }
-    if (g.mode == GEMM_EPI_LINEAR && !g.resid && g.out_t && !g.out_f32 && (g.bias_on_rows || !g.bias) && (g.col_div > 0 || g.bias_on_rows))
+    if (g.mode == GEMM_EPI_LINEAR && !g.resid && g.out_t && !g.out_f32 && (g.bias_on_rows || !g.bias) && (g.col_div > 0 || g.bias_on_rows) &&
+        pair_ok)
         return WIDE_TOKCOLS_BF16;
     if (g.col_div || g.bias_on_rows || (g.Nvalid & 3)) return -1;
     if (g.mode == GEMM_EPI_LINEAR && !g.resid && g.out_t && !g.out_f32) return WIDE_BF16;
@@ -1163,6 +1168,11 @@ int gemm_nt(int dtype_bf16, GemmArgs g, hipStream_t s) {
     const int bk = dtype_bf16 ? 64 : 32;
     if (g.K % bk) return PNP_ERR_ARG;
     if ((g.lda * (dtype_bf16 ? 2 : 4)) % 16 || (g.ldb * (dtype_bf16 ? 2 : 4)) % 16) return PNP_ERR_ARG;
+    // store_frag and the accumulator preload read the per-column bias, the residual row and the GELU stash as one 16-byte
+    // group of four columns (and write the stash that way): with N % 4 != 0 the last group would reach past column N -- past
+    // the end of bias and of the last residual row, and, the stash, a WRITE past column N of every row.  Refused as a whole
+    // (broader than the fault: a padded residual only over-reads on its last row): no engine launch uses the combination
+    if ((g.N & 3) && ((g.bias && !g.bias_on_rows) || g.resid || g.aux)) return PNP_ERR_ARG;
     g.Nvalid = g.N;
     int variant = 0;
 #ifdef PNP_DEV

@@ -86,6 +86,8 @@ def load_library():
         "pnp_op_gemm": (i32, [i32, vp, i32, vp, i32, i32, i32, i32, vp, vp, i32, vp, i32, i32, vp]),
         "pnp_op_gemm_ex": (i32, [i32, vp, i32, vp, i32, i32, i32, i32, vp, vp, i32, vp, i32, vp, i32, i32, vp]),
         "pnp_op_gemm_tokcols": (i32, [i32, vp, i32, vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, vp]),
+        "pnp_op_gemm_args": (i32, [i32, vp, i32, vp, i32, i32, i32, i32, vp, i32, vp, i32, vp, i32, vp, i32, i32, vp, i32, i32, i32,
+                                   i32, vp]),
         "pnp_op_vit_attention": (i32, [i32, vp, i32, i32, vp, i32, i32, vp, i32, i32, i32, f32, vp]),
         "pnp_op_vit_attention_x3": (i32, [vp, vp, i32, i32, vp, vp, i32, i32, i32, f32, vp]),
         "pnp_preprocess_images": (i32, [vp, vp, i32, i32, i32, vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_float), vp, vp]),
@@ -129,7 +131,8 @@ EXPORTED = ["pnp_create", "pnp_create_shared", "pnp_destroy", "pnp_last_error", 
             "pnp_op_vit_attention_x3", "pnp_jpeg_decode", "pnp_op_sort_pairs", "pnp_op_scan_i32", "pnp_set_tuning",
             "pnp_streamk_status", "pnp_text_forward_text", "pnp_project_normalize", "pnp_itc_similarity",
             "pnp_op_text_self_attn", "pnp_op_text_self_attn_bwd", "pnp_op_layernorm_ex", "pnp_op_layernorm_bwd",
-            "pnp_op_text_embed", "pnp_op_itm_head", "pnp_op_itm_grad_seed", "pnp_op_patchify", "pnp_op_cls_rows"]
+            "pnp_op_text_embed", "pnp_op_itm_head", "pnp_op_itm_grad_seed", "pnp_op_patchify", "pnp_op_cls_rows",
+            "pnp_op_gemm_args"]
 
 
 PROJ_NAMES = ("vision_proj.weight", "vision_proj.bias", "text_proj.weight", "text_proj.bias")      # the optional ITC projections

@@ -71,6 +71,38 @@ def test_operator_entry_points_validate_arguments_without_a_gpu(lib):
     n = None
     assert lib.pnp_op_gemm_x3a(n, 64, n, n, 64, 8, 64, 64, n, n, 0, n, 64, 0, n, 0, n) == -22
     assert lib.pnp_op_gemm_x3(n, n, 64, n, n, 64, 8, 64, 64, n, 0, n, 0, n, 0, n, n, 0, 0, 0, 0, n) == -22
+    # pnp_op_gemm_args: (bf16, A, lda, B, ldb, M, N, K, bias, bias_on_rows, resid, ldr, out_f32, ldo, out_t, ldo_t, mode, aux,
+    # ld_aux, row_div, col_div, col_pad, stream).  `p` is never dereferenced: every call below is refused on the host.
+    lib.pnp_op_gemm_args.restype = ctypes.c_int
+    lib.pnp_op_gemm.restype = ctypes.c_int
+    lib.pnp_op_gemm_ex.restype = ctypes.c_int
+    p = ctypes.c_void_p(4096)
+    ga = lib.pnp_op_gemm_args
+    assert ga(0, n, 64, p, 64, 8, 64, 64, n, 0, n, 0, p, 64, n, 0, 0, n, 0, 0, 0, 0, n) == -22        # A null
+    assert ga(0, p, 64, n, 64, 8, 64, 64, n, 0, n, 0, p, 64, n, 0, 0, n, 0, 0, 0, 0, n) == -22        # B null
+    assert ga(0, p, 64, p, 64, 8, 64, 64, n, 0, n, 0, n, 64, n, 0, 0, n, 0, 0, 0, 0, n) == -22        # no output
+    for M, N, K in ((0, 64, 64), (8, 0, 64), (8, 64, 0), (-1, 64, 64)):
+        assert ga(0, p, 64, p, 64, M, N, K, n, 0, n, 0, p, 64, n, 0, 0, n, 0, 0, 0, 0, n) == -22
+    assert ga(0, p, 32, p, 64, 8, 64, 64, n, 0, n, 0, p, 64, n, 0, 0, n, 0, 0, 0, 0, n) == -22        # lda < K
+    assert ga(0, p, 64, p, 64, 8, 64, 64, n, 0, n, 0, p, 64, n, 0, 3, p, 64, 0, 0, 0, n) == -22       # mode out of range
+    assert ga(0, p, 64, p, 64, 8, 64, 64, n, 0, n, 0, p, 64, n, 0, -1, p, 64, 0, 0, 0, n) == -22
+    assert ga(0, p, 64, p, 64, 8, 64, 64, n, 0, n, 0, p, 64, n, 0, 2, n, 0, 0, 0, 0, n) == -22        # GELU' without aux
+    assert ga(0, p, 64, p, 64, 8, 64, 64, n, 1, n, 0, p, 64, n, 0, 0, n, 0, 0, 8, 4, n) == -22        # col_pad < col_div
+    assert ga(0, p, 64, p, 64, 8, 64, 64, n, 0, n, 0, p, 64, n, 0, 0, n, 0, -1, 0, 0, n) == -22       # negative row_div
+    assert ga(0, p, 64, p, 64, 8, 64, 64, n, 0, n, 0, p, 64, n, 0, 0, n, 0, 0, -1, 0, n) == -22
+    assert ga(0, p, 64, p, 64, 8, 64, 48, n, 0, n, 0, p, 64, n, 0, 0, n, 0, 0, 0, 0, n) == -22        # K % 32
+    assert ga(1, p, 64, p, 64, 8, 64, 32, n, 0, n, 0, p, 64, n, 0, 0, n, 0, 0, 0, 0, n) == -22        # bf16: K % 64
+    # N % 4 != 0 with an operand the kernels read four columns at a time: per-column bias, residual, GELU stash (both types,
+    # every non-split entry point)
+    for bf in (0, 1):
+        for N in (65, 66, 67):
+            assert ga(bf, p, 64, p, 64, 8, N, 64, p, 0, n, 0, p, 72, n, 0, 0, n, 0, 0, 0, 0, n) == -22
+            assert ga(bf, p, 64, p, 64, 8, N, 64, n, 0, p, 72, p, 72, n, 0, 0, n, 0, 0, 0, 0, n) == -22
+            assert ga(bf, p, 64, p, 64, 8, N, 64, n, 0, n, 0, p, 72, n, 0, 1, p, 72, 0, 0, 0, n) == -22
+            assert lib.pnp_op_gemm(bf, p, 64, p, 64, 8, N, 64, p, n, 0, p, 72, 0, n) == -22
+            assert lib.pnp_op_gemm_ex(bf, p, 64, p, 64, 8, N, 64, n, p, 72, p, 72, n, 0, 0, n) == -22
+    # the split token-column form stores token pairs when col_div is even: an odd N is refused
+    assert lib.pnp_op_gemm_x3(p, p, 64, p, p, 64, 8, 63, 64, n, 1, n, 0, p, 448, n, n, 0, 0, 442, 448, n) == -22
 
 
 def _gfx950_code_objects(lib_path, tmpdir):

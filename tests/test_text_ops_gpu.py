@@ -16,11 +16,11 @@ import pytest
 torch = pytest.importorskip("torch")
 
 import _text_refs as R          # noqa: E402
+from _gpu_guard import SENTINEL, Acc, Guarded, _bits          # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
 
 ERR_ARG = -22
-SENTINEL = 12345.0
 POISON_I64 = 1 << 62             # in mask / id columns the kernels must not read
 
 
@@ -30,57 +30,6 @@ def lib():
     lib = hip.load_library()
     yield lib
     assert lib.pnp_set_tuning(b"text_rows", 0) == 0
-
-
-def _bits(t):
-    return t.view({1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()])
-
-
-class Guarded:
-    """A device buffer: NaN-filled live region of `shape` between two guard blocks of >= `guard` sentinel elements."""
-
-    def __init__(self, shape, dtype, guard):
-        self.n = int(np.prod(shape))
-        self.g = max(64, (int(guard) + 63) // 64 * 64)          # multiples of 64 elements keep the live region 16-byte aligned
-        self.buf = torch.full((2 * self.g + self.n,), SENTINEL, dtype=dtype, device="cuda")
-        self.live = self.buf[self.g:self.g + self.n].view(shape)
-        self.live.fill_(float("nan"))
-        self.guard_bits = _bits(torch.full((self.g,), SENTINEL, dtype=dtype))
-
-    @property
-    def ptr(self):
-        return self.live.data_ptr()
-
-    def check(self, tag, written=None):
-        """Guards untouched bit for bit, no NaN in the live region (or in its first `written` elements).  Returns a CPU copy."""
-        raw = _bits(self.buf).cpu()
-        assert torch.equal(raw[:self.g], self.guard_bits), f"{tag}: front guard written"
-        assert torch.equal(raw[self.g + self.n:], self.guard_bits), f"{tag}: back guard written"
-        out = self.live.cpu()
-        chk = out.reshape(-1)[:written] if written is not None else out
-        nan = int(torch.isnan(chk.float()).sum())
-        assert nan == 0, f"{tag}: {nan} elements NaN / not written"
-        return out
-
-
-class Acc:
-    """Collects (error, bound) pairs of one test; `add` asserts, `flush` reports the largest error and fraction of its bound."""
-
-    def __init__(self, tag):
-        self.tag, self.worst = tag, {}
-
-    def add(self, name, err, bound, case):
-        err, bound = float(err), float(bound)
-        e, f = self.worst.get(name, (0.0, 0.0))
-        self.worst[name] = (max(e, err), max(f, err / bound if bound > 0 else float(err > 0)))
-        if not (np.isfinite(err) and err <= bound):
-            print(f"[measured] {self.tag}/{name} {case}: error {err:.3e} bound {bound:.3e}")
-        assert np.isfinite(err) and err <= bound, (self.tag, name, case, err, bound)
-
-    def flush(self):
-        for name, (e, f) in self.worst.items():
-            R.measure(f"{self.tag}/{name}/max_abs_err", e)
-            R.measure(f"{self.tag}/{name}/max_fraction_of_bound", f)
 
 
 def _tdt(bf16):
