@@ -9,6 +9,7 @@
 #include <map>
 #include <memory>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/pnp_hip.h"
@@ -24,13 +25,31 @@ struct Buf {
     size_t bytes = 0;
 };
 
+// A GEMM weight [rows, cols] in the engine's compute mode.  bf16x3 keeps the wide Linears' weights as a (hi | lo) bf16 pair in the
+// bytes of the fp32 copy: the hi array, then the lo array.  Only this type and new_weight / fill_weight know it.
+struct Weight {
+    void* p = nullptr;
+    int rows = 0, cols = 0;
+    int esz = 0;               // bytes per stored element
+    bool pair = false;
+    void* hi(int r0 = 0) const { return (char*)p + (size_t)r0 * cols * esz; }      // row r0 on: a layer of the layer-major ck_w / cv_w
+    void* lo(int r0 = 0) const { return pair ? (char*)p + ((size_t)rows + r0) * cols * esz : nullptr; }
+};
+
+// An activation buffer of the ViT side: one array of the compute type, or in bf16x3 a (hi, lo) bf16 pair whose lo array starts
+// at the buffer's row capacity, whatever batch is in flight (alloc_act)
+struct Act {
+    void* hi = nullptr;
+    void* lo = nullptr;        // null outside bf16x3
+};
+
 struct TextLayerW {
     // forward (T = compute dtype)
-    void *qkv_w = nullptr, *so_w = nullptr, *cq_w = nullptr, *co_w = nullptr, *i_w = nullptr, *o_w = nullptr;
+    Weight qkv_w, so_w, cq_w, co_w, i_w, o_w;
     float *qkv_b = nullptr, *so_b = nullptr, *sln_w = nullptr, *sln_b = nullptr, *cq_b = nullptr, *co_b = nullptr,
           *cln_w = nullptr, *cln_b = nullptr, *i_b = nullptr, *o_b = nullptr, *oln_w = nullptr, *oln_b = nullptr;
     // backward (transposed copies, layers >= stash_layer)
-    void *o_wT = nullptr, *i_wT = nullptr, *co_wT = nullptr, *cq_wT = nullptr, *so_wT = nullptr, *qkv_wT = nullptr;
+    Weight o_wT, i_wT, co_wT, cq_wT, so_wT, qkv_wT;
 };
 
 struct TextLayerA {
@@ -49,7 +68,7 @@ struct TextLayerA {
 
 struct VitLayerW {
     float *n1w, *n1b, *n2w, *n2b, *qkv_b, *proj_b, *fc1_b, *fc2_b;
-    void *qkv_w, *proj_w, *fc1_w, *fc2_w;
+    Weight qkv_w, proj_w, fc1_w, fc2_w;
 };
 
 // Device allocations that hold WEIGHTS (converted GEMM weights, biases, LayerNorm parameters, embeddings): read-only once
@@ -84,16 +103,16 @@ struct pnp_engine {
 
     // ---- weights
     float *cls = nullptr, *pos = nullptr, *patch_b = nullptr, *vnorm_w = nullptr, *vnorm_b = nullptr;
-    void* patch_w = nullptr;
+    Weight patch_w;
     std::vector<VitLayerW> vit;
     float *word = nullptr, *tpos = nullptr, *eln_w = nullptr, *eln_b = nullptr, *itm_w = nullptr, *itm_b = nullptr;
     std::vector<TextLayerW> txt;
     // optional ITC projections, [0] vision_proj (D -> E), [1] text_proj (H -> E) (B/blip_image_text_matching.py:54-55): present when
     // the state dict carried weight and bias; E is read from the weight's first dimension
-    void* proj_w[2] = {nullptr, nullptr};
+    Weight proj_w[2];
     float* proj_b[2] = {nullptr, nullptr};
     int proj_E[2] = {0, 0};
-    void *ck_w = nullptr, *cv_w = nullptr;     // cross K / V weights of all layers: [TL*H, D]
+    Weight ck_w, cv_w;                         // cross K / V weights of all layers: [TL*H, D]
     float *ck_b = nullptr, *cv_b = nullptr;    // [TL*H]
     std::vector<Buf> staging;                  // fp32 staging of GEMM weights until finalize
 
@@ -106,7 +125,8 @@ struct pnp_engine {
     // always starts a batch with embed == 1; pnp_vit_forward / pnp_text_forward_xattn invalidate the record)
     struct { const float* images = nullptr; const int64_t* ids = nullptr; const int64_t* mask = nullptr; int B = 0, L = 0, ld = 0;
              bool vit = false, text = false; } reuse;
-    void *patches = nullptr, *xn = nullptr, *qk = nullptr, *vt = nullptr, *ctx = nullptr, *h1 = nullptr, *embT = nullptr;
+    void *patches = nullptr, *vt = nullptr;
+    Act xn, qk, ctx, h1, embT;
     float *x = nullptr, *emb32 = nullptr;
     void *Knat = nullptr, *Vnat = nullptr, *Kt = nullptr, *Vt = nullptr;
     std::vector<TextLayerA> ta;
@@ -222,6 +242,13 @@ int dalloc_t(pnp_engine* e, void** out, size_t count, bool zero = false) {   // 
     *out = p;
     return r;
 }
+int alloc_act(pnp_engine* e, Act* a, size_t rows, size_t ld) {   // the pair's two bf16 arrays fill the bytes of the fp32 rows
+    KCHK(e, dalloc_t(e, &a->hi, rows * ld));
+    a->lo = e->x3 ? (char*)a->hi + rows * ld * 2 : nullptr;
+    return PNP_OK;
+}
+// a raw kernel launch: KCHK(e, launched()) right behind it
+int launched() { return hipPeekAtLastError() == hipSuccess ? PNP_OK : PNP_ERR_HIP; }   // (KCHK reads and clears the error)
 
 bool ends_with(const std::string& s, const char* suf) {
     const size_t n = strlen(suf);
@@ -275,8 +302,6 @@ __global__ void tok_to_feat_kernel(const float* __restrict__ src, int ld_src, fl
     }
 }
 
-// fp32 [rows, cols] staging -> compute-type device weight (optionally transposed); split: a bf16 (hi | lo) pair in
-// the same bytes as the fp32 copy, hi first (split-bf16 mode, weights of the wide GEMMs)
 // Patch embeddings of a later drop iteration: the images are the ones of iteration 0 with more 16 x 16 blocks zeroed
 // (PnP.py:597-603), so a token's embedding is either what iteration 0 computed or, for a dropped patch, bias + pos exactly as the
 // GEMM epilogue forms it from a zero accumulator ((0 + bias[n]) + pos[t][n]); the cls row never changes.  One pass over x instead of
@@ -300,8 +325,19 @@ __global__ void embed_reuse_kernel(const float* __restrict__ x0, const uint8_t* 
     }
 }
 
-int make_weight(pnp_engine* e, const float* src32, int rows, int cols, bool transpose, void** out, bool split = false) {
-    KCHK(e, dalloc_t(e, out, (size_t)rows * cols));
+int new_weight(pnp_engine* e, int rows, int cols, bool pair, Weight* w) {
+    *w = Weight{nullptr, rows, cols, pair ? 2 : (int)e->esz, pair};
+    return dalloc_t(e, &w->p, (size_t)rows * cols);      // a pair belongs to bf16x3, whose compute type is fp32
+}
+// fp32 [n, w.cols] staging -> rows r0 .. r0 + n of the device weight
+int fill_weight(pnp_engine* e, const float* src32, const Weight& w, int r0, int n) {
+    const size_t count = (size_t)n * w.cols;
+    return w.pair ? split_f32(src32, w.hi(r0), w.lo(r0), count, 0) : cast_f32(e->bf, src32, w.hi(r0), count, 0);
+}
+// fp32 [rows, cols] staging -> device weight of the compute type, or a (hi | lo) pair (`pair`: bf16x3, weights of the wide
+// GEMMs); transpose: the weight is the [cols, rows] transpose
+int make_weight(pnp_engine* e, const float* src32, int rows, int cols, bool transpose, Weight* out, bool pair = false) {
+    KCHK(e, new_weight(e, transpose ? cols : rows, transpose ? rows : cols, pair, out));
     const float* s = src32;
     float* tmp = nullptr;
     if (transpose) {
@@ -310,8 +346,8 @@ int make_weight(pnp_engine* e, const float* src32, int rows, int cols, bool tran
                            rows, cols);
         s = tmp;
     }
-    int r = split ? split_f32(s, *out, (char*)*out + (size_t)rows * cols * 2, (size_t)rows * cols, 0)
-                  : cast_f32(e->bf, s, *out, (size_t)rows * cols, 0);
+    int r = transpose ? launched() : PNP_OK;
+    if (r == PNP_OK) r = fill_weight(e, s, *out, 0, out->rows);
     hipError_t st = hipDeviceSynchronize();
     if (tmp) (void)hipFree(tmp);
     if (r != PNP_OK || st != hipSuccess) return fail(e, PNP_ERR_HIP, "weight conversion failed");
@@ -324,26 +360,35 @@ GemmArgs G_(const void* A, int lda, const void* B, int ldb, int M, int N, int K)
     return g;
 }
 
-// every GEMM of an engine goes through here: the launch is timed into the engine's own ring when profiling is on
-int egemm(pnp_engine* e, int bf, GemmArgs g, hipStream_t s) {
+// The launch of a Linear in the engine's mode, y[M, n] = a[M, K] . w[r0 .. r0 + n, K]^T (n = 0: the whole weight); the caller
+// adds the epilogue.  A pair weight (bf16x3) meets either a pair activation, or one fp32 array whose rows the kernel splits
+// (a_f32: the text side, gemm_nt_small_x3_kernel).
+GemmArgs linear(const void* a, int lda, const Weight& w, int M, int r0 = 0, int n = 0) {
+    GemmArgs g = G_(a, lda, w.hi(r0), w.cols, M, n ? n : w.rows, w.cols);
+    g.B_lo = w.lo(r0);
+    g.a_f32 = w.pair;
+    return g;
+}
+GemmArgs linear(const Act& a, int lda, const Weight& w, int M, int r0 = 0, int n = 0) {
+    GemmArgs g = linear(a.hi, lda, w, M, r0, n);
+    g.A_lo = a.lo;
+    g.a_f32 = w.pair && !a.lo;
+    return g;
+}
+// the same product written feature-major, y^T[n, M] = w . a^T: the operands change places
+GemmArgs linear_t(const Act& a, int lda, const Weight& w, int M, int r0 = 0, int n = 0) {
+    GemmArgs g = linear(a, lda, w, M, r0, n);
+    std::swap(g.A, g.B); std::swap(g.A_lo, g.B_lo); std::swap(g.lda, g.ldb); std::swap(g.M, g.N);
+    return g;
+}
+
+// every GEMM of an engine goes through here: the launch is timed into the engine's own ring when profiling is on.  gemm_nt
+// takes the bf16 kernels by itself when an operand is a pair
+int egemm(pnp_engine* e, GemmArgs g, hipStream_t s) {
     g.prof = e->gemm_prof;
     g.sk = e->sk_ws.part ? &e->sk_ws : nullptr;
-    return gemm_nt(bf, g, s);
+    return gemm_nt(e->bf, g, s);
 }
-
-// a text-side Linear (M = B*L rows): in the split-bf16 mode the weight is a (hi | lo) bf16 pair and the fp32 activations are
-// split by the kernel (gemm_nt_small_x3_kernel); otherwise the compute type's generic kernel
-int tgemm(pnp_engine* e, GemmArgs g, hipStream_t s) {
-    if (e->x3) {
-        g.a_f32 = 1;
-        g.B_lo = (const char*)g.B + (size_t)g.N * g.K * 2;      // make_weight(split): lo array behind the hi array
-    }
-    return egemm(e, e->bf, g, s);
-}
-
-const char* kVitNames[] = {"norm1.weight", "norm1.bias", "attn.qkv.weight", "attn.qkv.bias", "attn.proj.weight",
-                           "attn.proj.bias", "norm2.weight", "norm2.bias", "mlp.fc1.weight", "mlp.fc1.bias",
-                           "mlp.fc2.weight", "mlp.fc2.bias"};
 
 }  // namespace
 
@@ -385,12 +430,6 @@ extern "C" void pnp_destroy(pnp_engine* e) {
     delete e;
 }
 
-static int create_impl(const pnp_config* cfg, pnp_engine* donor, pnp_engine** out);
-extern "C" int pnp_create(const pnp_config* cfg, pnp_engine** out) { return create_impl(cfg, nullptr, out); }
-extern "C" int pnp_create_shared(const pnp_config* cfg, pnp_engine* donor, pnp_engine** out) {
-    if (!donor) return PNP_ERR_ARG;
-    return create_impl(cfg, donor, out);
-}
 static int create_impl(const pnp_config* cfg, pnp_engine* donor, pnp_engine** out) {
     if (!cfg || !out) return PNP_ERR_ARG;
     pnp_engine* e = new pnp_engine();
@@ -453,16 +492,16 @@ static int create_impl(const pnp_config* cfg, pnp_engine* donor, pnp_engine** ou
     KCHK(e, dalloc_t(e, &e->patches, B * e->PP * 768));
     KCHK(e, dalloc(e, &e->x, M * D));
     KCHK(e, dalloc(e, &e->x0, M * D));
-    KCHK(e, dalloc_t(e, &e->xn, M * D));
+    KCHK(e, alloc_act(e, &e->xn, M, D));
     // bf16 / split-bf16 modes: fused q|k|v rows at a stride of 3D + 64 elements; fp32 mode: q|k rows (v goes to vt).
     // The pad matters: an attention K / V tile is 64 rows x 128 B at the row stride, and at 6144 B (3D bf16, D = 1024) those
     // rows crowd a few L2 channels -- 151 us per launch against 136-138 us at 6272 ... 6656 B (tools/attn_ld_probe.py)
     e->ldq = 3 * (int)D + 64;
-    KCHK(e, dalloc_t(e, &e->qk, M * (size_t)e->ldq));
+    KCHK(e, alloc_act(e, &e->qk, M, e->ldq));
     KCHK(e, dalloc_t(e, &e->vt, D * ldv, true));
-    KCHK(e, dalloc_t(e, &e->ctx, M * D));
-    KCHK(e, dalloc_t(e, &e->h1, M * D * c.vit_mlp_ratio));
-    KCHK(e, dalloc_t(e, &e->embT, M * D));
+    KCHK(e, alloc_act(e, &e->ctx, M, D));
+    KCHK(e, alloc_act(e, &e->h1, M, D * c.vit_mlp_ratio));
+    KCHK(e, alloc_act(e, &e->embT, M, D));
     KCHK(e, dalloc(e, &e->emb32, M * D));
     const int nVn = e->TL - e->SL, nKt = e->TL - e->SL - 1;
     KCHK(e, dalloc_t(e, &e->Knat, M * TL * H));
@@ -552,7 +591,6 @@ static int create_impl(const pnp_config* cfg, pnp_engine* donor, pnp_engine** ou
         KCHK(e, dalloc(e, &v.n1w, D)); KCHK(e, dalloc(e, &v.n1b, D)); KCHK(e, dalloc(e, &v.n2w, D)); KCHK(e, dalloc(e, &v.n2b, D));
         KCHK(e, dalloc(e, &v.qkv_b, 3 * D)); KCHK(e, dalloc(e, &v.proj_b, D));
         KCHK(e, dalloc(e, &v.fc1_b, D * c.vit_mlp_ratio)); KCHK(e, dalloc(e, &v.fc2_b, D));
-        v.qkv_w = v.proj_w = v.fc1_w = v.fc2_w = nullptr;
     }
     for (auto& t : e->txt) {
         KCHK(e, dalloc(e, &t.qkv_b, 3 * H)); KCHK(e, dalloc(e, &t.so_b, H)); KCHK(e, dalloc(e, &t.sln_w, H)); KCHK(e, dalloc(e, &t.sln_b, H));
@@ -562,96 +600,112 @@ static int create_impl(const pnp_config* cfg, pnp_engine* donor, pnp_engine** ou
     e->to_store = false;
     return PNP_OK;
 }
+extern "C" int pnp_create(const pnp_config* cfg, pnp_engine** out) { return create_impl(cfg, nullptr, out); }
+extern "C" int pnp_create_shared(const pnp_config* cfg, pnp_engine* donor, pnp_engine** out) {
+    if (!donor) return PNP_ERR_ARG;
+    return create_impl(cfg, donor, out);
+}
 
 // =========================================================================================== weights
 
 namespace {
 
-struct Slot {
-    float* small = nullptr;    // direct fp32 destination (biases, LN, embeddings)
+// One tensor of the reference state dict and where it goes.  The three lists below (top level, ViT block, text layer) are the
+// only place that names the keys: pnp_load_weight resolves a name through them, pnp_finalize_weights walks them to see that
+// everything arrived.
+struct Key {
+    const char* name = "";
+    float* small = nullptr;    // direct fp32 destination (biases, LN, embeddings); null: a GEMM weight, staged fp32 until finalize
     size_t small_off = 0;      // element offset inside `small`
-    bool gemm = false;         // GEMM weight: staged fp32 until finalize
-    int rows = 0, cols = 0;
+    int rows = 1, cols = 0;
+    int id = 0;                // GEMM weight: its index in finalize's array of staged pointers (the enums below)
 };
+Key small(const char* name, float* p, int count, size_t off = 0) { return {name, p, off, 1, count, 0}; }
+Key gemm(const char* name, int id, int rows, int cols) { return {name, nullptr, 0, rows, cols, id}; }
+
+enum { W_PATCH };
+enum { W_QKV, W_PROJ, W_FC1, W_FC2 };
+enum { W_Q, W_K, W_V, W_SO, W_CQ, W_CK, W_CV, W_CO, W_I, W_O, W_MAX };
+
+std::vector<Key> top_keys(pnp_engine* e) {
+    const int D = e->D, H = e->H;
+    return {small("visual_encoder.cls_token", e->cls, D),
+            small("visual_encoder.pos_embed", e->pos, e->N * D),
+            gemm("visual_encoder.patch_embed.proj.weight", W_PATCH, D, 768),
+            small("visual_encoder.patch_embed.proj.bias", e->patch_b, D),
+            small("visual_encoder.norm.weight", e->vnorm_w, D),
+            small("visual_encoder.norm.bias", e->vnorm_b, D),
+            small("text_encoder.embeddings.word_embeddings.weight", e->word, e->c.vocab * H),
+            small("text_encoder.embeddings.position_embeddings.weight", e->tpos, e->c.max_pos * H),
+            small("text_encoder.embeddings.LayerNorm.weight", e->eln_w, H),
+            small("text_encoder.embeddings.LayerNorm.bias", e->eln_b, H),
+            small("itm_head.weight", e->itm_w, 2 * H),
+            small("itm_head.bias", e->itm_b, 2)};
+}
+const char* const kVitPrefix = "visual_encoder.blocks.";
+std::vector<Key> vit_keys(pnp_engine* e, int li) {
+    VitLayerW& v = e->vit[li];
+    const int D = e->D, F = D * e->c.vit_mlp_ratio;
+    return {small("norm1.weight", v.n1w, D),       small("norm1.bias", v.n1b, D),
+            gemm("attn.qkv.weight", W_QKV, 3 * D, D),   small("attn.qkv.bias", v.qkv_b, 3 * D),
+            gemm("attn.proj.weight", W_PROJ, D, D),     small("attn.proj.bias", v.proj_b, D),
+            small("norm2.weight", v.n2w, D),       small("norm2.bias", v.n2b, D),
+            gemm("mlp.fc1.weight", W_FC1, F, D),        small("mlp.fc1.bias", v.fc1_b, F),
+            gemm("mlp.fc2.weight", W_FC2, D, F),        small("mlp.fc2.bias", v.fc2_b, D)};
+}
+const char* const kTextPrefix = "text_encoder.encoder.layer.";
+std::vector<Key> text_keys(pnp_engine* e, int li) {
+    TextLayerW& t = e->txt[li];
+    const int D = e->D, H = e->H, I = e->I;
+    const size_t l = (size_t)li * H;               // this layer's part of the layer-major cross K / V biases
+    return {gemm("attention.self.query.weight", W_Q, H, H),            small("attention.self.query.bias", t.qkv_b, H, 0),
+            gemm("attention.self.key.weight", W_K, H, H),              small("attention.self.key.bias", t.qkv_b, H, H),
+            gemm("attention.self.value.weight", W_V, H, H),            small("attention.self.value.bias", t.qkv_b, H, 2 * H),
+            gemm("attention.output.dense.weight", W_SO, H, H),         small("attention.output.dense.bias", t.so_b, H),
+            small("attention.output.LayerNorm.weight", t.sln_w, H),    small("attention.output.LayerNorm.bias", t.sln_b, H),
+            gemm("crossattention.self.query.weight", W_CQ, H, H),      small("crossattention.self.query.bias", t.cq_b, H),
+            gemm("crossattention.self.key.weight", W_CK, H, D),        small("crossattention.self.key.bias", e->ck_b, H, l),
+            gemm("crossattention.self.value.weight", W_CV, H, D),      small("crossattention.self.value.bias", e->cv_b, H, l),
+            gemm("crossattention.output.dense.weight", W_CO, H, H),    small("crossattention.output.dense.bias", t.co_b, H),
+            small("crossattention.output.LayerNorm.weight", t.cln_w, H), small("crossattention.output.LayerNorm.bias", t.cln_b, H),
+            gemm("intermediate.dense.weight", W_I, I, H),              small("intermediate.dense.bias", t.i_b, I),
+            gemm("output.dense.weight", W_O, H, I),                    small("output.dense.bias", t.o_b, H),
+            small("output.LayerNorm.weight", t.oln_w, H),              small("output.LayerNorm.bias", t.oln_b, H)};
+}
+
+bool find_key(const std::vector<Key>& keys, const char* name, Key& out) {
+    for (const Key& k : keys)
+        if (!strcmp(k.name, name)) {
+            out = k;
+            return true;
+        }
+    return false;
+}
 
 // resolve a reference state-dict key
-bool resolve(pnp_engine* e, const std::string& n, Slot& s) {
-    const int D = e->D, H = e->H, I = e->I;
-    auto small = [&](float* p, int count, size_t off = 0) { s.small = p; s.small_off = off; s.rows = 1; s.cols = count; return true; };
-    auto gemm = [&](int r, int c) { s.gemm = true; s.rows = r; s.cols = c; return true; };
-    if (n == "visual_encoder.cls_token") return small(e->cls, D);
-    if (n == "visual_encoder.pos_embed") return small(e->pos, e->N * D);
-    if (n == "visual_encoder.patch_embed.proj.weight") return gemm(D, 768);
-    if (n == "visual_encoder.patch_embed.proj.bias") return small(e->patch_b, D);
-    if (n == "visual_encoder.norm.weight") return small(e->vnorm_w, D);
-    if (n == "visual_encoder.norm.bias") return small(e->vnorm_b, D);
-    if (n == "text_encoder.embeddings.word_embeddings.weight") return small(e->word, e->c.vocab * H);
-    if (n == "text_encoder.embeddings.position_embeddings.weight") return small(e->tpos, e->c.max_pos * H);
-    if (n == "text_encoder.embeddings.LayerNorm.weight") return small(e->eln_w, H);
-    if (n == "text_encoder.embeddings.LayerNorm.bias") return small(e->eln_b, H);
-    if (n == "itm_head.weight") return small(e->itm_w, 2 * H);
-    if (n == "itm_head.bias") return small(e->itm_b, 2);
+bool resolve(pnp_engine* e, const std::string& n, Key& s) {
     int li = -1;
     char rest[128];
-    if (sscanf(n.c_str(), "visual_encoder.blocks.%d.%127s", &li, rest) == 2 && li >= 0 && li < e->c.vit_depth) {
-        VitLayerW& v = e->vit[li];
-        const std::string r(rest);
-        const int F = D * e->c.vit_mlp_ratio;
-        if (r == "norm1.weight") return small(v.n1w, D);
-        if (r == "norm1.bias") return small(v.n1b, D);
-        if (r == "norm2.weight") return small(v.n2w, D);
-        if (r == "norm2.bias") return small(v.n2b, D);
-        if (r == "attn.qkv.bias") return small(v.qkv_b, 3 * D);
-        if (r == "attn.proj.bias") return small(v.proj_b, D);
-        if (r == "mlp.fc1.bias") return small(v.fc1_b, F);
-        if (r == "mlp.fc2.bias") return small(v.fc2_b, D);
-        if (r == "attn.qkv.weight") return gemm(3 * D, D);
-        if (r == "attn.proj.weight") return gemm(D, D);
-        if (r == "mlp.fc1.weight") return gemm(F, D);
-        if (r == "mlp.fc2.weight") return gemm(D, F);
-        return false;
-    }
-    if (sscanf(n.c_str(), "text_encoder.encoder.layer.%d.%127s", &li, rest) == 2 && li >= 0 && li < e->TL) {
-        TextLayerW& t = e->txt[li];
-        const std::string r(rest);
-        if (r == "attention.self.query.bias") return small(t.qkv_b, H, 0);
-        if (r == "attention.self.key.bias") return small(t.qkv_b, H, H);
-        if (r == "attention.self.value.bias") return small(t.qkv_b, H, 2 * H);
-        if (r == "attention.output.dense.bias") return small(t.so_b, H);
-        if (r == "attention.output.LayerNorm.weight") return small(t.sln_w, H);
-        if (r == "attention.output.LayerNorm.bias") return small(t.sln_b, H);
-        if (r == "crossattention.self.query.bias") return small(t.cq_b, H);
-        if (r == "crossattention.self.key.bias") return small(e->ck_b, H, (size_t)li * H);
-        if (r == "crossattention.self.value.bias") return small(e->cv_b, H, (size_t)li * H);
-        if (r == "crossattention.output.dense.bias") return small(t.co_b, H);
-        if (r == "crossattention.output.LayerNorm.weight") return small(t.cln_w, H);
-        if (r == "crossattention.output.LayerNorm.bias") return small(t.cln_b, H);
-        if (r == "intermediate.dense.bias") return small(t.i_b, I);
-        if (r == "output.dense.bias") return small(t.o_b, H);
-        if (r == "output.LayerNorm.weight") return small(t.oln_w, H);
-        if (r == "output.LayerNorm.bias") return small(t.oln_b, H);
-        if (r == "attention.self.query.weight" || r == "attention.self.key.weight" || r == "attention.self.value.weight" ||
-            r == "attention.output.dense.weight" || r == "crossattention.self.query.weight" ||
-            r == "crossattention.output.dense.weight")
-            return gemm(H, H);
-        if (r == "crossattention.self.key.weight" || r == "crossattention.self.value.weight") return gemm(H, D);
-        if (r == "intermediate.dense.weight") return gemm(I, H);
-        if (r == "output.dense.weight") return gemm(H, I);
-        return false;
-    }
-    return false;
+    auto layer_of = [&](const char* prefix, int depth) {      // "<prefix><li>.<rest>" with li < depth
+        const size_t len = strlen(prefix);
+        return n.compare(0, len, prefix) == 0 && sscanf(n.c_str() + len, "%d.%127s", &li, rest) == 2 && li >= 0 && li < depth;
+    };
+    if (layer_of(kVitPrefix, e->c.vit_depth)) return find_key(vit_keys(e, li), rest, s);
+    if (layer_of(kTextPrefix, e->TL)) return find_key(text_keys(e, li), rest, s);
+    return find_key(top_keys(e), n.c_str(), s);
 }
 
 // the optional ITC projections: 1 = `name` is one of the four tensors (staged like a GEMM weight until finalize), 0 = it is
 // not, < 0 = its shape contradicts the model.  The embedding width E is the weight's first dimension.
-int resolve_proj(pnp_engine* e, const std::string& n, const int64_t* shape, int ndim, Slot& s) {
+const char* const kProj[2] = {"vision_proj", "text_proj"};
+int resolve_proj(pnp_engine* e, const std::string& n, const int64_t* shape, int ndim, Key& s) {
     int which = -1;
     bool bias = false;
-    if (n == "vision_proj.weight") which = 0;
-    else if (n == "vision_proj.bias") which = 0, bias = true;
-    else if (n == "text_proj.weight") which = 1;
-    else if (n == "text_proj.bias") which = 1, bias = true;
-    else return 0;
+    for (int i = 0; i < 2; i++) {
+        if (n == std::string(kProj[i]) + ".weight") which = i;
+        if (n == std::string(kProj[i]) + ".bias") which = i, bias = true;
+    }
+    if (which < 0) return 0;
     const int K = which == 0 ? e->D : e->H;
     if (ndim != (bias ? 1 : 2) || (!bias && shape[1] != K))
         return fail(e, PNP_ERR_ARG, "%s: expected %s, second dimension %d", n.c_str(), bias ? "a vector" : "a matrix", K);
@@ -660,10 +714,23 @@ int resolve_proj(pnp_engine* e, const std::string& n, const int64_t* shape, int 
     if (e->proj_E[which] && e->proj_E[which] != (int)E)
         return fail(e, PNP_ERR_ARG, "%s: %lld rows, but the other tensor of this projection has %d", n.c_str(), (long long)E, e->proj_E[which]);
     e->proj_E[which] = (int)E;
-    s.gemm = true;
     s.rows = (int)E;
     s.cols = bias ? 1 : K;
     return 1;
+}
+
+const float* staged(pnp_engine* e, const std::string& n) {
+    auto it = e->named.find("stage:" + n);
+    return it == e->named.end() ? nullptr : (const float*)it->second.p;
+}
+
+// every tensor of a family must have arrived; st[id] <- the fp32 staging of its GEMM weights
+int collect(pnp_engine* e, const std::string& prefix, const std::vector<Key>& keys, const float** st) {
+    for (const Key& k : keys) {
+        const std::string n = prefix + k.name;
+        if (k.small ? !e->loaded.count(n) : !(st[k.id] = staged(e, n))) return fail(e, PNP_ERR_STATE, "missing weight %s", n.c_str());
+    }
+    return PNP_OK;
 }
 
 }  // namespace
@@ -674,7 +741,7 @@ extern "C" int pnp_load_weight(pnp_engine* e, const char* name, const float* dat
     if (e->shares_weights) return fail(e, PNP_ERR_STATE, "this engine uses a donor's weights (pnp_create_shared)");
     if (e->finalized) return fail(e, PNP_ERR_STATE, "weights already finalized");
     HIPCHK(e, hipSetDevice(e->c.device));
-    Slot s;
+    Key s;
     const int pj = resolve_proj(e, name, shape, ndim, s);
     if (pj < 0) return pj;
     if (!pj && !resolve(e, name, s)) return PNP_OK;   // strict=False: not a tensor of this path
@@ -702,104 +769,54 @@ extern "C" int pnp_finalize_weights(pnp_engine* e) {
     HIPCHK(e, hipSetDevice(e->c.device));
     e->to_store = true;                        // everything allocated from here to the end of the call is a weight
     struct StoreOff { pnp_engine* e; ~StoreOff() { e->to_store = false; } } store_off{e};
-    const int D = e->D, H = e->H, I = e->I, TL = e->TL;
-    auto stage = [&](const std::string& n) -> const float* {
-        auto it = e->named.find("stage:" + n);
-        return it == e->named.end() ? nullptr : (const float*)it->second.p;
-    };
-#define NEED(ptr, nm)                                                         \
-    const float* ptr = stage(nm);                                             \
-    if (!ptr) return fail(e, PNP_ERR_STATE, "missing weight %s", std::string(nm).c_str());
-    // every small tensor must have arrived too
-    {
-        const char* smalls[] = {"visual_encoder.cls_token", "visual_encoder.pos_embed", "visual_encoder.patch_embed.proj.bias",
-                                "visual_encoder.norm.weight", "visual_encoder.norm.bias",
-                                "text_encoder.embeddings.word_embeddings.weight", "text_encoder.embeddings.position_embeddings.weight",
-                                "text_encoder.embeddings.LayerNorm.weight", "text_encoder.embeddings.LayerNorm.bias",
-                                "itm_head.weight", "itm_head.bias"};
-        for (const char* s : smalls)
-            if (!e->loaded.count(s)) return fail(e, PNP_ERR_STATE, "missing weight %s", s);
-    }
-    {
-        NEED(pw, "visual_encoder.patch_embed.proj.weight");
-        KCHK(e, make_weight(e, pw, D, 768, false, &e->patch_w));
-    }
-    const int F = D * e->c.vit_mlp_ratio;
+    const int D = e->D, H = e->H, I = e->I, TL = e->TL, F = D * e->c.vit_mlp_ratio;
+    const float* st[W_MAX];
+    if (int r = collect(e, "", top_keys(e), st)) return r;
+    KCHK(e, make_weight(e, st[W_PATCH], D, 768, false, &e->patch_w));
     for (int i = 0; i < e->c.vit_depth; i++) {
-        const std::string b = "visual_encoder.blocks." + std::to_string(i) + ".";
-        for (const char* k : kVitNames)
-            if (!e->loaded.count(b + k)) return fail(e, PNP_ERR_STATE, "missing weight %s%s", b.c_str(), k);
-        NEED(w0, b + "attn.qkv.weight");
-        NEED(w1, b + "attn.proj.weight");
-        NEED(w2, b + "mlp.fc1.weight");
-        NEED(w3, b + "mlp.fc2.weight");
-        KCHK(e, make_weight(e, w0, 3 * D, D, false, &e->vit[i].qkv_w, e->x3));
-        KCHK(e, make_weight(e, w1, D, D, false, &e->vit[i].proj_w, e->x3));
-        KCHK(e, make_weight(e, w2, F, D, false, &e->vit[i].fc1_w, e->x3));
-        KCHK(e, make_weight(e, w3, D, F, false, &e->vit[i].fc2_w, e->x3));
+        VitLayerW& v = e->vit[i];
+        if (int r = collect(e, kVitPrefix + std::to_string(i) + ".", vit_keys(e, i), st)) return r;
+        KCHK(e, make_weight(e, st[W_QKV], 3 * D, D, false, &v.qkv_w, e->x3));
+        KCHK(e, make_weight(e, st[W_PROJ], D, D, false, &v.proj_w, e->x3));
+        KCHK(e, make_weight(e, st[W_FC1], F, D, false, &v.fc1_w, e->x3));
+        KCHK(e, make_weight(e, st[W_FC2], D, F, false, &v.fc2_w, e->x3));
     }
     // cross-attention K / V weights of all layers, layer-major, so one GEMM projects every layer
-    KCHK(e, dalloc_t(e, &e->ck_w, (size_t)TL * H * D));
-    KCHK(e, dalloc_t(e, &e->cv_w, (size_t)TL * H * D));
+    KCHK(e, new_weight(e, TL * H, D, e->x3, &e->ck_w));
+    KCHK(e, new_weight(e, TL * H, D, e->x3, &e->cv_w));
     for (int i = 0; i < TL; i++) {
-        const std::string b = "text_encoder.encoder.layer." + std::to_string(i) + ".";
         TextLayerW& t = e->txt[i];
-        const char* req[] = {"attention.self.query.bias", "attention.self.key.bias", "attention.self.value.bias",
-                             "attention.output.dense.bias", "attention.output.LayerNorm.weight", "attention.output.LayerNorm.bias",
-                             "crossattention.self.query.bias", "crossattention.self.key.bias", "crossattention.self.value.bias",
-                             "crossattention.output.dense.bias", "crossattention.output.LayerNorm.weight",
-                             "crossattention.output.LayerNorm.bias", "intermediate.dense.bias", "output.dense.bias",
-                             "output.LayerNorm.weight", "output.LayerNorm.bias"};
-        for (const char* k : req)
-            if (!e->loaded.count(b + k)) return fail(e, PNP_ERR_STATE, "missing weight %s%s", b.c_str(), k);
-        NEED(wq, b + "attention.self.query.weight");
-        NEED(wk, b + "attention.self.key.weight");
-        NEED(wv, b + "attention.self.value.weight");
-        NEED(wso, b + "attention.output.dense.weight");
-        NEED(wcq, b + "crossattention.self.query.weight");
-        NEED(wck, b + "crossattention.self.key.weight");
-        NEED(wcv, b + "crossattention.self.value.weight");
-        NEED(wco, b + "crossattention.output.dense.weight");
-        NEED(wi, b + "intermediate.dense.weight");
-        NEED(wo, b + "output.dense.weight");
+        if (int r = collect(e, kTextPrefix + std::to_string(i) + ".", text_keys(e, i), st)) return r;
         // fused self q|k|v [3H, H]
         float* fused = nullptr;
         HIPCHK(e, hipMalloc((void**)&fused, (size_t)3 * H * H * 4));
-        HIPCHK(e, hipMemcpy(fused, wq, (size_t)H * H * 4, hipMemcpyDeviceToDevice));
-        HIPCHK(e, hipMemcpy(fused + (size_t)H * H, wk, (size_t)H * H * 4, hipMemcpyDeviceToDevice));
-        HIPCHK(e, hipMemcpy(fused + (size_t)2 * H * H, wv, (size_t)H * H * 4, hipMemcpyDeviceToDevice));
+        HIPCHK(e, hipMemcpy(fused, st[W_Q], (size_t)H * H * 4, hipMemcpyDeviceToDevice));
+        HIPCHK(e, hipMemcpy(fused + (size_t)H * H, st[W_K], (size_t)H * H * 4, hipMemcpyDeviceToDevice));
+        HIPCHK(e, hipMemcpy(fused + (size_t)2 * H * H, st[W_V], (size_t)H * H * 4, hipMemcpyDeviceToDevice));
         int r = make_weight(e, fused, 3 * H, H, false, &t.qkv_w, e->x3);
         if (r == PNP_OK && i > e->SL) r = make_weight(e, fused, 3 * H, H, true, &t.qkv_wT, e->x3);
         (void)hipFree(fused);
         if (r != PNP_OK) return r;
-        KCHK(e, make_weight(e, wso, H, H, false, &t.so_w, e->x3));
-        KCHK(e, make_weight(e, wcq, H, H, false, &t.cq_w, e->x3));
-        KCHK(e, make_weight(e, wco, H, H, false, &t.co_w, e->x3));
-        KCHK(e, make_weight(e, wi, I, H, false, &t.i_w, e->x3));
-        KCHK(e, make_weight(e, wo, H, I, false, &t.o_w, e->x3));
-        if (e->x3) {               // (hi | lo) halves over all layers: hi[TL*H*D] then lo[TL*H*D]
-            const size_t half = (size_t)TL * H * D * 2, off = (size_t)i * H * D * 2;
-            KCHK(e, split_f32(wck, (char*)e->ck_w + off, (char*)e->ck_w + half + off, (size_t)H * D, 0));
-            KCHK(e, split_f32(wcv, (char*)e->cv_w + off, (char*)e->cv_w + half + off, (size_t)H * D, 0));
-        } else {
-            KCHK(e, cast_f32(e->bf, wck, (char*)e->ck_w + (size_t)i * H * D * e->esz, (size_t)H * D, 0));
-            KCHK(e, cast_f32(e->bf, wcv, (char*)e->cv_w + (size_t)i * H * D * e->esz, (size_t)H * D, 0));
-        }
+        KCHK(e, make_weight(e, st[W_SO], H, H, false, &t.so_w, e->x3));
+        KCHK(e, make_weight(e, st[W_CQ], H, H, false, &t.cq_w, e->x3));
+        KCHK(e, make_weight(e, st[W_CO], H, H, false, &t.co_w, e->x3));
+        KCHK(e, make_weight(e, st[W_I], I, H, false, &t.i_w, e->x3));
+        KCHK(e, make_weight(e, st[W_O], H, I, false, &t.o_w, e->x3));
+        KCHK(e, fill_weight(e, st[W_CK], e->ck_w, i * H, H));
+        KCHK(e, fill_weight(e, st[W_CV], e->cv_w, i * H, H));
         if (i >= e->SL) {
-            KCHK(e, make_weight(e, wo, H, I, true, &t.o_wT, e->x3));      // [I][H]
-            KCHK(e, make_weight(e, wi, I, H, true, &t.i_wT, e->x3));      // [H][I]
-            KCHK(e, make_weight(e, wco, H, H, true, &t.co_wT, e->x3));
+            KCHK(e, make_weight(e, st[W_O], H, I, true, &t.o_wT, e->x3));      // [I][H]
+            KCHK(e, make_weight(e, st[W_I], I, H, true, &t.i_wT, e->x3));      // [H][I]
+            KCHK(e, make_weight(e, st[W_CO], H, H, true, &t.co_wT, e->x3));
         }
         if (i > e->SL) {
-            KCHK(e, make_weight(e, wcq, H, H, true, &t.cq_wT, e->x3));
-            KCHK(e, make_weight(e, wso, H, H, true, &t.so_wT, e->x3));
+            KCHK(e, make_weight(e, st[W_CQ], H, H, true, &t.cq_wT, e->x3));
+            KCHK(e, make_weight(e, st[W_SO], H, H, true, &t.so_wT, e->x3));
         }
     }
-#undef NEED
     // the optional ITC projections: converted like every other Linear weight when weight and bias both arrived
     for (int i = 0; i < 2; i++) {
-        const std::string b = i == 0 ? "vision_proj." : "text_proj.";
-        const float *w = stage(b + "weight"), *bs = stage(b + "bias");
+        const float *w = staged(e, std::string(kProj[i]) + ".weight"), *bs = staged(e, std::string(kProj[i]) + ".bias");
         if (!w || !bs) {
             e->proj_E[i] = 0;
             continue;
@@ -823,11 +840,6 @@ extern "C" int pnp_finalize_weights(pnp_engine* e) {
 
 // embed: 0 = compute the token embeddings (the operator form) | 1 = compute them and keep a copy (drop iteration 0) | 2 = the
 // images are those of the last embed-1 call with the patches of d_dropped zeroed: reuse the copy (embed_reuse_kernel)
-static int vit_forward_impl(pnp_engine* e, const float* d_images, const uint8_t* d_dropped, int32_t B, void* stream, int embed);
-extern "C" int pnp_vit_forward(pnp_engine* e, const float* d_images, const uint8_t* d_dropped, int32_t B, void* stream) {
-    if (e) e->reuse.vit = false;                 // the operator form writes e->x: x0 no longer describes what follows
-    return vit_forward_impl(e, d_images, d_dropped, B, stream, 0);
-}
 static int vit_forward_impl(pnp_engine* e, const float* d_images, const uint8_t* d_dropped, int32_t B, void* stream, int embed) {
     if (!e || !d_images) return PNP_ERR_ARG;
     if (!e->finalized) return fail(e, PNP_ERR_STATE, "weights not finalized");
@@ -839,183 +851,193 @@ static int vit_forward_impl(pnp_engine* e, const float* d_images, const uint8_t*
     if (embed == 2 && d_dropped) {
         hipLaunchKernelGGL(embed_reuse_kernel, dim3(2048), dim3(256), 0, s, (const float*)e->x0, d_dropped, (const float*)e->patch_b,
                            (const float*)e->pos, e->x, M, N, D / 4);
-        if (hipGetLastError() != hipSuccess) return fail(e, PNP_ERR_HIP, "embed_reuse launch");
+        KCHK(e, launched());
     } else {
-    KCHK(e, patchify(bf, d_images, d_dropped, e->patches, B, e->c.img_size, e->P, s));
-    KCHK(e, cls_rows(e->cls, e->pos, e->x, B, N, D, s));
-    {
-        GemmArgs g = G_(e->patches, 768, e->patch_w, 768, B * e->PP, D, 768);
-        g.bias = e->patch_b; g.resid = e->pos; g.ldr = D; g.out_f32 = e->x; g.ldo = D; g.row_div = e->PP;
-        KCHK(e, egemm(e, bf, g, s));
-    }
-    if (embed == 1) {
-        HIPCHK(e, hipMemcpyAsync(e->x0, e->x, (size_t)M * D * sizeof(float), hipMemcpyDeviceToDevice, s));
-        e->reuse.images = d_images;
-        e->reuse.B = B;
-        e->reuse.vit = true;
-    }
+        KCHK(e, patchify(bf, d_images, d_dropped, e->patches, B, e->c.img_size, e->P, s));
+        KCHK(e, cls_rows(e->cls, e->pos, e->x, B, N, D, s));
+        {
+            GemmArgs g = linear(e->patches, 768, e->patch_w, B * e->PP);
+            g.bias = e->patch_b; g.resid = e->pos; g.ldr = D; g.out_f32 = e->x; g.ldo = D; g.row_div = e->PP;
+            KCHK(e, egemm(e, g, s));
+        }
+        if (embed == 1) {
+            HIPCHK(e, hipMemcpyAsync(e->x0, e->x, (size_t)M * D * sizeof(float), hipMemcpyDeviceToDevice, s));
+            e->reuse.images = d_images;
+            e->reuse.B = B;
+            e->reuse.vit = true;
+        }
     }
     const float scale = 1.0f / sqrtf(64.f);
-    if (e->x3) {
-        // split-bf16 ("bf16x3"): every Linear of the block is a wide-kernel launch on (hi, lo) bf16 operand pairs -- three
-        // bf16 MFMA passes per product, fp32-class result; LayerNorm, the attention kernel and the GELU epilogue hand the
-        // next GEMM its operand already split; attention runs in the split form of the bf16 kernel (vit_attn32_x3_kernel).
-        const size_t cap = (size_t)e->c.max_batch * N;                    // row capacity of the activation buffers
-        void* const xn_lo = (char*)e->xn + cap * D * 2;
-        void* const ctx_lo = (char*)e->ctx + cap * D * 2;
-        void* const h1_lo = (char*)e->h1 + cap * F * 2;
-        void* const qk_lo = (char*)e->qk + cap * e->ldq * 2;
-        for (int l = 0; l < e->c.vit_depth; l++) {
-            const VitLayerW& w = e->vit[l];
-            const char* const qkv_lo = (const char*)w.qkv_w + (size_t)3 * D * D * 2;
-            KCHK(e, layernorm(1, e->x, w.n1w, w.n1b, e->c.vit_ln_eps, M, D, nullptr, e->xn, nullptr, nullptr, s, xn_lo));
-            {   // q | k | v in one launch as a (hi, lo) bf16 pair: [M, 3D] each, halves of the qk buffer
-                GemmArgs g = G_(e->xn, D, w.qkv_w, D, M, 3 * D, D);
-                g.A_lo = xn_lo; g.B_lo = qkv_lo;
-                g.bias = w.qkv_b; g.out_t = e->qk; g.out_lo = qk_lo; g.ldo_t = e->ldq;
-                KCHK(e, egemm(e, 1, g, s));
-            }
-            KCHK(e, vit_attention_x3(e->qk, qk_lo, e->ldq, D, e->ctx, ctx_lo, B, e->c.vit_heads, N, scale, s));
-            {
-                GemmArgs g = G_(e->ctx, D, w.proj_w, D, M, D, D);
-                g.A_lo = ctx_lo; g.B_lo = (const char*)w.proj_w + (size_t)D * D * 2;
-                g.bias = w.proj_b; g.resid = e->x; g.ldr = D; g.out_f32 = e->x; g.ldo = D;
-                KCHK(e, egemm(e, 1, g, s));
-            }
-            KCHK(e, layernorm(1, e->x, w.n2w, w.n2b, e->c.vit_ln_eps, M, D, nullptr, e->xn, nullptr, nullptr, s, xn_lo));
-            {
-                GemmArgs g = G_(e->xn, D, w.fc1_w, D, M, F, D);
-                g.A_lo = xn_lo; g.B_lo = (const char*)w.fc1_w + (size_t)F * D * 2;
-                g.bias = w.fc1_b; g.mode = GEMM_EPI_GELU; g.out_t = e->h1; g.out_lo = h1_lo; g.ldo_t = F;
-                KCHK(e, egemm(e, 1, g, s));
-            }
-            {
-                GemmArgs g = G_(e->h1, F, w.fc2_w, F, M, D, F);
-                g.A_lo = h1_lo; g.B_lo = (const char*)w.fc2_w + (size_t)D * F * 2;
-                g.bias = w.fc2_b; g.resid = e->x; g.ldr = D; g.out_f32 = e->x; g.ldo = D;
-                KCHK(e, egemm(e, 1, g, s));
-            }
-        }
-        KCHK(e, layernorm(1, e->x, e->vnorm_w, e->vnorm_b, e->c.vit_ln_eps, M, D, e->emb32, e->embT, nullptr, nullptr, s,
-                          (char*)e->embT + cap * D * 2));
-        return pnp_cross_kv(e, B, stream);
-    }
+    // split-bf16 ("bf16x3"): every Linear of the block is a wide-kernel launch on (hi, lo) bf16 operand pairs -- three bf16 MFMA
+    // passes per product, fp32-class result; LayerNorm, the attention kernel and the GELU epilogue hand the next GEMM its
+    // operand already split (the handles' lo halves, null in the other modes)
+    const int ln = bf | e->x3;                   // LayerNorm writes bf16 for the pair too
     for (int l = 0; l < e->c.vit_depth; l++) {
         const VitLayerW& w = e->vit[l];
-        KCHK(e, layernorm(bf, e->x, w.n1w, w.n1b, e->c.vit_ln_eps, M, D, nullptr, e->xn, nullptr, nullptr, s));
-        if (bf) {   // q | k | v natural in one launch: [M, 3D]; the attention kernel transposes V on its LDS reads
-            GemmArgs g = G_(e->xn, D, w.qkv_w, D, M, 3 * D, D);
-            g.bias = w.qkv_b; g.out_t = e->qk; g.ldo_t = e->ldq;
-            KCHK(e, egemm(e, bf, g, s));
-            KCHK(e, vit_attention(bf, e->qk, e->ldq, D, (const char*)e->qk + (size_t)2 * D * e->esz, e->ldq, e->Npad, e->ctx, B,
-                                  e->c.vit_heads, N, scale, s));
+        KCHK(e, layernorm(ln, e->x, w.n1w, w.n1b, e->c.vit_ln_eps, M, D, nullptr, e->xn.hi, nullptr, nullptr, s, e->xn.lo));
+        if (bf || e->x3) {   // q | k | v natural in one launch: [M, 3D] at the padded stride; the attention kernel transposes V on its LDS reads
+            GemmArgs g = linear(e->xn, D, w.qkv_w, M);
+            g.bias = w.qkv_b; g.out_t = e->qk.hi; g.out_lo = e->qk.lo; g.ldo_t = e->ldq;
+            KCHK(e, egemm(e, g, s));
+            if (e->x3)       // the split form of the bf16 kernel (vit_attn32_x3_kernel)
+                KCHK(e, vit_attention_x3(e->qk.hi, e->qk.lo, e->ldq, D, e->ctx.hi, e->ctx.lo, B, e->c.vit_heads, N, scale, s));
+            else
+                KCHK(e, vit_attention(bf, e->qk.hi, e->ldq, D, (const char*)e->qk.hi + (size_t)2 * D * e->esz, e->ldq, e->Npad, e->ctx.hi,
+                                      B, e->c.vit_heads, N, scale, s));
         } else {
-        {   // q | k  natural: [M, 2D]
-            GemmArgs g = G_(e->xn, D, w.qkv_w, D, M, 2 * D, D);
-            g.bias = w.qkv_b; g.out_t = e->qk; g.ldo_t = 2 * D;
-            KCHK(e, egemm(e, bf, g, s));
-        }
-        {   // V^T: [D, B*Npad] = Wv . xn^T, token columns padded per image
-            GemmArgs g = G_((const char*)w.qkv_w + (size_t)2 * D * D * e->esz, D, e->xn, D, D, M, D);
-            g.bias = w.qkv_b + 2 * D; g.bias_on_rows = 1; g.out_t = e->vt; g.ldo_t = ldv; g.col_div = N; g.col_pad = e->Npad;
-            KCHK(e, egemm(e, bf, g, s));
-        }
-        KCHK(e, vit_attention(bf, e->qk, 2 * D, D, e->vt, ldv, e->Npad, e->ctx, B, e->c.vit_heads, N, scale, s));
+            {   // q | k  natural: [M, 2D]
+                GemmArgs g = linear(e->xn, D, w.qkv_w, M, 0, 2 * D);
+                g.bias = w.qkv_b; g.out_t = e->qk.hi; g.ldo_t = 2 * D;
+                KCHK(e, egemm(e, g, s));
+            }
+            {   // V^T: [D, B*Npad] = Wv . xn^T, token columns padded per image
+                GemmArgs g = linear_t(e->xn, D, w.qkv_w, M, 2 * D, D);
+                g.bias = w.qkv_b + 2 * D; g.bias_on_rows = 1; g.out_t = e->vt; g.ldo_t = ldv; g.col_div = N; g.col_pad = e->Npad;
+                KCHK(e, egemm(e, g, s));
+            }
+            KCHK(e, vit_attention(bf, e->qk.hi, 2 * D, D, e->vt, ldv, e->Npad, e->ctx.hi, B, e->c.vit_heads, N, scale, s));
         }
         {
-            GemmArgs g = G_(e->ctx, D, w.proj_w, D, M, D, D);
+            GemmArgs g = linear(e->ctx, D, w.proj_w, M);
             g.bias = w.proj_b; g.resid = e->x; g.ldr = D; g.out_f32 = e->x; g.ldo = D;
-            KCHK(e, egemm(e, bf, g, s));
+            KCHK(e, egemm(e, g, s));
         }
-        KCHK(e, layernorm(bf, e->x, w.n2w, w.n2b, e->c.vit_ln_eps, M, D, nullptr, e->xn, nullptr, nullptr, s));
+        KCHK(e, layernorm(ln, e->x, w.n2w, w.n2b, e->c.vit_ln_eps, M, D, nullptr, e->xn.hi, nullptr, nullptr, s, e->xn.lo));
         {
-            GemmArgs g = G_(e->xn, D, w.fc1_w, D, M, F, D);
-            g.bias = w.fc1_b; g.mode = GEMM_EPI_GELU; g.out_t = e->h1; g.ldo_t = F;
-            KCHK(e, egemm(e, bf, g, s));
+            GemmArgs g = linear(e->xn, D, w.fc1_w, M);
+            g.bias = w.fc1_b; g.mode = GEMM_EPI_GELU; g.out_t = e->h1.hi; g.out_lo = e->h1.lo; g.ldo_t = F;
+            KCHK(e, egemm(e, g, s));
         }
         {
-            GemmArgs g = G_(e->h1, F, w.fc2_w, F, M, D, F);
+            GemmArgs g = linear(e->h1, F, w.fc2_w, M);
             g.bias = w.fc2_b; g.resid = e->x; g.ldr = D; g.out_f32 = e->x; g.ldo = D;
-            KCHK(e, egemm(e, bf, g, s));
+            KCHK(e, egemm(e, g, s));
         }
     }
-    KCHK(e, layernorm(bf, e->x, e->vnorm_w, e->vnorm_b, e->c.vit_ln_eps, M, D, e->emb32, e->embT, nullptr, nullptr, s));
+    KCHK(e, layernorm(ln, e->x, e->vnorm_w, e->vnorm_b, e->c.vit_ln_eps, M, D, e->emb32, e->embT.hi, nullptr, nullptr, s, e->embT.lo));
     return pnp_cross_kv(e, B, stream);
+}
+extern "C" int pnp_vit_forward(pnp_engine* e, const float* d_images, const uint8_t* d_dropped, int32_t B, void* stream) {
+    if (e) e->reuse.vit = false;                 // the operator form writes e->x: x0 no longer describes what follows
+    return vit_forward_impl(e, d_images, d_dropped, B, stream, 0);
 }
 
 // encoder_hidden_states -> key / value of every text layer's cross-attention (B/med.py:208-211): the reference
 // projects image_embeds once per layer inside BertSelfAttention.forward; here all 12 layers are projected in four
-// GEMMs (natural + transposed layouts) right after the ViT, from the compute-type copy of image_embeds.
+// launches (natural + transposed layouts) right after the ViT, from the compute-type copy of image_embeds.
 extern "C" int pnp_cross_kv(pnp_engine* e, int32_t B, void* stream) {
     if (!e) return PNP_ERR_ARG;
     if (!e->finalized) return fail(e, PNP_ERR_STATE, "weights not finalized");
     if (B <= 0 || B > e->c.max_batch) return fail(e, PNP_ERR_ARG, "batch %d out of range (max %d)", B, e->c.max_batch);
     hipStream_t s = (hipStream_t)stream;
-    const int D = e->D, N = e->N, M = B * N, bf = e->bf;
+    const int D = e->D, N = e->N, M = B * N;
     const int ldv = e->c.max_batch * e->Npad;
-    const int H = e->H, TL = e->TL, SL = e->SL;
-    if (e->x3) {
-        const size_t cap = (size_t)e->c.max_batch * N, whalf = (size_t)TL * H * D * 2;
-        const void* const emb_lo = (const char*)e->embT + cap * D * 2;
-        const char *ck = (const char*)e->ck_w, *cv = (const char*)e->cv_w;
-        {
-            GemmArgs g = G_(e->embT, D, ck, D, M, TL * H, D);
-            g.A_lo = emb_lo; g.B_lo = ck + whalf;
-            g.bias = e->ck_b; g.out_f32 = (float*)e->Knat; g.ldo = TL * H;
-            KCHK(e, egemm(e, 1, g, s));
-        }
-        {
-            GemmArgs g = G_(cv, D, e->embT, D, TL * H, M, D);
-            g.A_lo = cv + whalf; g.B_lo = emb_lo;
-            g.bias = e->cv_b; g.bias_on_rows = 1; g.out_f32 = (float*)e->Vt; g.ldo = ldv; g.col_div = N; g.col_pad = e->Npad;
-            KCHK(e, egemm(e, 1, g, s));
-        }
-        {   // V token-major of layers >= SL from V^T, K^T of layers > SL from K token-major (see feat_to_tok_kernel)
-            const int nVn = TL - SL, R = nVn * H;
-            hipLaunchKernelGGL(feat_to_tok_kernel, dim3((R + 31) / 32, (N + 31) / 32, B), dim3(32, 8), 0, s,
-                               (const float*)e->Vt + (size_t)SL * H * ldv, ldv, e->Npad, (float*)e->Vnat, R, N);
-            const int nKt = TL - SL - 1;
-            if (nKt > 0)
-                hipLaunchKernelGGL(tok_to_feat_kernel, dim3((nKt * H + 31) / 32, (N + 31) / 32, B), dim3(32, 8), 0, s,
-                                   (const float*)e->Knat + (size_t)(SL + 1) * H, TL * H, (float*)e->Kt, ldv, e->Npad, nKt * H, N);
-            if (hipGetLastError() != hipSuccess) return fail(e, PNP_ERR_HIP, "cross K / V layout kernels failed to launch");
+    const int H = e->H, TL = e->TL, SL = e->SL, nVn = TL - SL, nKt = TL - SL - 1;
+    // K token-major and V^T feature-major of all layers: fp32 from the pair GEMM in bf16x3, the compute type otherwise
+    auto out = [&](GemmArgs& g, void* p, int ld) {
+        if (e->x3) { g.out_f32 = (float*)p; g.ldo = ld; }
+        else { g.out_t = p; g.ldo_t = ld; }
+    };
+    {
+        GemmArgs g = linear(e->embT, D, e->ck_w, M);
+        g.bias = e->ck_b; out(g, e->Knat, TL * H);
+        KCHK(e, egemm(e, g, s));
+    }
+    {
+        GemmArgs g = linear_t(e->embT, D, e->cv_w, M);
+        g.bias = e->cv_b; g.bias_on_rows = 1; out(g, e->Vt, ldv); g.col_div = N; g.col_pad = e->Npad;
+        KCHK(e, egemm(e, g, s));
+    }
+    // V token-major of layers >= SL, K^T of layers > SL
+    if (e->x3) {             // from V^T and from K token-major (see feat_to_tok_kernel)
+        hipLaunchKernelGGL(feat_to_tok_kernel, dim3((nVn * H + 31) / 32, (N + 31) / 32, B), dim3(32, 8), 0, s,
+                           (const float*)e->Vt + (size_t)SL * H * ldv, ldv, e->Npad, (float*)e->Vnat, nVn * H, N);
+        KCHK(e, launched());
+        if (nKt > 0) {
+            hipLaunchKernelGGL(tok_to_feat_kernel, dim3((nKt * H + 31) / 32, (N + 31) / 32, B), dim3(32, 8), 0, s,
+                               (const float*)e->Knat + (size_t)(SL + 1) * H, TL * H, (float*)e->Kt, ldv, e->Npad, nKt * H, N);
+            KCHK(e, launched());
         }
         return PNP_OK;
     }
     {
-        GemmArgs g = G_(e->embT, D, e->ck_w, D, M, TL * H, D);
-        g.bias = e->ck_b; g.out_t = e->Knat; g.ldo_t = TL * H;
-        KCHK(e, egemm(e, bf, g, s));
-    }
-    {
-        GemmArgs g = G_(e->cv_w, D, e->embT, D, TL * H, M, D);
-        g.bias = e->cv_b; g.bias_on_rows = 1; g.out_t = e->Vt; g.ldo_t = ldv; g.col_div = N; g.col_pad = e->Npad;
-        KCHK(e, egemm(e, bf, g, s));
-    }
-    {
-        const int nVn = TL - SL;
-        GemmArgs g = G_(e->embT, D, (const char*)e->cv_w + (size_t)SL * H * D * e->esz, D, M, nVn * H, D);
+        GemmArgs g = linear(e->embT, D, e->cv_w, M, SL * H, nVn * H);
         g.bias = e->cv_b + (size_t)SL * H; g.out_t = e->Vnat; g.ldo_t = nVn * H;
-        KCHK(e, egemm(e, bf, g, s));
+        KCHK(e, egemm(e, g, s));
     }
-    if (TL - SL - 1 > 0) {
-        const int nKt = TL - SL - 1;
-        GemmArgs g = G_((const char*)e->ck_w + (size_t)(SL + 1) * H * D * e->esz, D, e->embT, D, nKt * H, M, D);
+    if (nKt > 0) {
+        GemmArgs g = linear_t(e->embT, D, e->ck_w, M, (SL + 1) * H, nKt * H);
         g.bias = e->ck_b + (size_t)(SL + 1) * H; g.bias_on_rows = 1; g.out_t = e->Kt; g.ldo_t = ldv; g.col_div = N; g.col_pad = e->Npad;
-        KCHK(e, egemm(e, bf, g, s));
+        KCHK(e, egemm(e, g, s));
     }
+    return PNP_OK;
+}
+
+// One BERT layer of the text stack on the R = B * L rows in place (layer 0 reads h0, layer i the h_out of layer i - 1): the
+// self-attention sub-layer, the cross-attention sub-layer over the image's K / V, the FFN.
+//   cross = false: the text-only form -- no cross-attention sub-layer (the FFN reads a_out), and nothing is kept for the backward
+//   self_in_place: the self-attention sub-layer's outputs of the previous call are valid (text_forward_impl's prefix reuse)
+static int text_layer(pnp_engine* e, int i, const int64_t* d_mask, int32_t ld, int32_t B, int32_t L, bool cross, bool self_in_place,
+                      hipStream_t s) {
+    const int H = e->H, I = e->I, TL = e->TL, R = B * L, bf = e->bf, N = e->N;
+    const int ldv = e->c.max_batch * e->Npad;
+    const TextLayerW& w = e->txt[i];
+    TextLayerA& a = e->ta[i];
+    const float* h = i ? e->ta[i - 1].h_out : e->h0;
+    const void* hT = i ? e->ta[i - 1].h_outT : e->h0T;
+    const bool keep_p = cross && i >= e->SL;                               // the attention probabilities of the stash layers
+    auto keep = [&](float* p) -> float* { return cross ? p : nullptr; };   // the LayerNorm x-hat / rstd the backward reads
+    if (!self_in_place) {
+        {
+            GemmArgs g = linear(hT, H, w.qkv_w, R);
+            g.bias = w.qkv_b; g.out_t = a.qkv; g.ldo_t = 3 * H;
+            KCHK(e, egemm(e, g, s));
+        }
+        KCHK(e, text_self_attn(bf, a.qkv, d_mask, ld, e->ctx_s, keep_p ? a.Ps : nullptr, e->dS, B, L, H, s));
+        {
+            GemmArgs g = linear(e->ctx_s, H, w.so_w, R);
+            g.bias = w.so_b; g.resid = h; g.ldr = H; g.out_f32 = e->tmp; g.ldo = H;
+            KCHK(e, egemm(e, g, s));
+        }
+        KCHK(e, layernorm(bf, e->tmp, w.sln_w, w.sln_b, e->c.txt_ln_eps, R, H, a.a_out, a.a_outT, keep(a.a_hat), keep(a.a_rstd), s));
+    }
+    const float* f = a.a_out;                    // the rows the FFN reads
+    const void* fT = a.a_outT;
+    if (cross) {
+        {
+            GemmArgs g = linear(a.a_outT, H, w.cq_w, R);
+            g.bias = w.cq_b; g.out_t = a.qc; g.ldo_t = H;
+            KCHK(e, egemm(e, g, s));
+        }
+        KCHK(e, xattn(bf, 0, (const char*)e->Knat + (size_t)i * H * e->esz, TL * H,
+                      (const char*)e->Vt + (size_t)i * H * ldv * e->esz, ldv, e->Npad, a.qc, H, e->ctx_c, H,
+                      keep_p ? a.Pc : nullptr, e->Nst, B, L, N, e->nh, s));
+        {
+            GemmArgs g = linear(e->ctx_c, H, w.co_w, R);
+            g.bias = w.co_b; g.resid = a.a_out; g.ldr = H; g.out_f32 = e->tmp; g.ldo = H;
+            KCHK(e, egemm(e, g, s));
+        }
+        KCHK(e, layernorm(bf, e->tmp, w.cln_w, w.cln_b, e->c.txt_ln_eps, R, H, a.c_out, a.c_outT, a.c_hat, a.c_rstd, s));
+        f = a.c_out;
+        fT = a.c_outT;
+    }
+    {
+        GemmArgs g = linear(fT, H, w.i_w, R);
+        g.bias = w.i_b; g.mode = GEMM_EPI_GELU; g.out_t = e->g; g.ldo_t = I;
+        if (cross) { g.aux = a.u; g.ld_aux = I; }                          // the GELU pre-activation, for the backward
+        KCHK(e, egemm(e, g, s));
+    }
+    {
+        GemmArgs g = linear(e->g, I, w.o_w, R);
+        g.bias = w.o_b; g.resid = f; g.ldr = H; g.out_f32 = e->tmp; g.ldo = H;
+        KCHK(e, egemm(e, g, s));
+    }
+    KCHK(e, layernorm(bf, e->tmp, w.oln_w, w.oln_b, e->c.txt_ln_eps, R, H, a.h_out, a.h_outT, keep(a.o_hat), keep(a.o_rstd), s));
     return PNP_OK;
 }
 
 // reuse_prefix: the token ids / mask are those of the previous call on this engine (drop iterations 1..): the embeddings and the
 // self-attention sub-layer of text layer 0 do not see the image -- their activations of the previous call are still in place
-static int text_forward_impl(pnp_engine* e, const int64_t* d_ids, const int64_t* d_mask, int32_t ld, int32_t B, int32_t L,
-                             float* d_logits, void* stream, bool reuse_prefix);
-extern "C" int pnp_text_forward_xattn(pnp_engine* e, const int64_t* d_ids, const int64_t* d_mask, int32_t ld, int32_t B,
-                                      int32_t L, float* d_logits, void* stream) {
-    if (e) e->reuse.text = false;
-    return text_forward_impl(e, d_ids, d_mask, ld, B, L, d_logits, stream, false);
-}
 static int text_forward_impl(pnp_engine* e, const int64_t* d_ids, const int64_t* d_mask, int32_t ld, int32_t B, int32_t L,
                              float* d_logits, void* stream, bool reuse_prefix) {
     if (!e || !d_ids || !d_mask) return PNP_ERR_ARG;
@@ -1023,67 +1045,26 @@ static int text_forward_impl(pnp_engine* e, const int64_t* d_ids, const int64_t*
     if (B <= 0 || B > e->c.max_batch || L < 5 || L > e->c.max_text_len || ld < L)
         return fail(e, PNP_ERR_ARG, "text batch %d x %d (ld %d) out of range (max %d x %d)", B, L, ld, e->c.max_batch, e->c.max_text_len);
     hipStream_t s = (hipStream_t)stream;
-    const int H = e->H, I = e->I, TL = e->TL, R = B * L, bf = e->bf, N = e->N, D = e->D;
-    const int ldv = e->c.max_batch * e->Npad;
-    (void)D;
+    const int H = e->H, TL = e->TL, R = B * L;
     e->acts_text_only = false;
     if (reuse_prefix && !(e->reuse.text && e->reuse.ids == d_ids && e->reuse.mask == d_mask && e->reuse.B == B && e->reuse.L == L &&
                           e->reuse.ld == ld))
         reuse_prefix = false;                    // not the captions whose prefix is in place: compute it
     if (!reuse_prefix) {
         KCHK(e, text_embed(d_ids, ld, e->word, e->tpos, e->temb, B, L, H, e->c.enc_token_id, e->c.vocab, s));
-        KCHK(e, layernorm(bf, e->temb, e->eln_w, e->eln_b, e->c.txt_ln_eps, R, H, e->h0, e->h0T, nullptr, nullptr, s));
+        KCHK(e, layernorm(e->bf, e->temb, e->eln_w, e->eln_b, e->c.txt_ln_eps, R, H, e->h0, e->h0T, nullptr, nullptr, s));
     }
-    const float* h = e->h0;
-    const void* hT = e->h0T;
     for (int i = 0; i < TL; i++) {
-        const TextLayerW& w = e->txt[i];
-        TextLayerA& a = e->ta[i];
-        const bool stash = i >= e->SL;
-        if (!(reuse_prefix && i == 0)) {
-        {
-            GemmArgs g = G_(hT, H, w.qkv_w, H, R, 3 * H, H);
-            g.bias = w.qkv_b; g.out_t = a.qkv; g.ldo_t = 3 * H;
-            KCHK(e, tgemm(e, g, s));
-        }
-        KCHK(e, text_self_attn(bf, a.qkv, d_mask, ld, e->ctx_s, stash ? a.Ps : nullptr, e->dS, B, L, H, s));
-        {
-            GemmArgs g = G_(e->ctx_s, H, w.so_w, H, R, H, H);
-            g.bias = w.so_b; g.resid = h; g.ldr = H; g.out_f32 = e->tmp; g.ldo = H;
-            KCHK(e, tgemm(e, g, s));
-        }
-        KCHK(e, layernorm(bf, e->tmp, w.sln_w, w.sln_b, e->c.txt_ln_eps, R, H, a.a_out, a.a_outT, a.a_hat, a.a_rstd, s));
-        }
-        {
-            GemmArgs g = G_(a.a_outT, H, w.cq_w, H, R, H, H);
-            g.bias = w.cq_b; g.out_t = a.qc; g.ldo_t = H;
-            KCHK(e, tgemm(e, g, s));
-        }
-        KCHK(e, xattn(bf, 0, (const char*)e->Knat + (size_t)i * H * e->esz, TL * H,
-                      (const char*)e->Vt + (size_t)i * H * ldv * e->esz, ldv, e->Npad, a.qc, H, e->ctx_c, H,
-                      stash ? a.Pc : nullptr, e->Nst, B, L, N, e->nh, s));
-        {
-            GemmArgs g = G_(e->ctx_c, H, w.co_w, H, R, H, H);
-            g.bias = w.co_b; g.resid = a.a_out; g.ldr = H; g.out_f32 = e->tmp; g.ldo = H;
-            KCHK(e, tgemm(e, g, s));
-        }
-        KCHK(e, layernorm(bf, e->tmp, w.cln_w, w.cln_b, e->c.txt_ln_eps, R, H, a.c_out, a.c_outT, a.c_hat, a.c_rstd, s));
-        {
-            GemmArgs g = G_(a.c_outT, H, w.i_w, H, R, I, H);
-            g.bias = w.i_b; g.mode = GEMM_EPI_GELU; g.aux = a.u; g.ld_aux = I; g.out_t = e->g; g.ldo_t = I;
-            KCHK(e, tgemm(e, g, s));
-        }
-        {
-            GemmArgs g = G_(e->g, I, w.o_w, I, R, H, I);
-            g.bias = w.o_b; g.resid = a.c_out; g.ldr = H; g.out_f32 = e->tmp; g.ldo = H;
-            KCHK(e, tgemm(e, g, s));
-        }
-        KCHK(e, layernorm(bf, e->tmp, w.oln_w, w.oln_b, e->c.txt_ln_eps, R, H, a.h_out, a.h_outT, a.o_hat, a.o_rstd, s));
-        h = a.h_out;
-        hT = a.h_outT;
+        int r = text_layer(e, i, d_mask, ld, B, L, true, reuse_prefix && i == 0, s);
+        if (r) return r;
     }
-    KCHK(e, itm_head(h, e->itm_w, e->itm_b, d_logits ? d_logits : e->logits_scratch, B, L, H, s));
+    KCHK(e, itm_head(e->ta[TL - 1].h_out, e->itm_w, e->itm_b, d_logits ? d_logits : e->logits_scratch, B, L, H, s));
     return PNP_OK;
+}
+extern "C" int pnp_text_forward_xattn(pnp_engine* e, const int64_t* d_ids, const int64_t* d_mask, int32_t ld, int32_t B,
+                                      int32_t L, float* d_logits, void* stream) {
+    if (e) e->reuse.text = false;
+    return text_forward_impl(e, d_ids, d_mask, ld, B, L, d_logits, stream, false);
 }
 
 // BertModel.forward(mode="text") (B/med.py:565-568, 473): the text stack without its cross-attention sub-layers and without the
@@ -1098,7 +1079,7 @@ extern "C" int pnp_text_forward_text(pnp_engine* e, const int64_t* d_ids, const 
         return fail(e, PNP_ERR_ARG, "text batch %d x %d (ld %d) out of range (2 <= L <= %d, T > 0)", T, L, ld, e->c.max_text_len);
     if (!e->finalized) return fail(e, PNP_ERR_STATE, "weights not finalized");
     hipStream_t s = (hipStream_t)stream;
-    const int H = e->H, I = e->I, TL = e->TL, bf = e->bf;
+    const int H = e->H, TL = e->TL;
     e->reuse.text = false;
     e->grad_layer = -1;
     e->acts_text_only = true;
@@ -1107,40 +1088,14 @@ extern "C" int pnp_text_forward_text(pnp_engine* e, const int64_t* d_ids, const 
         const int64_t* ids = d_ids + (size_t)t0 * ld;
         const int64_t* mask = d_mask + (size_t)t0 * ld;
         KCHK(e, text_embed(ids, ld, e->word, e->tpos, e->temb, B, L, H, -1, e->c.vocab, s));
-        KCHK(e, layernorm(bf, e->temb, e->eln_w, e->eln_b, e->c.txt_ln_eps, R, H, e->h0, e->h0T, nullptr, nullptr, s));
-        const float* h = e->h0;
-        const void* hT = e->h0T;
+        KCHK(e, layernorm(e->bf, e->temb, e->eln_w, e->eln_b, e->c.txt_ln_eps, R, H, e->h0, e->h0T, nullptr, nullptr, s));
         for (int i = 0; i < TL; i++) {
-            const TextLayerW& w = e->txt[i];
-            TextLayerA& a = e->ta[i];
-            {
-                GemmArgs g = G_(hT, H, w.qkv_w, H, R, 3 * H, H);
-                g.bias = w.qkv_b; g.out_t = a.qkv; g.ldo_t = 3 * H;
-                KCHK(e, tgemm(e, g, s));
-            }
-            KCHK(e, text_self_attn(bf, a.qkv, mask, ld, e->ctx_s, nullptr, e->dS, B, L, H, s));
-            {
-                GemmArgs g = G_(e->ctx_s, H, w.so_w, H, R, H, H);
-                g.bias = w.so_b; g.resid = h; g.ldr = H; g.out_f32 = e->tmp; g.ldo = H;
-                KCHK(e, tgemm(e, g, s));
-            }
-            KCHK(e, layernorm(bf, e->tmp, w.sln_w, w.sln_b, e->c.txt_ln_eps, R, H, a.a_out, a.a_outT, nullptr, nullptr, s));
-            {
-                GemmArgs g = G_(a.a_outT, H, w.i_w, H, R, I, H);
-                g.bias = w.i_b; g.mode = GEMM_EPI_GELU; g.out_t = e->g; g.ldo_t = I;
-                KCHK(e, tgemm(e, g, s));
-            }
-            {
-                GemmArgs g = G_(e->g, I, w.o_w, I, R, H, I);
-                g.bias = w.o_b; g.resid = a.a_out; g.ldr = H; g.out_f32 = e->tmp; g.ldo = H;
-                KCHK(e, tgemm(e, g, s));
-            }
-            KCHK(e, layernorm(bf, e->tmp, w.oln_w, w.oln_b, e->c.txt_ln_eps, R, H, a.h_out, a.h_outT, nullptr, nullptr, s));
-            h = a.h_out;
-            hT = a.h_outT;
+            int r = text_layer(e, i, mask, ld, B, L, false, false, s);
+            if (r) return r;
         }
         if (d_hidden)
-            HIPCHK(e, hipMemcpyAsync(d_hidden + (size_t)t0 * L * H, h, (size_t)R * H * sizeof(float), hipMemcpyDeviceToDevice, s));
+            HIPCHK(e, hipMemcpyAsync(d_hidden + (size_t)t0 * L * H, e->ta[TL - 1].h_out, (size_t)R * H * sizeof(float),
+                                     hipMemcpyDeviceToDevice, s));
     }
     return PNP_OK;
 }
@@ -1160,9 +1115,9 @@ extern "C" int pnp_project_normalize(pnp_engine* e, int32_t which, const float* 
     if ((int64_t)rows * row_stride * 4 >= (int64_t)1 << 32)
         return fail(e, PNP_ERR_ARG, "rows %d x row_stride %lld: the input must span less than 4 GiB", rows, (long long)row_stride);
     if (!e->finalized) return fail(e, PNP_ERR_STATE, "weights not finalized");
-    if (!e->proj_w[which] || !e->proj_b[which])
-        return fail(e, PNP_ERR_STATE, "missing weight %s (the state dict held no %s.weight / .bias)", which == 0 ? "vision_proj.weight" : "text_proj.weight",
-                    which == 0 ? "vision_proj" : "text_proj");
+    const Weight& w = e->proj_w[which];
+    if (!w.p || !e->proj_b[which])
+        return fail(e, PNP_ERR_STATE, "missing weight %s.weight (the state dict held no %s.weight / .bias)", kProj[which], kProj[which]);
     hipStream_t s = (hipStream_t)stream;
     const int E = e->proj_E[which];
     if (e->bf) {
@@ -1171,15 +1126,15 @@ extern "C" int pnp_project_normalize(pnp_engine* e, int32_t which, const float* 
         cap = cap < 16384 ? cap : 16384;           // (and few enough for the generic tiles: the wide bf16 kernel has no such epilogue)
         for (size_t r0 = 0; r0 < (size_t)rows; r0 += cap) {
             const int n = (int)((size_t)rows - r0 < cap ? (size_t)rows - r0 : cap);
-            KCHK(e, cast_rows_bf16(d_x + r0 * row_stride, (int)row_stride, e->xn, n, K, s));
-            GemmArgs g = G_(e->xn, K, e->proj_w[which], K, n, E, K);
+            KCHK(e, cast_rows_bf16(d_x + r0 * row_stride, (int)row_stride, e->xn.hi, n, K, s));
+            GemmArgs g = linear(e->xn.hi, K, w, n);
             g.bias = e->proj_b[which]; g.out_f32 = d_out + r0 * E; g.ldo = E;
-            KCHK(e, egemm(e, 1, g, s));
+            KCHK(e, egemm(e, g, s));
         }
     } else {
-        GemmArgs g = G_(d_x, (int)row_stride, e->proj_w[which], K, rows, E, K);
+        GemmArgs g = linear(d_x, (int)row_stride, w, rows);
         g.bias = e->proj_b[which]; g.out_f32 = d_out; g.ldo = E;
-        KCHK(e, tgemm(e, g, s));
+        KCHK(e, egemm(e, g, s));
     }
     KCHK(e, l2_normalize_rows(d_out, rows, E, 1e-12f, s));
     return PNP_OK;
@@ -1214,20 +1169,20 @@ extern "C" int pnp_xattn_grad_layer(pnp_engine* e, int32_t B, int32_t L, int32_t
         TextLayerA& a = e->ta[i];
         KCHK(e, layernorm_bwd(bf, e->dh, w.oln_w, a.o_hat, a.o_rstd, R, H, e->d_pre, e->d_preT, s));
         {   // dg = (d_pre . Wo2) * gelu'(u)
-            GemmArgs g = G_(e->d_preT, H, w.o_wT, H, R, I, H);
+            GemmArgs g = linear(e->d_preT, H, w.o_wT, R);
             g.mode = GEMM_EPI_GELU_GRAD; g.aux = a.u; g.ld_aux = I; g.out_t = e->dg; g.ldo_t = I;
-            KCHK(e, tgemm(e, g, s));
+            KCHK(e, egemm(e, g, s));
         }
         {   // dc = d_pre + dg . Wi
-            GemmArgs g = G_(e->dg, I, w.i_wT, I, R, H, I);
+            GemmArgs g = linear(e->dg, I, w.i_wT, R);
             g.resid = e->d_pre; g.ldr = H; g.out_f32 = e->dc; g.ldo = H;
-            KCHK(e, tgemm(e, g, s));
+            KCHK(e, egemm(e, g, s));
         }
         KCHK(e, layernorm_bwd(bf, e->dc, w.cln_w, a.c_hat, a.c_rstd, R, H, e->d_cpre, e->d_cpreT, s));
         {
-            GemmArgs g = G_(e->d_cpreT, H, w.co_wT, H, R, H, H);
+            GemmArgs g = linear(e->d_cpreT, H, w.co_wT, R);
             g.out_t = e->dctxc; g.ldo_t = H;
-            KCHK(e, tgemm(e, g, s));
+            KCHK(e, egemm(e, g, s));
         }
         const char* vnat = (const char*)e->Vnat + (size_t)(i - SL) * H * e->esz;
         if (i == layer) {
@@ -1237,21 +1192,21 @@ extern "C" int pnp_xattn_grad_layer(pnp_engine* e, int32_t B, int32_t L, int32_t
         KCHK(e, xattn(bf, 1, vnat, nVn * H, (const char*)e->Kt + (size_t)(i - SL - 1) * H * ldv * e->esz, ldv, e->Npad,
                       e->dctxc, H, e->dqc, H, a.Pc, e->Nst, B, L, N, e->nh, s));
         {
-            GemmArgs g = G_(e->dqc, H, w.cq_wT, H, R, H, H);
+            GemmArgs g = linear(e->dqc, H, w.cq_wT, R);
             g.resid = e->d_cpre; g.ldr = H; g.out_f32 = e->da; g.ldo = H;
-            KCHK(e, tgemm(e, g, s));
+            KCHK(e, egemm(e, g, s));
         }
         KCHK(e, layernorm_bwd(bf, e->da, w.sln_w, a.a_hat, a.a_rstd, R, H, e->d_apre, e->d_apreT, s));
         {
-            GemmArgs g = G_(e->d_apreT, H, w.so_wT, H, R, H, H);
+            GemmArgs g = linear(e->d_apreT, H, w.so_wT, R);
             g.out_f32 = e->dctx_s; g.ldo = H;
-            KCHK(e, tgemm(e, g, s));
+            KCHK(e, egemm(e, g, s));
         }
         KCHK(e, text_self_attn_bwd(bf, a.qkv, e->dctx_s, a.Ps, e->dS, e->dqkv, B, L, H, s));
         {
-            GemmArgs g = G_(e->dqkv, 3 * H, w.qkv_wT, 3 * H, R, H, 3 * H);
+            GemmArgs g = linear(e->dqkv, 3 * H, w.qkv_wT, R);
             g.resid = e->d_apre; g.ldr = H; g.out_f32 = e->dh; g.ldo = H;
-            KCHK(e, tgemm(e, g, s));
+            KCHK(e, egemm(e, g, s));
         }
     }
     return PNP_OK;
@@ -1270,14 +1225,6 @@ extern "C" int pnp_gradcam_gather(pnp_engine* e, const int64_t* d_mask, int32_t 
 
 static int compute_gradcam_impl(pnp_engine* e, const float* d_images, const uint8_t* d_dropped, const int64_t* d_ids,
                                 const int64_t* d_mask, int32_t ld, int32_t B, int32_t L, int32_t layer, int32_t head,
-                                float* d_out, float* d_logits, void* stream, int embed);
-extern "C" int pnp_compute_gradcam_layer(pnp_engine* e, const float* d_images, const uint8_t* d_dropped, const int64_t* d_ids,
-                                         const int64_t* d_mask, int32_t ld, int32_t B, int32_t L, int32_t layer, int32_t head,
-                                         float* d_out, float* d_logits, void* stream) {
-    return compute_gradcam_impl(e, d_images, d_dropped, d_ids, d_mask, ld, B, L, layer, head, d_out, d_logits, stream, 0);
-}
-static int compute_gradcam_impl(pnp_engine* e, const float* d_images, const uint8_t* d_dropped, const int64_t* d_ids,
-                                const int64_t* d_mask, int32_t ld, int32_t B, int32_t L, int32_t layer, int32_t head,
                                 float* d_out, float* d_logits, void* stream, int embed) {
     int r = vit_forward_impl(e, d_images, d_dropped, B, stream, embed);
     if (r) return r;
@@ -1294,6 +1241,11 @@ static int compute_gradcam_impl(pnp_engine* e, const float* d_images, const uint
     r = pnp_xattn_grad_layer(e, B, L, layer, stream);
     if (r) return r;
     return pnp_gradcam_gather(e, d_mask, ld, B, L, head, d_out, stream);
+}
+extern "C" int pnp_compute_gradcam_layer(pnp_engine* e, const float* d_images, const uint8_t* d_dropped, const int64_t* d_ids,
+                                         const int64_t* d_mask, int32_t ld, int32_t B, int32_t L, int32_t layer, int32_t head,
+                                         float* d_out, float* d_logits, void* stream) {
+    return compute_gradcam_impl(e, d_images, d_dropped, d_ids, d_mask, ld, B, L, layer, head, d_out, d_logits, stream, 0);
 }
 
 extern "C" int pnp_compute_gradcam(pnp_engine* e, const float* d_images, const uint8_t* d_dropped, const int64_t* d_ids,
@@ -1777,7 +1729,7 @@ extern "C" int pnp_get_buffer(pnp_engine* e, const char* name, void** d_ptr, siz
     auto& p = e->post;
     auto set = [&](void* ptr, size_t b) { *d_ptr = ptr; *bytes = b; return PNP_OK; };
     if (n == "image_embeds") return set(e->emb32, B * e->N * (size_t)e->D * 4);
-    if (n == "image_embeds_t") return set(e->embT, B * e->N * (size_t)e->D * e->esz);
+    if (n == "image_embeds_t") return set(e->embT.hi, B * e->N * (size_t)e->D * e->esz);
     if (n == "x") return set(e->x, B * e->N * (size_t)e->D * 4);
     if (n == "P") return set(e->ta[e->grad_layer >= 0 ? e->grad_layer : e->SL].Pc, B * e->nh * L * (size_t)e->Nst * 4);
     if (n == "dP") return set(e->dPc, B * e->nh * L * (size_t)e->Nst * 4);
