@@ -193,7 +193,8 @@ int pnp_blur_minmax(pnp_engine* e, void* stream);                               
 int pnp_densecrf(pnp_engine* e, int32_t iters, float pos_w, float pos_xy, float bi_w, float bi_xy, float bi_rgb,
                  void* stream);                                                                  /* PnP.py:1030-1074 */
 /* argmax (+CRF marginals when from_crf) -> remap -> uint8 labels (concatenated, sum H*W) and, when
- * d_gt was given, hist[n_class*gt + pred] += 1 (PnP.py:1106-1146). d_hist: n_class*n_class uint64. */
+ * d_gt was given, hist[n_class*gt + pred] += 1 for 0 <= gt < n_class (PnP.py:1106-1146; the flat np.bincount index: a
+ * pred >= n_class counts in the next row, an index >= n_class^2 is dropped). d_hist: n_class*n_class uint64. */
 int pnp_remap_hist(pnp_engine* e, int32_t from_crf, uint8_t* d_labels, unsigned long long* d_hist, int32_t n_class,
                    void* stream);
 /* merge -> threshold/upsample -> [blur] -> [crf] -> argmax/remap/hist.  mode: bit0 blur, bit1 crf. */

@@ -1743,7 +1743,7 @@ extern "C" int pnp_get_buffer(pnp_engine* e, const char* name, void** d_ptr, siz
     if (n == "dctx_xattn") return set(e->dctxc, B * L * (size_t)e->H * e->esz);
     if (p.reserved) {
         const size_t mk = (size_t)p.max_total_pix * p.maxK * 4;
-        const size_t mq = (size_t)p.max_total_pix * p.maxKp * 4;
+        const size_t mq = (size_t)p.max_total_pix * p.maxKp * 4 * p.groups_cap;   // as allocated: a paired run fills two groups per row
         if (n == "merged") return set(p.merged, (size_t)p.maxB * p.maxK * e->PP * 4);
         if (n == "maps") return set(p.maps_in_2 ? p.maps2 : p.maps, mk);
         if (n == "maps_pre_blur") return set(p.maps, mk);

@@ -779,10 +779,12 @@ __global__ __launch_bounds__(256) void hist_kernel(const uint8_t* __restrict__ l
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         const float g = gt[label_off[b] + i];
         if (g >= 0.f && g < (float)n_class) {
-            const int gi = (int)g, pi = labels[label_off[b] + i];
-            if (pi < n_class) {
-                if (use_lds) atomicAdd(&mybins[gi * n_class + pi], 1u);
-                else atomicAdd(&hist[(size_t)gi * n_class + pi], 1ULL);
+            // the flat bin of np.bincount: a prediction >= n_class is counted in the next row, as the reference counts it; a
+            // bin past the matrix (where the reference's reshape raises) is dropped
+            const int bin = (int)g * n_class + labels[label_off[b] + i];
+            if (bin < nb) {
+                if (use_lds) atomicAdd(&mybins[bin], 1u);
+                else atomicAdd(&hist[bin], 1ULL);
             }
         }
     }
