@@ -266,6 +266,39 @@ int pnp_jpeg_decode(const uint8_t* d_data, const pnp_jpeg_image* d_images, const
                     int16_t* d_coef, int64_t coef_elems, uint8_t* d_planes, uint8_t* d_rgb, int32_t max_blocks_per_image,
                     int32_t max_pixels_per_image, int32_t* d_err, void* stream);
 
+/* ---- output side: what the reference's Draw_Segmentation_map writes (PnP_OVSS_0514_updated_segmentation_coco.py:966-983) ----
+ * Colour overlay of label maps on their images: skimage.color.label2rgb(kind="overlay", alpha, bg_label=0, image_alpha=1,
+ * saturation=0) followed by matplotlib's float -> uint8 conversion, in double precision and in this order:
+ *   g = (0.2125 R + 0.7154 G + 0.0721 B) / 255;  label 0: out_c = uint8(g * 255);
+ *   label l > 0: out_c = uint8((palette[l][c] / 255 * alpha + g * (1 - alpha)) * 255)       (truncation).
+ * d_labels: the concatenated uint8 label maps of B images (pnp_remap_hist / pnp_postprocess output), d_rgb / d_out: the
+ * concatenated HWC uint8 images (pnp_post_batch.d_rgb), d_pix_off: int64[B + 1] pixel offsets of the images (only the total
+ * d_pix_off[B] matters: the operation is per pixel), d_palette: uint8[256 * 3] indexed by label -- the colour of a class does
+ * not depend on which other classes an image holds (the reference colours by rank among the labels present).
+ * 0 <= alpha <= 1.  Stateless. */
+int pnp_overlay_labels(const uint8_t* d_labels, const uint8_t* d_rgb, const int64_t* d_pix_off, int32_t B,
+                       const uint8_t* d_palette, double alpha, uint8_t* d_out, void* stream);
+
+/* Baseline JPEG encode of a batch of HWC uint8 RGB images of any sizes: the entropy-coded scan (0xFF00-stuffed, last byte
+ * padded with 1-bits, no markers) that libjpeg writes with its defaults -- YCbCr 4:2:0, islow integer DCT, the T.81 Annex K
+ * Huffman tables, no restart markers -- so that markers + scan + EOI (pnp_ovss/jpeg.py) equal Pillow's
+ * Image.save(buf, "JPEG", quality=q) byte for byte.  h_images: HOST array of n_images descriptors; h_quant: HOST uint16[2][64],
+ * the luma and chroma quantisation tables in natural order, values 1..255.  Image i's scan goes to d_out + out_off and its
+ * length to d_out_len[i]; an image whose scan would exceed out_cap gets d_out_len[i] = -1, sets *d_err = 1 and has nothing
+ * written, the other images are unaffected (*d_err is 0 otherwise).  d_ws: workspace of at least *ws_need bytes, 256-byte
+ * aligned; a call with d_ws = NULL only computes *ws_need for these descriptors.  At most 2^31 / 1664 blocks of 8 x 8 per call
+ * (215 000 MCUs: 280 images of 500 x 375), PNP_ERR_ARG beyond.  Stateless; nothing is read back to the host. */
+typedef struct pnp_jpeg_enc_image {
+    int64_t rgb_off;            /* byte offset of the image in d_rgb (H*W*3, row-major HWC uint8) */
+    int64_t out_off;            /* byte offset of its scan in d_out */
+    int32_t H, W;               /* 1..65535 */
+    int32_t out_cap;            /* bytes reserved at out_off */
+    int32_t pad;
+} pnp_jpeg_enc_image;
+int pnp_jpeg_encode(const uint8_t* d_rgb, const pnp_jpeg_enc_image* h_images, int32_t n_images, const uint16_t* h_quant,
+                    uint8_t* d_out, int32_t* d_out_len, int32_t* d_err, void* d_ws, int64_t ws_bytes, int64_t* ws_need,
+                    void* stream);
+
 /* ---- introspection (tests / profiling) --------------------------------------------------- */
 /* Named internal device buffers: "image_embeds" (fp32 B*N*D), "text_hidden" (fp32 B*L*H: last_hidden_state of the most recent
  * text pass, multimodal or text-only), "maps" (fp32 post-process maps), "crf_q", "P", "dP", "crf_M" (int32 [2][B+1] lattice id

@@ -17,6 +17,10 @@ Multi-rank (the reference: DDP-constructor broadcast PnP.py:1218, 
   * `--gather_labels`: the final (N-drop) uint8 label maps of every rank are gathered on rank 0 over RCCL and written to
     `{save_path}/label_maps.npz` (image id -> H x W), north_star's mask-gather.
 
+`--in_the_wild` (the COCO driver's branch, PnPc.py:351-384): every {home_dir}/In_the_wild/{id}.jpeg|.jpg with the class names of
+`--wild_classes FILE.json` -> {save_path}/0519_Segmentation/BLIP_N_drop_{id}_{postprocess}.jpeg (colour overlay) + {id}.npy (label
+map); no ground truth, no histogram (pnp_ovss.wild).  `--save_vis` writes the same overlay for every image of a dataset run.
+
 Device work happens in libpnp_hip.so via pnp_ovss.model.Segmenter; this file is host orchestration.
 """
 import argparse
@@ -88,6 +92,13 @@ def get_args_parser():
     p.add_argument("--share_gpu", action="store_true",
                    help="diagnostic: every rank uses cuda:0 (rehearses world_size > 1 on a one-GPU box with --backend gloo; RCCL "
                         "refuses two ranks on one device)")
+    p.add_argument("--wild_classes", default=None,
+                   help='--in_the_wild: JSON file {"image id": ["class name", ...]} for the images {home_dir}/In_the_wild/{id}.jpeg|.jpg '
+                        "(the reference keeps these lists as literals in its source); an image without an entry is an error")
+    p.add_argument("--save_vis", action="store_true",
+                   help="write a colour overlay of every image's final label map, rendered and JPEG-encoded on the GPU, as "
+                        "{save_path}/0519_Segmentation/BLIP_N_drop_{id}_{postprocess}.jpeg (the reference's Draw_Segmentation_map; "
+                        "colours are stable per class id).  Rank-local files, no collective.  Costs one read-back per batch")
     p.add_argument("--synthetic_images", default=70, type=int)
     p.add_argument("--max_batches", default=0, type=int)
     return p
@@ -169,6 +180,14 @@ def main(rank, world_size, args):
         raise SystemExit("--prune_att_head is required (reference :277)")
     if args.del_patch_num is None or "sort_thresh" not in args.del_patch_num:
         raise SystemExit('--del_patch_num must contain "sort_thresh" (reference :645-647)')
+    if args.in_the_wild:
+        # the COCO driver's in-the-wild branch (PnPc.py:351-384, 594-595): the caller's images and class names, no ground truth,
+        # no histogram -- overlays and label maps only, every rank its own files
+        from pnp_ovss import wild
+        wild.run_cli(rank, world_size, args)
+        if world_size > 1:
+            dist.destroy_process_group()
+        return
     ds = make_dataset(args, rank, world_size)
     from lavis.models import load_model_and_preprocess
     stash_layer = args.max_att_block_num - 1
@@ -248,6 +267,14 @@ def main(rank, world_size, args):
             dst.copy_(src, non_blocking=True)                # ordered behind the launch on the current stream; read after synchronize()
             kept[str(i)] = dst
 
+    def save_vis(img_ids, maps, branch, prep):
+        """--save_vis: the overlays of a launch, rendered and encoded on the device (pnp_ovss.vis), one file per image."""
+        from pnp_ovss import vis, wild
+        os.makedirs(f"{args.save_path}/0519_Segmentation", exist_ok=True)
+        for i, f in zip(img_ids, vis.encode_overlays(maps, prep["rgb"], prep["sizes"])):
+            with open(wild.vis_file_name(args.save_path, branch, i, args.postprocess), "wb") as fh:
+                fh.write(f)
+
     if args.pipelines > 1:
         # P replicas (model + Segmenter + stream + host thread) consume the batch stream; each batch still runs the whole
         # path on one replica, into that replica's own pair of confusion matrices (bench.py --pipelines is the same scheme)
@@ -283,6 +310,8 @@ def main(rank, world_size, args):
                             l1, ln = sg.launch(pargs, batch["imgs"], prep, run_1drop=True, hists=ring[:2])
                             if args.gather_labels:
                                 keep_labels(batch["img_ids"], ln if ln is not None else l1)      # (dict stores of distinct keys: no lock)
+                            if args.save_vis:
+                                save_vis(batch["img_ids"], *((ln, "N_drop") if ln is not None else (l1, "1_drop")), prep)
                             ring[2].record()
                             last = finish((batch["img_ids"], layer, head, l1 is not None, ln is not None, ring))
                         with lock:
@@ -319,6 +348,8 @@ def main(rank, world_size, args):
             l1, ln = seg.launch(pargs, batch["imgs"], prep, run_1drop=True, hists=ring[:2])
             if args.gather_labels:
                 keep_labels(batch["img_ids"], ln if ln is not None else l1)
+            if args.save_vis:
+                save_vis(batch["img_ids"], *((ln, "N_drop") if ln is not None else (l1, "1_drop")), prep)
             ring[2].record()
             job = (batch["img_ids"], layer, head, l1 is not None, ln is not None, ring)
             if pending is not None:

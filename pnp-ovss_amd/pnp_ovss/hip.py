@@ -94,6 +94,8 @@ def load_library():
         "pnp_op_layernorm": (i32, [vp, vp, vp, f32, i32, i32, vp, vp]),
         "pnp_op_cast": (i32, [i32, vp, vp, i64, vp]),
         "pnp_jpeg_decode": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, vp, i64, vp, vp, i32, i32, vp, vp]),
+        "pnp_overlay_labels": (i32, [vp, vp, vp, i32, vp, C.c_double, vp, vp]),
+        "pnp_jpeg_encode": (i32, [vp, vp, i32, vp, vp, vp, vp, vp, i64, C.POINTER(i64), vp]),
         "pnp_op_split": (i32, [vp, vp, vp, i64, vp]),
         "pnp_op_gemm_x3": (i32, [vp, vp, i32, vp, vp, i32, i32, i32, i32, vp, i32, vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, vp]),
         "pnp_op_gemm_x3a": (i32, [vp, i32, vp, vp, i32, i32, i32, i32, vp, vp, i32, vp, i32, i32, vp, i32, vp]),
@@ -132,7 +134,7 @@ EXPORTED = ["pnp_create", "pnp_create_shared", "pnp_destroy", "pnp_last_error", 
             "pnp_streamk_status", "pnp_text_forward_text", "pnp_project_normalize", "pnp_itc_similarity",
             "pnp_op_text_self_attn", "pnp_op_text_self_attn_bwd", "pnp_op_layernorm_ex", "pnp_op_layernorm_bwd",
             "pnp_op_text_embed", "pnp_op_itm_head", "pnp_op_itm_grad_seed", "pnp_op_patchify", "pnp_op_cls_rows",
-            "pnp_op_gemm_args"]
+            "pnp_op_gemm_args", "pnp_overlay_labels", "pnp_jpeg_encode"]
 
 
 PROJ_NAMES = ("vision_proj.weight", "vision_proj.bias", "text_proj.weight", "text_proj.bias")      # the optional ITC projections
@@ -282,6 +284,137 @@ def jpeg_decode_batch(files, device=None):
     for h, w in sizes:
         out.append(d_rgb[o:o + h * w * 3].view(h, w, 3))
         o += h * w * 3
+    return out
+
+
+class PnpJpegEncImage(C.Structure):
+    _fields_ = [("rgb_off", C.c_int64), ("out_off", C.c_int64), ("H", C.c_int32), ("W", C.c_int32), ("out_cap", C.c_int32),
+                ("pad", C.c_int32)]
+
+
+JPEG_ENC_MAX_MCUS = 200_000        # per pnp_jpeg_encode call (its bit offsets are int32: include/pnp_hip.h); larger batches are split
+
+
+def _concat_rgb(images, dev):
+    """(H, W, 3) uint8 device tensors / numpy arrays -> (one flat uint8 device tensor, [(H, W)])."""
+    sizes = []
+    for im in images:
+        if im.ndim != 3 or int(im.shape[2]) != 3 or not (im.dtype == torch.uint8 or im.dtype == np.uint8):
+            raise ValueError(f"images are (H, W, 3) uint8, not {tuple(im.shape)} {im.dtype}")
+        sizes.append((int(im.shape[0]), int(im.shape[1])))
+    if all(isinstance(im, torch.Tensor) and im.is_cuda for im in images):
+        rgb = torch.cat([im.reshape(-1) for im in images]) if len(images) > 1 else images[0].contiguous().reshape(-1)
+    else:
+        rgb = torch.from_numpy(np.concatenate([np.ascontiguousarray(im.cpu().numpy() if isinstance(im, torch.Tensor) else im,
+                                                                    dtype=np.uint8).reshape(-1) for im in images])).to(dev)
+    return rgb, sizes
+
+
+def jpeg_encode_scans(images, quality=75, capacities=None, out=None, device=None):
+    """pnp_jpeg_encode for one batch: the entropy-coded scans of `images` ((H, W, 3) uint8 device tensors or numpy arrays) at
+    libjpeg quality 1..95.  capacities: bytes reserved per image (default jpeg.scan_capacity); out: a uint8 device tensor to
+    write into (default: a new one), image i's scan starts at offsets[i] = sum of the capacities before it.
+    Returns (out, offsets, lengths, err): lengths[i] = -1 and err = 1 when image i did not fit its capacity -- nothing of it
+    is written then, the other images are."""
+    if not torch.cuda.is_available():
+        raise RuntimeError("pnp_ovss.hip.jpeg_encode_scans needs a HIP device (no CPU fallback)")
+    from . import jpeg as J
+    lib = load_library()
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    B = len(images)
+    quant = np.ascontiguousarray(J.quality_tables(quality))
+    rgb, sizes = _concat_rgb(images, dev)
+    caps = [J.scan_capacity(h, w) for h, w in sizes] if capacities is None else [int(c) for c in capacities]
+    if len(caps) != B:
+        raise ValueError("one capacity per image")
+    desc = (PnpJpegEncImage * B)()
+    offsets, ro, oo = [], 0, 0
+    for i, ((h, w), c) in enumerate(zip(sizes, caps)):
+        desc[i] = PnpJpegEncImage(ro, oo, h, w, c, 0)
+        offsets.append(oo)
+        ro += h * w * 3
+        oo += c
+    if out is None:
+        out = torch.empty(oo, dtype=torch.uint8, device=dev)
+    elif not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() >= oo):
+        raise ValueError(f"out: a contiguous uint8 device tensor of at least {oo} bytes")
+    need = C.c_int64()
+    r = lib.pnp_jpeg_encode(None, desc, B, quant.ctypes.data, None, None, None, None, 0, C.byref(need), None)
+    if r != 0:
+        raise RuntimeError(f"pnp_jpeg_encode refused the batch ({r}): image sizes 1..65535, at most {JPEG_ENC_MAX_MCUS} MCUs per call")
+    ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+    d_len = torch.empty(B, dtype=torch.int32, device=dev)
+    d_err = torch.empty(1, dtype=torch.int32, device=dev)
+    r = lib.pnp_jpeg_encode(rgb.data_ptr(), desc, B, quant.ctypes.data, out.data_ptr(), d_len.data_ptr(), d_err.data_ptr(),
+                            ws.data_ptr(), need.value, None, torch.cuda.current_stream().cuda_stream)
+    if r != 0:
+        raise RuntimeError(f"pnp_jpeg_encode failed ({r})")
+    lens = [int(v) for v in d_len.cpu()]           # (synchronises: the workspace and the inputs may go after this)
+    return out, offsets, lens, int(d_err.item())
+
+
+def jpeg_encode_batch(images, quality=75, device=None):
+    """`Image.fromarray(rgb).save(buf, "JPEG", quality=quality)` for a batch of (H, W, 3) uint8 images (device tensors or numpy
+    arrays, any sizes), encoded on the device: returns the files as a list of bytes, equal to Pillow's byte for byte (4:2:0,
+    islow DCT, standard Huffman tables).  The device writes the entropy-coded scans (pnp_jpeg_encode), the host the markers
+    around them (pnp_ovss.jpeg.encode_headers); only the finished scans cross to the host, in one copy."""
+    from . import jpeg as J
+    images = list(images)
+    if not images:
+        return []
+    quant = J.quality_tables(quality)
+    files = [None] * len(images)
+    groups, cur, n = [], [], 0
+    for i, im in enumerate(images):                # split at the per-call MCU limit
+        m = -(-int(im.shape[0]) // 16) * -(-int(im.shape[1]) // 16)
+        if cur and n + m > JPEG_ENC_MAX_MCUS:
+            groups.append(cur)
+            cur, n = [], 0
+        cur.append(i)
+        n += m
+    groups.append(cur)
+    for grp in groups:
+        todo, worst = grp, False
+        while todo:
+            ims = [images[i] for i in todo]
+            caps = [J.scan_capacity(int(im.shape[0]), int(im.shape[1]), worst) for im in ims]
+            out, offs, lens, err = jpeg_encode_scans(ims, quality, caps, device=device)
+            good = [k for k, n_ in enumerate(lens) if n_ >= 0]
+            if good:
+                flat = torch.cat([out[offs[k]:offs[k] + lens[k]] for k in good]).cpu().numpy().tobytes()
+                o = 0
+                for k in good:
+                    im = ims[k]
+                    files[todo[k]] = J.encode_headers(int(im.shape[0]), int(im.shape[1]), quant) + flat[o:o + lens[k]] + b"\xff\xd9"
+                    o += lens[k]
+            todo = [todo[k] for k, n_ in enumerate(lens) if n_ < 0]
+            if todo and worst:
+                raise RuntimeError("pnp_jpeg_encode: a scan exceeded its worst-case bound")
+            worst = True                           # (rare: noise-like content at a high quality) once more with the bound no input exceeds
+    return files
+
+
+def overlay_labels(labels, rgb, pix_off, palette, alpha=0.3):
+    """pnp_overlay_labels: labels -- the concatenated uint8 label maps of a batch (Engine.postprocess output), rgb -- the
+    concatenated HWC uint8 images (Segmenter.prepare's "rgb"), both device tensors; pix_off -- int64 [B + 1] pixel offsets
+    (device tensor or a sequence); palette -- uint8 [256, 3] indexed by label.  Returns the overlays, concatenated like rgb."""
+    if not torch.cuda.is_available():
+        raise RuntimeError("pnp_ovss.hip.overlay_labels needs a HIP device (no CPU fallback)")
+    lib = load_library()
+    dev = labels.device
+    total = int(pix_off[-1])                       # (a device tensor is read back here: the kernel trusts this total)
+    if total != labels.numel() or int(pix_off[0]) != 0:
+        raise ValueError(f"pix_off runs from {int(pix_off[0])} to {total}, the batch has {labels.numel()} pixels")
+    if not isinstance(pix_off, torch.Tensor):
+        pix_off = torch.as_tensor(np.asarray(pix_off, dtype=np.int64)).to(dev)
+    if not isinstance(palette, torch.Tensor):
+        palette = torch.as_tensor(np.ascontiguousarray(palette, dtype=np.uint8)).to(dev)
+    assert labels.dtype == torch.uint8 and rgb.dtype == torch.uint8 and pix_off.dtype == torch.int64 and palette.dtype == torch.uint8
+    assert palette.numel() == 768 and rgb.numel() == 3 * labels.numel(), "palette is [256, 3]; rgb has three bytes per label"
+    out = torch.empty_like(rgb)
+    r = lib.pnp_overlay_labels(_ptr(labels), _ptr(rgb), _ptr(pix_off), pix_off.numel() - 1, _ptr(palette), float(alpha), _ptr(out), _stream())
+    if r != 0:
+        raise RuntimeError(f"pnp_overlay_labels failed ({r})")
     return out
 
 

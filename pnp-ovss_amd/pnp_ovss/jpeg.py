@@ -5,6 +5,9 @@ entropy-coded bytes plus descriptors to the GPU, which does the Huffman decode, 
 conversion for the whole batch.  Baseline sequential files (grayscale / YCbCr 4:4:4, 4:2:2, 4:2:0) are supported --
 what VOC / COCO / ADE20K ship; anything else (progressive, arithmetic, CMYK) raises `UnsupportedJpeg` and the dataset
 decodes that one file with Pillow.
+
+Below it, the host half of the device ENCODER (csrc/jpeg_enc.hip, `pnp_jpeg_encode`): libjpeg's quality-scaled quantisation
+tables and the markers around the entropy-coded scan the GPU writes, byte for byte those of Pillow's `save(..., "JPEG")`.
 """
 import ctypes as C
 
@@ -234,3 +237,62 @@ def pack_batch(files):
     data = np.concatenate(chunks) if chunks else np.zeros(16, dtype=np.uint8)
     return data, imgs, tabs, sg, sizes, dict(coef_elems=coef, plane_bytes=plane, rgb_bytes=rgb, clean_bytes=clean, max_blocks=max_blocks,
                                              max_pixels=max_pixels)
+
+
+# ---------------------------------------------------------------------------------------------------------- encoder, host half
+# The device (csrc/jpeg_enc.hip, `pnp_jpeg_encode`) produces the entropy-coded scan; the markers around it are written here,
+# byte for byte what libjpeg writes for Pillow's `Image.save(buf, "JPEG", quality=q)`: SOI, APP0 (JFIF 1.01, aspect 1:1),
+# two DQT segments, SOF0 (Y 2x2, Cb / Cr 1x1), four DHT segments (T.81 Annex K.3: DC0, AC0, DC1, AC1), SOS -- scan -- EOI.
+STD_LUMA_QUANT = np.array([16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22,
+                           29, 51, 87, 80, 62, 18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87,
+                           103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99], dtype=np.int64)
+STD_CHROMA_QUANT = np.array([17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99,
+                             47, 66, 99, 99, 99, 99, 99, 99] + [99] * 32, dtype=np.int64)
+STD_DHT = (
+    (0x00, bytes([0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0]), bytes(range(12))),
+    (0x10, bytes([0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d]), bytes.fromhex(
+        "01020300041105122131410613516107227114328191a1082342b1c11552d1f02433627282090a161718191a25262728292a3435363738393a"
+        "434445464748494a535455565758595a636465666768696a737475767778797a838485868788898a92939495969798999aa2a3a4a5a6a7a8a9aa"
+        "b2b3b4b5b6b7b8b9bac2c3c4c5c6c7c8c9cad2d3d4d5d6d7d8d9dae1e2e3e4e5e6e7e8e9eaf1f2f3f4f5f6f7f8f9fa")),
+    (0x01, bytes([0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0]), bytes(range(12))),
+    (0x11, bytes([0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77]), bytes.fromhex(
+        "000102031104052131061241510761711322328108144291a1b1c109233352f0156272d10a162434e125f11718191a262728292a35363738393a"
+        "434445464748494a535455565758595a636465666768696a737475767778797a82838485868788898a92939495969798999aa2a3a4a5a6a7a8a9aa"
+        "b2b3b4b5b6b7b8b9bac2c3c4c5c6c7c8c9cad2d3d4d5d6d7d8d9dae2e3e4e5e6e7e8e9eaf2f3f4f5f6f7f8f9fa")),
+)
+
+
+def quality_tables(quality=75):
+    """libjpeg's jpeg_set_quality (force_baseline): uint16 [2, 64], luma and chroma, natural order."""
+    q = int(quality)
+    if not 1 <= q <= 95:
+        raise ValueError(f"quality {quality!r}: 1..95 (Pillow's range for the standard tables)")
+    s = 5000 // q if q < 50 else 200 - 2 * q
+    return np.stack([np.clip((b * s + 50) // 100, 1, 255) for b in (STD_LUMA_QUANT, STD_CHROMA_QUANT)]).astype(np.uint16)
+
+
+def _segment(marker, payload):
+    return bytes((0xFF, marker)) + (len(payload) + 2).to_bytes(2, "big") + payload
+
+
+def encode_headers(H, W, quant):
+    """Everything in front of the entropy-coded scan, for an H x W image and the tables of quality_tables()."""
+    if not (1 <= H <= 65535 and 1 <= W <= 65535):
+        raise ValueError(f"JPEG frames are 1..65535 pixels a side, not {H} x {W}")
+    out = [b"\xff\xd8", _segment(0xE0, b"JFIF\x00\x01\x01\x00\x00\x01\x00\x01\x00\x00")]
+    for t in (0, 1):
+        out.append(_segment(0xDB, bytes((t,)) + bytes(int(v) for v in np.asarray(quant[t])[ZIGZAG])))
+    out.append(_segment(0xC0, bytes((8,)) + int(H).to_bytes(2, "big") + int(W).to_bytes(2, "big") +
+                        bytes((3, 1, 0x22, 0, 2, 0x11, 1, 3, 0x11, 1))))
+    for tc_th, counts, symbols in STD_DHT:
+        out.append(_segment(0xC4, bytes((tc_th,)) + counts + symbols))
+    out.append(_segment(0xDA, bytes((3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0))))
+    return b"".join(out)
+
+
+def scan_capacity(H, W, worst=False):
+    """Bytes to reserve for an image's scan.  Default: 1.5 bytes per pixel of the MCU grid (the size of the raw 4:2:0 samples;
+    photographs and overlays need a fraction of it).  worst=True: the bound no input exceeds -- every block at its longest
+    codes (20 + 63 * 26 bits) and every byte stuffed."""
+    mcus = -(-H // 16) * -(-W // 16)
+    return mcus * 6 * 416 + 16 if worst else mcus * 384 + 64

@@ -1,6 +1,11 @@
 """Throughput of the device JPEG decoder against Pillow on the same synthetic files (GPU box only).
 
     python tools/jpeg_bench.py [--images 35] [--size 375x500] [--quality 90] [--reps 5] [--out gpurun_out/jpeg_bench.json]
+    python tools/jpeg_bench.py --encode [--images 35] [--size 375x500] [--enc_quality 75] [--out profiles/jpeg_encode.json]
+
+--encode: the other direction -- the same images, already on the device, through hip.jpeg_encode_batch (pnp_jpeg_encode: warm,
+HIP events around the device work; the wall time of the whole call with its read-back and marker writing beside it) against
+`Image.fromarray(rgb).save(buf, "JPEG", quality=q)` on one host thread.
 
 Images are smooth colour fields plus texture noise (compressed size close to a VOC / COCO photograph of that size),
 written with Pillow at 4:2:0.  Prints one JSON line: host marker walk (pack_batch), device time per batch by kernel
@@ -30,6 +35,53 @@ def synth_photo(rng, H, W):
     return np.clip(img, 0, 255).astype(np.uint8)
 
 
+def encode_leg(a, H, W, rng):
+    from PIL import Image
+    import torch
+    from pnp_ovss import hip, jpeg as J
+    imgs = [synth_photo(rng, H, W) for _ in range(a.images)]
+
+    def pil_one(im):
+        b = io.BytesIO()
+        Image.fromarray(im).save(b, "JPEG", quality=a.enc_quality)
+        return b.getvalue()
+    ref = [pil_one(im) for im in imgs]
+    t0 = time.perf_counter()
+    for _ in range(a.reps):
+        for im in imgs:
+            pil_one(im)
+    t_pil1 = (time.perf_counter() - t0) / a.reps
+    dev = [torch.from_numpy(im).cuda() for im in imgs]
+    got = hip.jpeg_encode_batch(dev, a.enc_quality)                        # warm-up + the check
+    exact = got == ref
+    caps = [J.scan_capacity(H, W)] * a.images
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    hip.jpeg_encode_scans(dev, a.enc_quality, caps)
+    ev_ms = []
+    for _ in range(a.reps):                                                # device work only: events around the launch sequence
+        torch.cuda.synchronize()
+        e0.record()
+        hip.jpeg_encode_scans(dev, a.enc_quality, caps)
+        e1.record()
+        torch.cuda.synchronize()
+        ev_ms.append(e0.elapsed_time(e1))
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(a.reps):
+        hip.jpeg_encode_batch(dev, a.enc_quality)
+    t_total = (time.perf_counter() - t0) / a.reps
+    rec = dict(images=a.images, size=[H, W], quality=a.enc_quality, jpeg_bytes=sum(len(f) for f in ref), byte_exact_vs_pillow=bool(exact),
+               pillow_1thread_ms=t_pil1 * 1e3, device_events_ms=float(np.median(ev_ms)), device_call_wall_ms=t_total * 1e3,
+               note="device_events_ms spans concatenation, workspace allocation, the kernels and the length read-back of "
+                    "jpeg_encode_scans; device_call_wall_ms is jpeg_encode_batch end to end (bytes objects on the host)",
+               images_per_s=dict(pillow_1thread=a.images / t_pil1, device=a.images / t_total))
+    line = json.dumps(rec)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
 def main():
     from PIL import Image
     import torch
@@ -41,9 +93,13 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--restart", type=int, default=0, help="restart interval in MCU rows (0 = none, what the datasets ship)")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--encode", action="store_true", help="measure the device encoder against Pillow's instead of the decoder")
+    ap.add_argument("--enc_quality", type=int, default=75)
     a = ap.parse_args()
     H, W = map(int, a.size.split("x"))
     rng = np.random.default_rng(0)
+    if a.encode:
+        return encode_leg(a, H, W, rng)
     files = []
     for _ in range(a.images):
         b = io.BytesIO()
