@@ -333,7 +333,14 @@ int pnp_profile_read_stage(pnp_engine* e, int32_t stage, int64_t* launches, doub
  *              229-283 self-attention forward and its backward): 0 (default) = chosen per launch from B * heads, L and the CU
  *              count, 1..4 = that many wherever the choice is made.  The split decides which workgroup computes a row, not one
  *              operation of its arithmetic: results are bit-identical for every value.  In the fp32 backward 1 selects the
- *              one-launch form and 2..4 the two-launch form (query-row phase, then key-row phase). */
+ *              one-launch form and 2..4 the two-launch form (query-row phase, then key-row phase).
+ *   "gemm_stamps": 0 (default) | 1 = every launch of the generic, wide-tile and split-bf16 wide GEMM kernels records
+ *              per-workgroup clock stamps for pnp_dbg_gemm_stamps.  There is one library build and it reads no environment
+ *              variable: this switch is the only way to turn the stamps on, and they time the kernels every caller runs.
+ *              The stamp buffer (8192 rows, 512 KB of device memory) is allocated by the first enable, on the device current at
+ *              that moment, and kept; PNP_ERR_HIP if that allocation fails.  Launches on any other device, and launches of
+ *              more than 8192 workgroups (the generic kernels run one per tile), record nothing and leave the buffer alone.
+ *              Results are bit-identical with stamps on and off. */
 int pnp_set_tuning(const char* key, int32_t value);
 /* Launches that used the engine's (e = NULL: the op-level entry points') stream-K workspace, and the give-up word of its
  * bounded spins (0 = no owner ever gave up waiting for a partial tile; anything else is a bug report).  Synchronises. */
@@ -410,11 +417,14 @@ int pnp_op_layernorm(const float* d_x, const float* d_w, const float* d_b, float
 int pnp_op_xattn(int32_t bf16, int32_t mode, const void* d_nat, int32_t ld_nat, const void* d_tr, int32_t ld_tr,
                  int32_t n_pad, const void* d_x, int32_t ldx, void* d_out, int32_t ldo, float* d_probs, int32_t n_stride,
                  int32_t B, int32_t L, int32_t N, int32_t heads, void* stream);
-/* Diagnostics, development builds only (`make DEV=1`, libpnp_hip_dev.so: the product library reads no environment
- * variable and records no stamps -- there this returns PNP_ERR_STATE).  A DEV build started with PNP_GEMM_STAMPS=1
- * records, per workgroup of the wide-tile GEMM, the shader clock (slots 0-3) and the 100 MHz wall clock (slots 4-7) at
- * kernel start, after the first slab landed, after the main loop and after the epilogue; this copies the last launch's
- * stamps to the host. */
+/* Diagnostics.  While pnp_set_tuning("gemm_stamps", 1) holds, every workgroup of a generic, wide-tile or split-bf16 wide
+ * GEMM launch writes one row of 8 words: the shader clock (slots 0-3) and the 100 MHz wall clock (slots 4-7) at kernel
+ * start (0), at two points in between that depend on the kernel (1, 2: see the stamp() calls in csrc/gemm.hip and
+ * csrc/gemm_x3.hip) and after the workgroup's last store has drained (3).  Every launch writes into the same buffer, so
+ * the rows describe the LAST stamped launch (rows past its grid keep what earlier launches left), and they are meaningful
+ * only with one stream launching GEMMs at a time.  A launch of more than 8192 workgroups, or on another device than the
+ * buffer's, writes no row.  This synchronises the device and copies the first max_blocks rows (at
+ * most 8192) to host_out.  PNP_ERR_STATE until stamps have been enabled once in this process. */
 int pnp_dbg_gemm_stamps(uint64_t* host_out, int32_t max_blocks);
 int pnp_op_cast(int32_t to_bf16, const float* d_in, void* d_out, int64_t n, void* stream);
 /* The device-wide primitives of the DenseCRF lattice build as operators (the reference reaches them through pydensecrf's

@@ -16,8 +16,6 @@
 // gathers of the current one, results stored one item later.
 #include <mutex>
 
-#include <stdlib.h>
-
 #include "common.h"
 #include "kernels.h"
 #include "../../include/pnp_math.h"
@@ -27,18 +25,13 @@ namespace pnp {
 // Streaming accesses of the mean-field kernels (data with no reuse inside a launch: contributor records, the value rows a splat
 // writes, the unary rows an update reads and the Q rows it writes) are marked non-temporal, so that they do not displace the
 // rows that ARE reused (a pixel's Q row is gathered by its 3 + 6 lattice points) from L2.  Round 5, same-box A/B
-// (tools/crf_nt_ab.sh, two alternations): mean-field per step 30.9 / 30.6 -> 30.3 / 30.6 ms on the headline batch (neutral),
+// (plain against non-temporal accesses, two alternations): mean-field per step 30.9 / 30.6 -> 30.3 / 30.6 ms on the headline batch (neutral),
 // 74.1 / 75.0 -> 72.5 / 72.9 ms at K = 59, 72.3 / 72.3 -> 67.3 / 71.1 ms at 3.6 lattice points per pixel, 252 / 257 -> 253 / 253 ms
 // at ADE20K size: small, never negative; the stores of the two-axis lattice blur on top of that: 30.6 / 30.8 -> 30.3 / 29.6 ms
 // (headline), 74.8 / 74.2 -> 73.1 / 73.1 (K = 59), 71.6 / 71.5 -> 69.7 / 66.6 (3.6 points per pixel).  Loads / stores are otherwise
 // identical: results unchanged.
-#ifdef PNP_CRF_NO_NT            // A/B opt-out (tools/crf_nt_ab.sh builds its `base` variant with it): plain accesses
-template <typename T> __device__ __forceinline__ T ld_stream(const T* p) { return *p; }
-template <typename T> __device__ __forceinline__ void st_stream(T* p, const T& v) { *p = v; }
-#else
 template <typename T> __device__ __forceinline__ T ld_stream(const T* p) { return __builtin_nontemporal_load(p); }
 template <typename T> __device__ __forceinline__ void st_stream(T* p, const T& v) { __builtin_nontemporal_store(v, p); }
-#endif
 __device__ __forceinline__ CrfEntry ld_entry(const CrfEntry* p) {
     return __builtin_bit_cast(CrfEntry, ld_stream(reinterpret_cast<const chunk16*>(p)));
 }
@@ -1190,11 +1183,7 @@ int crf_update(const CrfLattice& Lg, const CrfLattice& Lb, const PostDesc* d_img
     // below 32 pixels the per-tile overheads win: 295 ms at 16, 389 ms at 8)
     while (tp > 16 && tp * per_pixel > 48 * 1024) tp >>= 1;
     if (tp * per_pixel > 158 * 1024) tp = 158 * 1024 / per_pixel;
-    int tile_w = 0;                                          // 0: crf_tile_w(pixels per tile)
-#ifdef PNP_DEV
-    if (getenv("PNP_CRF_TP") && (size_t)atoi(getenv("PNP_CRF_TP")) < tp) tp = (size_t)atoi(getenv("PNP_CRF_TP"));
-    if (getenv("PNP_CRF_TW")) tile_w = atoi(getenv("PNP_CRF_TW"));   // a power of two <= tp (tp: the whole strip, as before)
-#endif
+    const int tile_w = 0;                                    // 0: crf_tile_w(pixels per tile)
     if (tp < 4) return PNP_ERR_ARG;
     const size_t smem = tp * per_pixel;
     const bool wide = max_kp / (groups > 0 ? groups : 1) >= CRF_WAVE_SOFTMAX_K;      // some image of the batch may have such rows

@@ -1874,6 +1874,10 @@ extern "C" int pnp_set_tuning(const char* key, int32_t value) {
         set_text_rows(value);
         return PNP_OK;
     }
+    if (!strcmp(key, "gemm_stamps")) {
+        if (value < 0 || value > 1) return PNP_ERR_ARG;
+        return gemm_set_stamps(value);
+    }
     return PNP_ERR_ARG;
 }
 

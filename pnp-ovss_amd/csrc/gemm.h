@@ -55,8 +55,9 @@ struct GemmArgs {
     unsigned* sk_flag = nullptr;            // tiles of the whole rounds, slab pairs per workgroup in the tail
     unsigned* sk_tmo = nullptr;
     int sk_full = 0, sk_upw = 0;
-    unsigned long long* stamps = nullptr;   // diagnostics (DEV builds, PNP_GEMM_STAMPS): per-workgroup clock stamps, 8 per block
-    int ablate = 0;                // DEV builds only (PNP_GEMM_ABLATE): 1 = no steady-state DMA, 2 = no MFMA
+    unsigned long long* stamps = nullptr;   // diagnostics, set by gemm_nt while gemm_set_stamps(1) holds: per-workgroup clock stamps, 8 per block
+    int reserved = 0;              // unused: keeps sizeof(GemmArgs) and with it the offsets of the hidden kernel arguments (grid size),
+                                   // which sit behind the struct in the kernarg segment
 };
 
 int gemm_nt(int dtype_bf16, GemmArgs g, hipStream_t s);
@@ -73,6 +74,7 @@ struct GemmProfile {
     long long launches = 0;
     double flops = 0;
 };
+int gemm_set_stamps(int on);                               // pnp_set_tuning("gemm_stamps"): process-wide, off by default
 int gemm_read_stamps(unsigned long long* host_out, int max_blocks);
 
 }  // namespace pnp

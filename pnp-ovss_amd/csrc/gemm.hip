@@ -11,8 +11,7 @@
 // reads (16 consecutive rows, same logical chunk) are conflict-free ds_read_b128.
 // Operands are swapped at the MFMA (D = Btile * Atile^T) so each lane owns 4 CONSECUTIVE output
 // columns of one row: the epilogue does one 8/16-byte store per fragment and vector bias loads.
-#include <stdlib.h>
-
+#include <mutex>
 #include <type_traits>
 
 #include "common.h"
@@ -159,9 +158,6 @@ __global__ __launch_bounds__((BM / WTM) * (BN / WTN) * 64) void gemm_nt_big_kern
         }
     }
     auto issue = [&](int kt) {
-#ifdef PNP_DEV
-        if (g.ablate == 1 && kt >= NS) return;           // timing ablation: no steady-state DMA
-#endif
         char* stage = smem + (kt % NS) * STAGE;
         const uint32_t koff = (uint32_t)kt * ROWB;
 #pragma unroll
@@ -232,16 +228,8 @@ __global__ __launch_bounds__((BM / WTM) * (BN / WTN) * 64) void gemm_nt_big_kern
             const char* cB = cA + BM * ROWB;
 #pragma unroll
             for (int j = 0; j < TM; j++) {
-#ifdef PNP_DEV
-                if (g.ablate == 2) {                         // timing ablation: no MFMA, operands kept alive
 #pragma unroll
-                    for (int i = 0; i < TN; i++) asm volatile("" ::"v"(fb_cur[i].v), "v"(fa_cur[j].v));
-                } else
-#endif
-                {
-#pragma unroll
-                    for (int i = 0; i < TN; i++) mma16(acc[i][j], fb_cur[i], fa_cur[j]);
-                }
+                for (int i = 0; i < TN; i++) mma16(acc[i][j], fb_cur[i], fa_cur[j]);
                 if (have_next) {
                     lds_frag<ROWB>(fa_cur[j], cA, wm * WTM + j * 16 + r, ks_n, q);
                     if (j < TN) lds_frag<ROWB>(fb_nxt[j], cB, wn * WTN + j * 16 + r, ks_n, q);
@@ -321,9 +309,14 @@ __global__ __launch_bounds__((BM / WTM) * (BN / WTN) * 64) void gemm_nt_big_kern
     }
 }
 
+// rows of the clock-stamp buffer (gemm_set_stamps): one per workgroup.  The persistent kernels launch at most one workgroup per CU
+// (and the stream-K rows sit at grid + block id); the generic kernel launches one per tile, with no bound
+static constexpr int kStampBlocks = 8192;
+
 template <typename T, int BM, int BN, int WTM, int WTN, int NS, bool PIPE = true>
-static int launch_big(const GemmArgs& g, hipStream_t s) {
+static int launch_big(GemmArgs g, hipStream_t s) {
     const int nbm = (g.M + BM - 1) / BM, nbn = g.N / BN;
+    if ((long)nbm * nbn > kStampBlocks) g.stamps = nullptr;            // more workgroups than stamp rows: this launch records none
     const size_t smem = (size_t)NS * (BM + BN) * 128;
     static std::atomic<uint32_t> opted{0};            // per device ordinal (common.h: lds_opt_in)
     if (lds_opt_in(opted, reinterpret_cast<const void*>(gemm_nt_big_kernel<T, BM, BN, WTM, WTN, NS, PIPE>), (int)smem) != PNP_OK) return PNP_ERR_HIP;
@@ -409,9 +402,6 @@ __global__ __launch_bounds__(512) void gemm_nt_wide_kernel(const GemmArgs g) {
         }
     };
     auto issue_one = [&](int kt, int i) {
-#ifdef PNP_DEV
-        if (g.ablate == 1 && kt >= 2) return;           // timing ablation: no steady-state DMA
-#endif
         char* stage = smem + (kt & 1) * STAGE;
         {
             const uint32_t koff = (uint32_t)kt * ROWB;
@@ -770,11 +760,7 @@ static int launch_wide(const GemmArgs& g, hipStream_t s) {
     static std::atomic<uint32_t> opted{0};            // per device ordinal (common.h: lds_opt_in)
     if (lds_opt_in(opted, reinterpret_cast<const void*>(gemm_nt_wide_kernel<EPI>), kWideSmem) != PNP_OK) return PNP_ERR_HIP;
     const int ntiles = nbm * nbn;
-    int cap = n_cu;
-#ifdef PNP_DEV
-    if (getenv("PNP_GEMM_GRID")) cap = atoi(getenv("PNP_GEMM_GRID"));
-#endif
-    const int grid = ntiles > cap ? cap : ntiles;        // one workgroup per CU (LDS-limited) walks the tiles
+    const int grid = ntiles > n_cu ? n_cu : ntiles;      // one workgroup per CU (LDS-limited) walks the tiles
     hipLaunchKernelGGL((gemm_nt_wide_kernel<EPI>), dim3(grid), dim3(512), kWideSmem, s, g);
     return hipGetLastError() == hipSuccess ? PNP_OK : PNP_ERR_HIP;
 }
@@ -988,168 +974,36 @@ static int launch_small_x3_t(const GemmArgs& g, hipStream_t s) {
 }
 
 static int launch_small_x3(const GemmArgs& g, hipStream_t s) {
-    int nw = 8, ks = g.K % 64 == 0 ? 2 : 1;
     // many more workgroups than CUs (the N = 3072 launches at M = 875: 672): three co-resident workgroups per CU on 48 KB rings
     // (3 slots of 32-deep slabs) run the launch as ONE round instead of three rounds of one 128 KB workgroup per CU: 28.9 -> 25.2 us.
     // Not more than that, and nothing at 504 workgroups (21.2 against 21.4 us) or on the deep-K shapes (58 against 29 us): these
     // launches run at what a CU ingests from L2 (~20-27 B/clk, tools/micro/lds_dma_rate.hip), whoever is resident on it.
-    int variant = (long)((g.M + 63) / 64) * (g.N / 64) > 600 && g.K <= 1024 ? 1 : 0;
-#ifdef PNP_DEV
-    if (getenv("PNP_SMALL_NW")) nw = atoi(getenv("PNP_SMALL_NW"));
-    if (getenv("PNP_SMALL_KS") && atoi(getenv("PNP_SMALL_KS")) == 1) ks = 1;
-    if (getenv("PNP_SMALL_VARIANT")) variant = atoi(getenv("PNP_SMALL_VARIANT"));
-#endif
-    if (variant == 1) return launch_small_x3_t<8, 1, 3>(g, s);
-    if (variant == 2) return launch_small_x3_t<8, 2, 3>(g, s);          // 96 KB: one per CU, for comparison
-    if (ks == 2) return nw == 4 ? launch_small_x3_t<4, 2>(g, s) : launch_small_x3_t<8, 2>(g, s);
-    return nw == 4 ? launch_small_x3_t<4, 1>(g, s) : launch_small_x3_t<8, 1>(g, s);
+    if ((long)((g.M + 63) / 64) * (g.N / 64) > 600 && g.K <= 1024) return launch_small_x3_t<8, 1, 3>(g, s);
+    return g.K % 64 == 0 ? launch_small_x3_t<8, 2>(g, s) : launch_small_x3_t<8, 1>(g, s);
 }
 
-template <typename T, int BM, int BN>
-__global__ __launch_bounds__(256) void gemm_nt_kernel(const GemmArgs g) {
-    constexpr int ROWB = 128;                       // bytes of k per LDS row per stage
-    constexpr int BK = ROWB / Elem<T>::kBytes;      // 64 bf16 / 32 f32
-    constexpr int WTM = BM / 2, WTN = BN / 2;       // wave tile
-    constexpr int TM = WTM / 16, TN = WTN / 16;     // 16x16 tiles per wave
-    constexpr int A_CHUNKS = BM * 8 / 256;          // 16-byte chunks per thread per stage
-    constexpr int B_CHUNKS = BN * 8 / 256;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int STAGE = (BM + BN) * ROWB;
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63, wave = tid >> 6;
-    const int r = lane & 15, q = lane >> 4;
-    const int wm = wave >> 1, wn = wave & 1;
-
-    const int nbm = (g.M + BM - 1) / BM, nbn = g.N / BN;
-    int bm, bn;
-    tile_coords<8>(blockIdx.x, nbm, nbn, bm, bn);
-    const int m0 = bm * BM, n0 = bn * BN;
-
-    const char* Ab = reinterpret_cast<const char*>(g.A);
-    const char* Bb = reinterpret_cast<const char*>(g.B);
-    const size_t lda_b = (size_t)g.lda * Elem<T>::kBytes, ldb_b = (size_t)g.ldb * Elem<T>::kBytes;
-
-    // per-thread staging assignment: chunk ci -> (row = ci / 8, chunk = ci % 8)
-    const char* a_src[A_CHUNKS];
-    int a_dst[A_CHUNKS];
-#pragma unroll
-    for (int i = 0; i < A_CHUNKS; i++) {
-        const int ci = tid + i * 256, row = ci >> 3, c = ci & 7;
-        int gr = m0 + row;
-        gr = gr < g.M ? gr : g.M - 1;
-        a_src[i] = Ab + (size_t)gr * lda_b + c * 16;
-        a_dst[i] = lds_off<ROWB>(row, c);
+static std::mutex g_stamp_mu;
+static unsigned long long* g_stamp_buf = nullptr;                  // allocated by the first gemm_set_stamps(1), never freed
+static std::atomic<int> g_stamp_dev{-1};                           // device ordinal the buffer lives on: launches elsewhere record nothing
+static std::atomic<unsigned long long*> g_stamps{nullptr};         // what launches are handed: the buffer, or null while switched off
+// pnp_set_tuning("gemm_stamps"): process-wide, default off
+int gemm_set_stamps(int on) {
+    std::lock_guard<std::mutex> lk(g_stamp_mu);
+    if (on && !g_stamp_buf) {
+        const int d = current_device();
+        if (d < 0 || hipMalloc(&g_stamp_buf, kStampBlocks * 64) != hipSuccess) return PNP_ERR_HIP;
+        g_stamp_dev.store(d, std::memory_order_relaxed);
     }
-    const char* b_src[B_CHUNKS];
-    int b_dst[B_CHUNKS];
-#pragma unroll
-    for (int i = 0; i < B_CHUNKS; i++) {
-        const int ci = tid + i * 256, row = ci >> 3, c = ci & 7;
-        int gr = n0 + row;
-        gr = gr < g.Nvalid ? gr : g.Nvalid - 1;
-        b_src[i] = Bb + (size_t)gr * ldb_b + c * 16;
-        b_dst[i] = lds_off<ROWB>(row, c);
-    }
-
-    f32x4 acc[TN][TM];
-#pragma unroll
-    for (int i = 0; i < TN; i++)
-#pragma unroll
-        for (int j = 0; j < TM; j++) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    chunk16 ra[A_CHUNKS], rb[B_CHUNKS];
-    const int nk = g.K / BK;
-#pragma unroll
-    for (int i = 0; i < A_CHUNKS; i++) ra[i] = *reinterpret_cast<const chunk16*>(a_src[i]);
-#pragma unroll
-    for (int i = 0; i < B_CHUNKS; i++) rb[i] = *reinterpret_cast<const chunk16*>(b_src[i]);
-#pragma unroll
-    for (int i = 0; i < A_CHUNKS; i++) *reinterpret_cast<chunk16*>(smem + a_dst[i]) = ra[i];
-#pragma unroll
-    for (int i = 0; i < B_CHUNKS; i++) *reinterpret_cast<chunk16*>(smem + BM * ROWB + b_dst[i]) = rb[i];
-    __syncthreads();
-
-    for (int kt = 0; kt < nk; kt++) {
-        const int cur = kt & 1;
-        const char* cA = smem + cur * STAGE;
-        const char* cB = cA + BM * ROWB;
-        char* nA = smem + (cur ^ 1) * STAGE;
-        char* nB = nA + BM * ROWB;
-        if (kt + 1 < nk) {
-            const size_t koff = (size_t)(kt + 1) * ROWB;
-#pragma unroll
-            for (int i = 0; i < A_CHUNKS; i++) ra[i] = *reinterpret_cast<const chunk16*>(a_src[i] + koff);
-#pragma unroll
-            for (int i = 0; i < B_CHUNKS; i++) rb[i] = *reinterpret_cast<const chunk16*>(b_src[i] + koff);
-        }
-        constexpr int KSTEPS = BK / 32;
-#pragma unroll
-        for (int ks = 0; ks < KSTEPS; ks++) {
-            Frag<T> fa[TM], fb[TN];
-#pragma unroll
-            for (int j = 0; j < TM; j++) lds_frag<ROWB>(fa[j], cA, wm * WTM + j * 16 + r, ks, q);
-#pragma unroll
-            for (int i = 0; i < TN; i++) lds_frag<ROWB>(fb[i], cB, wn * WTN + i * 16 + r, ks, q);
-#pragma unroll
-            for (int i = 0; i < TN; i++)
-#pragma unroll
-                for (int j = 0; j < TM; j++) mma16(acc[i][j], fb[i], fa[j]);
-        }
-        if (kt + 1 < nk) {
-#pragma unroll
-            for (int i = 0; i < A_CHUNKS; i++) *reinterpret_cast<chunk16*>(nA + a_dst[i]) = ra[i];
-#pragma unroll
-            for (int i = 0; i < B_CHUNKS; i++) *reinterpret_cast<chunk16*>(nB + b_dst[i]) = rb[i];
-        }
-        __syncthreads();
-    }
-
-    // ---- epilogue: lane owns rows m = .. + r, columns n = .. + 4q .. 4q+3 of each 16x16 tile
-#pragma unroll
-    for (int j = 0; j < TM; j++) {
-        const int m = m0 + wm * WTM + j * 16 + r;
-        if (m >= g.M) continue;
-        const RowCtx rc = row_ctx(g, m);
-#pragma unroll
-        for (int i = 0; i < TN; i++) {
-            const int n = n0 + wn * WTN + i * 16 + q * 4;
-            if (n >= g.Nvalid) continue;
-            store_frag<T>(g, rc, acc[i][j], m, n, n + 3 < g.Nvalid);
-        }
-    }
-}
-
-template <typename T, int BM, int BN>
-static int launch_cfg(const GemmArgs& g, hipStream_t s) {
-    const int nbm = (g.M + BM - 1) / BM, nbn = g.N / BN;
-    const size_t smem = 2 * (BM + BN) * 128;
-    static std::atomic<uint32_t> opted{0};            // per device ordinal (common.h: lds_opt_in)
-    if (lds_opt_in(opted, reinterpret_cast<const void*>(gemm_nt_kernel<T, BM, BN>), (int)smem) != PNP_OK) return PNP_ERR_HIP;
-    hipLaunchKernelGGL((gemm_nt_kernel<T, BM, BN>), dim3(nbm * nbn), dim3(256), smem, s, g);
-    return hipGetLastError() == hipSuccess ? PNP_OK : PNP_ERR_HIP;
-}
-
-static constexpr int kStampBlocks = 8192;
-static unsigned long long*& stamp_buf() {
-    static unsigned long long* p = nullptr;
-    return p;
+    g_stamps.store(on ? g_stamp_buf : nullptr, std::memory_order_relaxed);
+    return PNP_OK;
 }
 int gemm_read_stamps(unsigned long long* host_out, int max_blocks) {
-    if (!stamp_buf()) return PNP_ERR_STATE;              // product builds never allocate it (see PNP_DEV above)
+    std::lock_guard<std::mutex> lk(g_stamp_mu);
+    if (!g_stamp_buf) return PNP_ERR_STATE;              // stamps were never enabled
     const int n = max_blocks < kStampBlocks ? max_blocks : kStampBlocks;
     if (hipDeviceSynchronize() != hipSuccess) return PNP_ERR_HIP;
-    return hipMemcpy(host_out, stamp_buf(), (size_t)n * 64, hipMemcpyDeviceToHost) == hipSuccess ? PNP_OK : PNP_ERR_HIP;
+    return hipMemcpy(host_out, g_stamp_buf, (size_t)n * 64, hipMemcpyDeviceToHost) == hipSuccess ? PNP_OK : PNP_ERR_HIP;
 }
-
-// Development knobs (timing ablations, forced tile variants, in-kernel clock stamps) exist only in builds made with
-// `make DEV=1` (-DPNP_DEV); the product library reads no environment variable.
-#ifdef PNP_DEV
-static int dev_env(const char* name, int dflt) {
-    const char* v = getenv(name);
-    return v ? atoi(v) : dflt;
-}
-#endif
 
 // Host entry.  N is rounded up to the tile internally (loads clamp, stores mask on Nvalid).
 int gemm_nt(int dtype_bf16, GemmArgs g, hipStream_t s) {
@@ -1174,16 +1028,8 @@ int gemm_nt(int dtype_bf16, GemmArgs g, hipStream_t s) {
     // (broader than the fault: a padded residual only over-reads on its last row): no engine launch uses the combination
     if ((g.N & 3) && ((g.bias && !g.bias_on_rows) || g.resid || g.aux)) return PNP_ERR_ARG;
     g.Nvalid = g.N;
-    int variant = 0;
-#ifdef PNP_DEV
-    variant = dev_env("PNP_GEMM_VARIANT", 0);              // 1 / 2 / 3 / 4: generic 256x128 / generic 256x256 / generic 128x128 / wide
-    g.ablate = dev_env("PNP_GEMM_ABLATE", 0);
-    if (getenv("PNP_GEMM_GM")) g.ablate = 100 + dev_env("PNP_GEMM_GM", 4);   // tile-order experiment (gemm_x3.hip)
-    if (dev_env("PNP_GEMM_STAMPS", 0)) {
-        if (!stamp_buf() && hipMalloc(&stamp_buf(), kStampBlocks * 64) != hipSuccess) return PNP_ERR_HIP;
-        g.stamps = stamp_buf();
-    }
-#endif
+    g.stamps = g_stamps.load(std::memory_order_relaxed);
+    if (g.stamps && current_device() != g_stamp_dev.load(std::memory_order_relaxed)) g.stamps = nullptr;
     // small problems (text side: M = B*L rows) use 64x64 tiles to fill more CUs
     const long tiles128 = (long)((g.M + 127) / 128) * ((g.N + 127) / 128);
     const bool small = tiles128 < 192 && !x3;
@@ -1191,12 +1037,6 @@ int gemm_nt(int dtype_bf16, GemmArgs g, hipStream_t s) {
         // text side (M = B*L rows): 64 x 64 tiles, 4 waves of 32 x 32, 3-slot DMA ring -- the deep
         // prefetch matters more than tile efficiency for these latency-bound launches
         g.N = (g.N + 63) / 64 * 64;
-#ifdef PNP_DEV
-        if (dev_env("PNP_GEMM_SMALL", 0) == 1) return dtype_bf16 ? launch_cfg<bf16, 64, 64>(g, s) : launch_cfg<float, 64, 64>(g, s);
-        const int small_ns = dev_env("PNP_GEMM_SMALL_NS", 3);
-        if (dtype_bf16 && small_ns == 4) return launch_big<bf16, 64, 64, 32, 32, 4>(g, s);
-        if (dtype_bf16 && small_ns == 6) return launch_big<bf16, 64, 64, 32, 32, 6>(g, s);
-#endif
         return dtype_bf16 ? launch_big<bf16, 64, 64, 32, 32, 3>(g, s) : launch_big<float, 64, 64, 32, 32, 3>(g, s);
     }
     static GemmProfile never_on;                           // launches outside an engine (pnp_op_*) are not timed
@@ -1213,7 +1053,7 @@ int gemm_nt(int dtype_bf16, GemmArgs g, hipStream_t s) {
     }
     const double fl = 2.0 * g.M * (double)g.N * g.K;       // algorithmic FLOPs (the split-bf16 form issues 3x as MFMA work)
     g.N = (g.N + 127) / 128 * 128;
-    // Tile choice (in-kernel clock stamps, tools/gemm_stamps.py on a DEV build):
+    // Tile choice (in-kernel clock stamps, tools/gemm_stamps.py):
     //   bf16 ViT-block epilogues (bias -> bf16 | bias+GELU -> bf16 | bias+residual -> f32), >= 128 tiles:
     //       gemm_nt_wide_kernel, 256 x 256, 32x32x16 MFMA; main loop ~2350 clk per 64-deep slab against
     //       2048 MFMA clk, epilogue staged through LDS (full-line stores)
@@ -1228,14 +1068,12 @@ int gemm_nt(int dtype_bf16, GemmArgs g, hipStream_t s) {
         if (wide < 0) return PNP_ERR_ARG;
         g.N = (g.Nvalid + 255) / 256 * 256;
         r = launch_x3_wide(wide, g, s);
-    } else if (wide >= 0 && (variant == 4 || (variant == 0 && tiles256 >= 128))) {
+    } else if (wide >= 0 && tiles256 >= 128) {
         g.N = (g.Nvalid + 255) / 256 * 256;
         r = wide == WIDE_BF16 ? launch_wide<WIDE_BF16>(g, s)
             : wide == WIDE_GELU_BF16 ? launch_wide<WIDE_GELU_BF16>(g, s)
             : wide == WIDE_RESID_F32 ? launch_wide<WIDE_RESID_F32>(g, s) : launch_wide<WIDE_TOKCOLS_BF16>(g, s);
-    } else if (variant == 1) {
-        r = dtype_bf16 ? launch_big<bf16, 256, 128, 64, 64, 3>(g, s) : launch_big<float, 256, 128, 64, 64, 3>(g, s);
-    } else if (dtype_bf16 && (variant == 2 || (variant == 0 && big_k))) {
+    } else if (dtype_bf16 && big_k) {
         g.N = (g.Nvalid + 255) / 256 * 256;
         r = launch_big<bf16, 256, 256, 128, 64, 2, false>(g, s);
     } else {

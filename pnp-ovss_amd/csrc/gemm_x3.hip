@@ -47,21 +47,12 @@
 // vmcnt, one lane stores the flag `sc1`; the consumer polls that word with `sc1` loads, joins a workgroup barrier, and every
 // load of the payload is an `sc1` buffer load (no L1 copy can be stale, no agent-scope fence is needed).  The owner resets
 // the flag it consumed, so the state is clean for the next launch (and under graph replay).
-#include <stdlib.h>
-
 #include <mutex>
 #include <type_traits>
 
 #include "common.h"
 #include "gemm.h"
 #include "gemm_wide.h"
-
-// epilogue stores: -DPNP_EPI_NT builds mark them non-temporal (A/B experiment: do the output tiles evict the operand panels from L2?)
-#ifdef PNP_EPI_NT
-#define PNP_EPI_STORE(ptr, val) __builtin_nontemporal_store((val), (ptr))
-#else
-#define PNP_EPI_STORE(ptr, val) (*(ptr) = (val))
-#endif
 
 namespace pnp {
 
@@ -85,11 +76,7 @@ __device__ __forceinline__ void x3_half(f32x4& c0, f32x4& c1, const frag16& ah, 
 // remapped to per-image padded columns -> fp32) | WIDE_GELU_SPLIT (+bias, erf-GELU -> (hi, lo) bf16 pair) | WIDE_SPLIT (+bias -> pair)
 typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 typedef __attribute__((address_space(1))) uint32_t gu32;
-#ifdef PNP_SK_PLAIN            // experiment: plain payload + agent-scope release / acquire fences instead of write-through stores
-#define PNP_SK_AUX 0
-#else
-#define PNP_SK_AUX 16          // sc1
-#endif
+constexpr int kSkAux = 16;     // sc1: the write-through form of the stream-K payload stores and loads
 
 template <int EPI, bool SK>
 __global__ __launch_bounds__(512) void gemm_nt_x3_kernel(const GemmArgs g) {
@@ -117,16 +104,6 @@ __global__ __launch_bounds__(512) void gemm_nt_x3_kernel(const GemmArgs g) {
     uint32_t soff[4];
     auto set_tile = [&](int tile, int& m0, int& n0, int lane) {
         int bm, bn;
-#ifdef PNP_DEV
-        if (g.ablate >= 100) {                               // PNP_GEMM_GM: group height of the tile order (0 = plain row-major ids)
-            if (g.ablate == 100) {
-                bm = tile / nbn;
-                bn = tile - bm * nbn;
-            } else {
-                tile_coords_rt(g.ablate - 100, tile, nbm, nbn, bm, bn);
-            }
-        } else
-#endif
         tile_coords<4>(tile, nbm, nbn, bm, bn);
         m0 = bm * BM;
         n0 = bn * BN;
@@ -147,9 +124,6 @@ __global__ __launch_bounds__(512) void gemm_nt_x3_kernel(const GemmArgs g) {
     // k range run the SAME instruction stream as the steady state (no peeled copies of the slab body whose register
     // assignment the allocator then has to reconcile with the loop's through scratch memory)
     auto issue_one = [&](int kt, int i, uint32_t on) {  // piece i: operand = i >> 2, row group = (i >> 1) & 1, array (hi | lo) = i & 1
-#ifdef PNP_X3_ABLATE                                // timing-only builds (results are garbage; tools/gemm_x3_ab.py): 1 = no steady-state
-        if (kt >= 2) return;                        // DMA, 3 = also no slab barrier, 4 = also no fragment reads.  Compile-time:
-#endif                                              // a run-time test inside the slab loop changes the schedule it is meant to time
         const int op = i >> 2, rg = (i >> 1) & 1, lo = i & 1;
         const char* base = op ? (lo ? Blo : Bb) : (lo ? Alo : Ab);
         const int d = (kt & 1) * SLOT + op * (2 * ARR) + lo * ARR + (wave * 2 + rg) * 1024;
@@ -268,17 +242,11 @@ __global__ __launch_bounds__(512) void gemm_nt_x3_kernel(const GemmArgs g) {
 
         frag16 ah[4], al[4], bh[2][IN], bl[2][IN];
         auto rd_a = [&](int slot, int s, int jm) {
-#if defined(PNP_X3_ABLATE) && PNP_X3_ABLATE >= 4
-            return;
-#endif
             const char* p = smem + fa_off[s] + jm * 1024;
             ah[slot] = *reinterpret_cast<const frag16*>(p);
             al[slot] = *reinterpret_cast<const frag16*>(p + ARR);
         };
         auto rd_b = [&](int set, int s, int in) {
-#if defined(PNP_X3_ABLATE) && PNP_X3_ABLATE >= 4
-            return;
-#endif
             const char* p = smem + fb_off[s] + in * 1024;
             bh[set][in] = *reinterpret_cast<const frag16*>(p);
             bl[set][in] = *reinterpret_cast<const frag16*>(p + ARR);
@@ -325,10 +293,8 @@ __global__ __launch_bounds__(512) void gemm_nt_x3_kernel(const GemmArgs g) {
                     if (j == JM - 3) {
                         // own reads of slab kt complete, own pieces of slab kt+1 landed (a builtin, not asm: the compiler's
                         // scoreboard sees it and adds no wait of its own behind the reads that follow)
-#if !defined(PNP_X3_ABLATE) || PNP_X3_ABLATE < 3
                         __builtin_amdgcn_s_waitcnt(0x0070);   // vmcnt(0) lgkmcnt(0)
                         __builtin_amdgcn_s_barrier();         // slab kt+1 complete; nobody reads slab kt's slot any more
-#endif
                     }
                     rd_a((j + 3) & 3, S ^ 1, j + 3 - JM);
                     if (j == JM - 2) rd_b(S ^ 1, S ^ 1, 1);
@@ -376,8 +342,7 @@ __global__ __launch_bounds__(512) void gemm_nt_x3_kernel(const GemmArgs g) {
                 stamp_sk(0);
                 request_next();
                 const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(g.sk_part + (size_t)bid * (BM * BN), 0, BM * BN * 4, 0x00020000);
-#if !defined(PNP_SK_ABLATE) || PNP_SK_ABLATE < 1 || PNP_SK_ABLATE == 3     // timing-only builds (tools/gemm_x3_streamk.py --lib): 1 = no
-                {                                     // partial-tile traffic, 2 = also no flag wait, 3 = stores only, 4 = loads only
+                {
                     // ONE lane-offset register walks the 32 pieces (8 KB apart): offsets folded into 32 constants would cost 32 scalar
                     // registers this kernel does not have (the allocator then parks accumulators in scratch memory)
                     int voff = tid * 16;
@@ -385,20 +350,11 @@ __global__ __launch_bounds__(512) void gemm_nt_x3_kernel(const GemmArgs g) {
                     for (int j = 0; j < JM; j++)
 #pragma unroll
                         for (int i = 0; i < IN; i++) {
-                            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[j][i]), rs, voff, 0, PNP_SK_AUX);   // aux 16 = sc1
+                            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[j][i]), rs, voff, 0, kSkAux);
                             voff += 8192;
                             asm volatile("" : "+v"(voff));
                         }
                 }
-#endif
-#ifdef PNP_SK_PLAIN
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __syncthreads();
-                if (tid == 0) {
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                }
-#endif
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // every storing wave drains before the flag is raised
                 __syncthreads();
                 if (tid == 0) __hip_atomic_store((gu32*)(g.sk_flag + bid), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -412,11 +368,7 @@ __global__ __launch_bounds__(512) void gemm_nt_x3_kernel(const GemmArgs g) {
                     if (wave == 0) {
                         gu32* const fl = (gu32*)(g.sk_flag + src);
                         uint32_t spins = 0;
-#if defined(PNP_SK_ABLATE) && PNP_SK_ABLATE >= 2
-                        while (false) {
-#else
                         while (__hip_atomic_load(fl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 1u) {
-#endif
                             __builtin_amdgcn_s_sleep(8);
                             if (++spins > (1u << 22)) {                      // ~1 s: give up loudly instead of hanging the device
                                 if (lane == 0) __hip_atomic_store((gu32*)g.sk_tmo, 1u + (uint32_t)bid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -427,28 +379,19 @@ __global__ __launch_bounds__(512) void gemm_nt_x3_kernel(const GemmArgs g) {
                     }
                     __syncthreads();
                     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(g.sk_part + (size_t)src * (BM * BN), 0, BM * BN * 4, 0x00020000);
-#ifdef PNP_SK_PLAIN
-                    if (tid == 0) {
-                        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    }
-                    __syncthreads();
-#endif
-#if !defined(PNP_SK_ABLATE) || PNP_SK_ABLATE < 1 || PNP_SK_ABLATE == 4
                     int voff = tid * 16;
 #pragma unroll
                     for (int grp = 0; grp < 4; grp++) {
                         u32x4 t[8];
 #pragma unroll
                         for (int x = 0; x < 8; x++) {
-                            t[x] = __builtin_amdgcn_raw_buffer_load_b128(rs, voff, 0, PNP_SK_AUX);
+                            t[x] = __builtin_amdgcn_raw_buffer_load_b128(rs, voff, 0, kSkAux);
                             voff += 8192;
                             asm volatile("" : "+v"(voff));
                         }
 #pragma unroll
                         for (int x = 0; x < 8; x++) acc[(grp * 8 + x) / IN][(grp * 8 + x) % IN] += __builtin_bit_cast(f32x4, t[x]);
                     }
-#endif
                 }
                 stamp_sk(3);
             }
@@ -593,7 +536,7 @@ __global__ __launch_bounds__(512) void gemm_nt_x3_kernel(const GemmArgs g) {
 #pragma unroll
                     for (int it = 0; it < 16; it++) {
                         const int m = em0 + wm * 128 + half * 64 + it * 4 + (lane >> 4);
-                        if (full || (m < g.M && nv)) PNP_EPI_STORE(reinterpret_cast<bf16x4*>(obase + (size_t)(half * 64 + it * 4) * g.ldo_t), sv[it]);
+                        if (full || (m < g.M && nv)) *reinterpret_cast<bf16x4*>(obase + (size_t)(half * 64 + it * 4) * g.ldo_t) = sv[it];
                     }
                 }
             }
@@ -631,7 +574,7 @@ __global__ __launch_bounds__(512) void gemm_nt_x3_kernel(const GemmArgs g) {
                     f32x4 v = sv[it] + bv;
                     if constexpr (kResid) v += rcur[it];
                     const int m = em0 + wm * 128 + qd * 32 + it * 4 + (lane >> 4);
-                    if (full || (m < g.M && nv)) PNP_EPI_STORE(reinterpret_cast<f32x4*>(obase + (size_t)(qd * 32 + it * 4) * g.ldo), v);
+                    if (full || (m < g.M && nv)) *reinterpret_cast<f32x4*>(obase + (size_t)(qd * 32 + it * 4) * g.ldo) = v;
                 }
                 if (qd == 0) request_next();
             }
@@ -686,10 +629,7 @@ static int launch_x3(GemmArgs g, hipStream_t s) {
     if (!n_cu) return PNP_ERR_HIP;
     static std::atomic<uint32_t> opted{0}, opted_sk{0};            // per device ordinal (common.h: lds_opt_in)
     const int ntiles = nbm * nbn;
-    int cap = n_cu;
-#ifdef PNP_DEV
-    if (getenv("PNP_GEMM_GRID")) cap = atoi(getenv("PNP_GEMM_GRID"));
-#endif
+    const int cap = n_cu;                                          // workgroups of a launch: one per CU (LDS-limited)
     const int mode = streamk_mode();
     StreamKWs* const ws = g.sk;
     if (mode && ws && ws->part && ws->wgs >= cap) {

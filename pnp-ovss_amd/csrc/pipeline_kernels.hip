@@ -8,8 +8,6 @@
 //   threshold / upsample / Scale_0_1 / background   PnP.py:348-379, 424-455, 1078-1094
 //   blur        PnP.py:1149-1153 (scipy.ndimage.gaussian_filter: reflect, truncate 4, double acc)
 //   remap/hist  PnP.py:390-399, 1106-1146
-#include <stdlib.h>
-
 #include "common.h"
 #include "kernels.h"
 #include "../../include/pnp_math.h"
@@ -866,9 +864,6 @@ int blur_maps(const float* in, float* tmp, float* out, const PostDesc* desc, con
     size_t lds0, lds1;
     lds_for(1, lds0, lds1);
     int nt = lds0 > 80 * 1024 ? 4 : 1;
-#ifdef PNP_DEV
-    if (getenv("PNP_BLUR_NT")) nt = atoi(getenv("PNP_BLUR_NT"));
-#endif
     lds_for(nt, lds0, lds1);
     while (nt > 1 && (lds0 > 120 * 1024 || lds1 > 120 * 1024)) lds_for(--nt, lds0, lds1);
     if (lds0 > 160 * 1024 || lds1 > 160 * 1024) return PNP_ERR_ARG;            // radius <= ~300 (images up to ~1500 px on the long side)

@@ -3,8 +3,6 @@
 // Reference: med.py:88-123 (embeddings), :191-311 (attention; probs stash + grad hook at :280-283),
 //            :321-325 / :393-411 (post-LN dense blocks), :776-852 (additive masks),
 //            blip_image_text_matching.py:238-249 (enc token, itm head), :399-404 (loss + backward).
-#include <stdlib.h>
-
 #include <type_traits>
 
 #include "common.h"
@@ -745,9 +743,6 @@ static int row_split(int pairs, size_t smem) {
     int per_cu = (int)(160 * 1024 / (smem ? smem : 1));
     per_cu = per_cu < 1 ? 1 : per_cu > 8 ? 8 : per_cu;
     const int slots = cus * per_cu;
-#ifdef PNP_DEV
-    if (getenv("PNP_TXT_NZ")) return atoi(getenv("PNP_TXT_NZ"));
-#endif
     int best = 1;
     double cost = 1e30;
     for (int nz = 1; nz <= 4; nz++) {

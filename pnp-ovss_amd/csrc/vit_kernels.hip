@@ -2,8 +2,6 @@
 // LayerNorm, and the fused patch self-attention (flash-style, MFMA QK^T / PV, LDS-staged K / V^T).
 // Reference: vit.py:274-290 (forward), :91-121 (Attention), :164-167 (Block);
 //            PnP_OVSS_0514_updated_segmentation.py:597-603 (zeroing dropped 16x16 blocks).
-#include <stdlib.h>
-
 #include "common.h"
 #include "kernels.h"
 
@@ -414,29 +412,6 @@ __global__ __launch_bounds__(512) void vit_attn32_kernel(const bf16* __restrict_
     }
 }
 
-#ifdef PNP_DEV
-// DEV diagnostics: per-(wave, key tile) issue-time clock stamps of workgroup (0, 0, 0) of the split-bf16 attention
-// (tools/attn_x3_probe.py --stamps): [wave][tile][6] = loop top, barrier passed, DMA issued, S issued, softmax done, P.V issued
-__device__ unsigned long long* g_attn_stamps = nullptr;
-__device__ int g_attn_ablate = 0;
-extern "C" int pnp_dev_attn_ablate(int on) {
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_attn_ablate), &on, sizeof(on)) == hipSuccess ? PNP_OK : PNP_ERR_HIP;
-}
-extern "C" int pnp_dev_attn_stamps(unsigned long long* d_buf) {
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_attn_stamps), &d_buf, sizeof(d_buf)) == hipSuccess ? PNP_OK : PNP_ERR_HIP;
-}
-#define PNP_ATTN_STAMP(k)                                                                                       \
-    do {                                                                                                        \
-        if (stamps && lane == 0) {                                                                              \
-            __builtin_amdgcn_sched_barrier(0);                                                                  \
-            stamps[((size_t)wave * ntiles + t) * 6 + (k)] = __builtin_readcyclecounter();                       \
-            __builtin_amdgcn_sched_barrier(0);                                                                  \
-        }                                                                                                       \
-    } while (0)
-#else
-#define PNP_ATTN_STAMP(k) do {} while (0)
-#endif
-
 // Split-bf16 ("bf16x3") form of the kernel above for compute mode 2: q, k, v arrive as (hi, lo) bf16 pairs (the fused
 // q|k|v rows of the split-output GEMM), both products run as three bf16 MFMA passes -- S = K_hi.Q_hi + K_hi.Q_lo + K_lo.Q_hi,
 // O += V_hi.P_hi + V_hi.P_lo + V_lo.P_hi with P split after the exp2 -- and the context leaves as a (hi, lo) pair for the
@@ -473,7 +448,7 @@ __global__ __launch_bounds__(768) void vit_attn32_x3_kernel(const bf16* __restri
     // are formed by integer masks from one base and three uniform differences -- never by indexing or selecting pointers:
     // hipcc keeps such pointers (the `kb[2]` / `vb[2]` arrays this kernel had) in scratch memory and loads the selected one per
     // piece, and that scratch load then waits -- vmcnt is one in-order counter -- for every DMA piece issued before it: ~700
-    // cycles per piece, 3600 of the 9500 cycles a key tile took (tools/attn_x3_probe.py --dev --stamps): 190 -> 149 us at 442
+    // cycles per piece, 3600 of the 9500 cycles a key tile took (found with per-wave clock stamps in this kernel, an instrument since removed: reproducible from commit fd1b36e): 190 -> 149 us at 442
     // tokens, 758 -> 606 us at 2305.  Rows past N - 1 (ragged last tile) re-read row N - 1: their scores are masked, their V
     // rows multiply exact zeros and must be finite.
     const uint64_t k0 = reinterpret_cast<uint64_t>(qk) + koff;
@@ -488,9 +463,6 @@ __global__ __launch_bounds__(768) void vit_attn32_x3_kernel(const bf16* __restri
             const uint64_t d = (m_v & m_lo & d_vlo) | (m_v & ~m_lo & d_v) | (~m_v & m_lo & d_klo);
             const uint32_t ld2 = ((uint32_t)ld_qk + ((uint32_t)m_v & (uint32_t)(ld_vt - ld_qk))) * 2u;
             int rs = t * 64 + (p & 7) * 8;
-#ifdef PNP_DEV
-            if (g_attn_ablate) rs = (p & 7) * 8;          // timing-only (results garbage): every tile fetches the first one's rows (cache-hot)
-#endif
             rs = rs < N - 1 ? rs : N - 1;
             const char* const sbase = reinterpret_cast<const char*>(k0 + d + (uint64_t)((uint32_t)rs * ld2));
             int lr = rs + prow;
@@ -522,17 +494,11 @@ __global__ __launch_bounds__(768) void vit_attn32_x3_kernel(const bf16* __restri
     const int sw = (l32 >> 1) & 7;
     const int ntiles = (N + 63) / 64;
 
-#ifdef PNP_DEV
-    unsigned long long* const stamps = (blockIdx.x | blockIdx.y | blockIdx.z) == 0 ? g_attn_stamps : nullptr;
-#endif
     issue_tile(0);
     for (int t = 0; t < ntiles; t++) {
-        PNP_ATTN_STAMP(0);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
-        PNP_ATTN_STAMP(1);
         if (t + 1 < ntiles) issue_tile(t + 1);
-        PNP_ATTN_STAMP(2);
         const char* Ks = ring[t & 1];
         const char* Vs = Ks + TILE;
         const char* Kl = Ks + 2 * TILE;
@@ -553,7 +519,6 @@ __global__ __launch_bounds__(768) void vit_attn32_x3_kernel(const bf16* __restri
                 s[kt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kh, fq[ks], s[kt], 0, 0, 0);
             }
         }
-        PNP_ATTN_STAMP(3);
         if (t == ntiles - 1 && (N & 63)) {
 #pragma unroll
             for (int kt = 0; kt < 2; kt++)
@@ -588,7 +553,6 @@ __global__ __launch_bounds__(768) void vit_attn32_x3_kernel(const bf16* __restri
                 fp[kt * 2 + (e >> 3)][e & 7] = ph;
                 fpl[kt * 2 + (e >> 3)][e & 7] = (bf16)(p - (float)ph);
             }
-        PNP_ATTN_STAMP(4);
         const int grp_d = ((lane >> 4) & 1) * 16, tq = (lane >> 2) & 3, tp = lane & 3;
 #pragma unroll
         for (int j = 0; j < 4; j++)
@@ -614,7 +578,6 @@ __global__ __launch_bounds__(768) void vit_attn32_x3_kernel(const bf16* __restri
                 o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fv[0], fpl[j], o[dt], 0, 0, 0);
                 o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fv[0], fp[j], o[dt], 0, 0, 0);
             }
-        PNP_ATTN_STAMP(5);
     }
     l_run += __shfl_xor(l_run, 32, 64);
     if (q_valid) {
@@ -665,10 +628,7 @@ int vit_attention_x3(const void* qkv_hi, const void* qkv_lo, int ld_qk, int D, v
     // one workgroup per CU (157 registers: 12 wave slots, two 7-wave workgroups do not fit and smaller ones lose more to the
     // per-tile hand-over than they win): long sequences take up to 12 waves per workgroup (-3 % at 2305 tokens), 442 tokens
     // are 14 waves = two workgroups of 7
-    int max_wpb = nqw > 24 ? 12 : 8;
-#ifdef PNP_DEV
-    if (getenv("PNP_ATTN_WPB")) max_wpb = atoi(getenv("PNP_ATTN_WPB"));   // <= 12 (launch bound 768 threads)
-#endif
+    const int max_wpb = nqw > 24 ? 12 : 8;
     const int nblk = (nqw + max_wpb - 1) / max_wpb, wpb = (nqw + nblk - 1) / nblk;
     const bf16 *qh = (const bf16*)qkv_hi, *ql = (const bf16*)qkv_lo;
     hipLaunchKernelGGL(vit_attn32_x3_kernel, dim3(nblk, H, B), dim3(wpb * 64), 0, s, qh, ql, ld_qk, D, qh + 2 * D, ql + 2 * D, ld_qk,

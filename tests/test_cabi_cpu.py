@@ -105,6 +105,36 @@ def test_operator_entry_points_validate_arguments_without_a_gpu(lib):
     assert lib.pnp_op_gemm_x3(p, p, 64, p, p, 64, 8, 63, 64, n, 1, n, 0, p, 448, n, n, 0, 0, 442, 448, n) == -22
 
 
+def test_library_reads_no_environment_variable(lib):
+    """include/pnp_hip.h: there is one build of the library and it reads no environment variable -- every switch is an argument
+    or a pnp_set_tuning key.  Pinned on the built library: getenv / secure_getenv are not among its undefined dynamic symbols."""
+    import shutil
+    import subprocess
+    nm = shutil.which("nm") or shutil.which("llvm-nm") or "/opt/rocm/lib/llvm/bin/llvm-nm"
+    if not os.path.exists(nm):
+        pytest.skip("no symbol lister (nm / llvm-nm) installed")
+    out = subprocess.run([nm, "-D", "--undefined-only", LIB], capture_output=True, text=True, check=True).stdout
+    names = {line.split()[-1].split("@")[0] for line in out.splitlines() if line.split()}
+    assert len(names) > 20, "no undefined symbols listed: not looking at the dynamic symbol table"
+    assert any(n.startswith("hip") for n in names), sorted(names)[:10]
+    assert not names & {"getenv", "secure_getenv", "__secure_getenv"}, sorted(names & {"getenv", "secure_getenv", "__secure_getenv"})
+
+
+def test_gemm_stamps_switch_without_a_gpu(lib):
+    """pnp_set_tuning("gemm_stamps"): 0 | 1 only; switching off needs no device; pnp_dbg_gemm_stamps has nothing to copy
+    (PNP_ERR_STATE = -1, before any HIP call) until stamps have been enabled once."""
+    import torch
+    lib.pnp_set_tuning.restype = ctypes.c_int
+    lib.pnp_dbg_gemm_stamps.restype = ctypes.c_int
+    assert lib.pnp_set_tuning(b"gemm_stamps", 2) == -22
+    assert lib.pnp_set_tuning(b"gemm_stamps", -1) == -22
+    assert lib.pnp_set_tuning(b"gemm_stamps", 0) == 0
+    if torch.cuda.is_available():
+        return                                  # another test of this process may have enabled them
+    buf = (ctypes.c_uint64 * 8)()
+    assert lib.pnp_dbg_gemm_stamps(buf, 1) == -1
+
+
 def _gfx950_code_objects(lib_path, tmpdir):
     """The gfx950 code objects inside the library's .hip_fatbin section (one clang offload bundle per translation unit:
     magic, u64 entry count, per entry u64 offset / u64 size / u64 triple length / triple)."""

@@ -531,3 +531,111 @@ def test_gemm_args_refuses_bad_arguments(lib):
                 dict(mode=2), dict(col_div=8, col_pad=4), dict(col_div=-1), dict(row_div=-1), dict(K=48), dict(lda=66)):
         assert call(**bad) == ERR_ARG, bad
     torch.cuda.synchronize()
+
+
+# ------------------------------------------------------------------------------------------ in-kernel clock stamps
+def test_gemm_stamps_time_the_shipped_kernels(lib):
+    """pnp_set_tuning("gemm_stamps", 1) / pnp_dbg_gemm_stamps on the three stamped kernel families at their smallest launches:
+    fp32 generic (four 64 x 64 workgroups), split-bf16 wide with the stream-K tail off (four tiles, one ragged row tile) and
+    bf16 wide at the dispatcher's threshold of 128 tiles.  Stamps change no output bit; every launched workgroup (grid =
+    min(tiles, CUs)) leaves a start (slot 0) and an end (slot 3) on the shader clock and on the wall clock (slots 4, 7), written
+    by THIS launch (its row differs from what the buffer held before); with the switch off again a launch leaves the rows alone."""
+    import numpy as np
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    gen = torch.Generator(device=DEV).manual_seed(11)
+    rnd = lambda *s: torch.randn(*s, generator=gen, device=DEV)
+
+    def fp32_generic():
+        M, N, K = 96, 128, 64
+        A, B, bias = rnd(M, K), rnd(N, K), rnd(N)
+        run = lambda out: lib.pnp_op_gemm(0, _ptr(A), K, _ptr(B), K, M, N, K, _ptr(bias), None, 0, _ptr(out), N, 0, None)
+        return run, (M, N, torch.float32), 4, R.gemm_branch("f32", M, N, K, False) == "g64"
+
+    def split_wide():
+        M, N, K = 300, 512, 128
+        (Ah, Al), (Bh, Bl), bias = R.split_pair(rnd(M, K)), R.split_pair(rnd(N, K) * 0.25), rnd(N)
+        run = lambda out: lib.pnp_op_gemm_x3(_ptr(Ah), _ptr(Al), K, _ptr(Bh), _ptr(Bl), K, M, N, K, _ptr(bias), 0, None, 0, _ptr(out), N,
+                                             None, None, 0, 0, 0, 0, None)
+        return run, (M, N, torch.float32), 4, R.gemm_branch("x3", M, N, K, False) == "x3_wide"
+
+    def bf16_wide():
+        M, N, K = 4096, 2048, 64
+        A, B, bias = rnd(M, K).bfloat16(), rnd(N, K).bfloat16(), rnd(N)
+        run = lambda out: lib.pnp_op_gemm_ex(1, _ptr(A), K, _ptr(B), K, M, N, K, _ptr(bias), None, 0, None, 0, _ptr(out), N, 0, None)
+        return run, (M, N, torch.bfloat16), 128, R.gemm_branch("bf16", M, N, K, True) == "wide"
+
+    def launch(run, shape):
+        out = torch.zeros(shape[0], shape[1], dtype=shape[2], device=DEV)
+        assert run(out) == 0
+        torch.cuda.synchronize()
+        return _bits(out).cpu()
+
+    def stamps(rows):
+        st = np.zeros((rows, 8), dtype=np.uint64)
+        assert lib.pnp_dbg_gemm_stamps(st.ctypes.data, rows) == 0
+        return st
+
+    try:
+        assert lib.pnp_set_tuning(b"streamk", 0) == 0
+        for case in (fp32_generic, split_wide, bf16_wide):
+            name = case.__name__
+            run, shape, tiles, lands = case()
+            assert lands, (name, "lands on another kernel")
+            grid = min(tiles, cus)
+            off = launch(run, shape)
+            assert bool(off.ne(0).any()), name
+            assert lib.pnp_set_tuning(b"gemm_stamps", 1) == 0
+            before = stamps(grid + 8)
+            on = launch(run, shape)
+            assert torch.equal(off, on), (name, "stamps changed the output")
+            st = stamps(grid + 8)
+            print(f"{name}: grid {grid}, shader clocks start..end min {int((st[:grid, 3] - st[:grid, 0]).min())} "
+                  f"max {int((st[:grid, 3] - st[:grid, 0]).max())}, wall ticks max {int((st[:grid, 7] - st[:grid, 4]).max())}")
+            for a, b in ((0, 3), (4, 7)):
+                assert (st[:grid, a] != 0).all() and (st[:grid, b] != 0).all(), (name, a, b)
+                assert (st[:grid, a] <= st[:grid, b]).all(), (name, a, b)
+            assert (st[:grid] != before[:grid]).any(axis=1).all(), (name, "a launched workgroup left no stamps")
+            assert (st[grid:] == before[grid:]).all(), (name, "rows past the grid were written")
+            assert lib.pnp_set_tuning(b"gemm_stamps", 0) == 0
+            assert torch.equal(off, launch(run, shape)), name
+            assert (stamps(grid + 8) == st).all(), (name, "a launch with stamps off wrote stamps")
+    finally:
+        assert lib.pnp_set_tuning(b"gemm_stamps", 0) == 0
+        assert lib.pnp_set_tuning(b"streamk", 1) == 0
+
+
+def test_gemm_stamps_skip_launches_with_more_workgroups_than_rows(lib):
+    """The stamp buffer has 8192 rows and the generic kernels launch one workgroup per tile: a launch of 8192 tiles of 128 stamps
+    every row up to the last, a launch of 8193 records nothing (it is handed no buffer: no write behind row 8191) and computes
+    the same output as with stamps off."""
+    import numpy as np
+    rows, K = 8192, 64
+    gen = torch.Generator(device=DEV).manual_seed(12)
+    A = torch.randn(1, K, generator=gen, device=DEV).bfloat16()
+    B = torch.randn((rows + 1) * 128, K, generator=gen, device=DEV).bfloat16()
+
+    def launch(tiles):
+        N = tiles * 128
+        assert R.gemm_branch("bf16", 1, N, K, False) == "g128"
+        out = torch.zeros(1, N, device=DEV)
+        assert lib.pnp_op_gemm(1, _ptr(A), K, _ptr(B), K, 1, N, K, None, None, 0, _ptr(out), N, 0, None) == 0
+        torch.cuda.synchronize()
+        return _bits(out).cpu()
+
+    def stamps():
+        st = np.zeros((rows, 8), dtype=np.uint64)
+        assert lib.pnp_dbg_gemm_stamps(st.ctypes.data, rows) == 0
+        return st
+
+    try:
+        off = launch(rows + 1)
+        assert lib.pnp_set_tuning(b"gemm_stamps", 1) == 0
+        before = stamps()
+        assert torch.equal(launch(rows), off[:, :rows * 128])
+        full = stamps()
+        assert (full != before).any(axis=1).all(), "a launch of exactly 8192 workgroups stamps every row"
+        assert (full[:, 0] != 0).all() and (full[:, 0] <= full[:, 3]).all()
+        assert torch.equal(launch(rows + 1), off), "stamps changed the output"
+        assert (stamps() == full).all(), "a launch of 8193 workgroups wrote stamps"
+    finally:
+        assert lib.pnp_set_tuning(b"gemm_stamps", 0) == 0

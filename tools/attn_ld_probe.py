@@ -10,8 +10,6 @@ sys.path.insert(0, os.path.join(ROOT, "pnp-ovss_amd"))
 import torch
 from pnp_ovss import hip
 
-if "--dev" in sys.argv:
-    hip.LIB_PATH = os.path.join(os.path.dirname(hip.LIB_PATH), "libpnp_hip_dev.so")
 lib = hip.load_library()
 B, H, N = 35, 16, 442
 D = H * 64

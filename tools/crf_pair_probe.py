@@ -14,12 +14,8 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "pnp-ovss_amd"))
 import numpy as np
 import torch
-from pnp_ovss import config as C, synth, hip
+from pnp_ovss import config as C, synth
 from pnp_ovss.hip import Engine
-
-if os.environ.get("PNP_DEV_LIB"):                          # DEV build: the PNP_CRF_* knobs of csrc/crf.hip
-    _name = os.environ["PNP_DEV_LIB"] if os.environ["PNP_DEV_LIB"].endswith(".so") else "libpnp_hip_dev.so"
-    hip.LIB_PATH = os.path.join(os.path.dirname(hip.LIB_PATH), _name)
 
 B, IMG = 35, 336
 REPS = int(sys.argv[1]) if len(sys.argv) > 1 else 3

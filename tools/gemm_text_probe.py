@@ -1,5 +1,5 @@
 """The text-side (M = B*L = 875 rows) GEMM shapes: the split-bf16 kernel (gemm_nt_small_x3_kernel, fp32 activations, weight as a
-(hi, lo) bf16 pair) next to the bf16 and the exact-fp32 kernels.  `--dev`: DEV library (PNP_SMALL_NW=4|8 selects the wave count)."""
+(hi, lo) bf16 pair) next to the bf16 and the exact-fp32 kernels."""
 import os
 import sys
 import time
@@ -10,8 +10,6 @@ sys.path.insert(0, os.path.join(ROOT, "pnp-ovss_amd"))
 import torch
 from pnp_ovss import hip
 
-if "--dev" in sys.argv:
-    hip.LIB_PATH = os.path.join(os.path.dirname(hip.LIB_PATH), "libpnp_hip_dev.so")
 lib = hip.load_library()
 M = int([a for a in sys.argv[1:] if a.isdigit()][0]) if any(a.isdigit() for a in sys.argv[1:]) else 875
 

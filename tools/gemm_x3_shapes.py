@@ -1,6 +1,6 @@
 """Split-bf16 ("bf16x3") wide GEMM at the four ViT-L block shapes of the bench batch: back-to-back launch time, issued and
-algorithmic rate; with the DEV library (make -C pnp-ovss_amd/csrc DEV=1 OBJDIR=build_dev OUT=../pnp_ovss/libpnp_hip_dev.so,
-PNP_GEMM_STAMPS=1, --dev) also the in-kernel clock and the main-loop cycles per slab from the workgroup stamps."""
+algorithmic rate; with --stamps also the in-kernel clock and the main-loop cycles per slab from the workgroup stamps
+(pnp_set_tuning("gemm_stamps", 1): switched on for one extra launch behind the timed ones)."""
 import os
 import sys
 import time
@@ -12,10 +12,8 @@ import numpy as np
 import torch
 from pnp_ovss import hip
 
-DEV = "--dev" in sys.argv
+STAMPS = "--stamps" in sys.argv
 ONLY = [a for a in sys.argv[1:] if not a.startswith("--")]
-if DEV:
-    hip.LIB_PATH = os.path.join(os.path.dirname(hip.LIB_PATH), "libpnp_hip_dev.so")
 if "--lib" in sys.argv:                                     # a named library variant next to the product one (A/B runs)
     hip.LIB_PATH = os.path.join(os.path.dirname(hip.LIB_PATH), sys.argv[sys.argv.index("--lib") + 1])
     ONLY = [a for a in ONLY if not a.endswith(".so")]
@@ -67,8 +65,11 @@ def run(tag, M, N, K, kind):
     fl = 2.0 * M * N * K
     print(f"{tag:6s} M={M} N={N} K={K}: {dt * 1e6:7.1f} us  algorithmic {fl / dt / 1e12:6.0f} TF  issued {3 * fl / dt / 1e12:6.0f} TF "
           f"({3 * fl / dt / 2.5e15:.3f} of 2.5 PF)  relerr {err:.1e}", flush=True)
-    if DEV and os.environ.get("PNP_GEMM_STAMPS"):
-        nb = min(((M + 255) // 256) * ((N + 255) // 256), 256)
+    if STAMPS:
+        hip.set_tuning("gemm_stamps", 1)
+        assert call() == 0
+        hip.set_tuning("gemm_stamps", 0)
+        nb = min(((M + 255) // 256) * ((N + 255) // 256), torch.cuda.get_device_properties(0).multi_processor_count)
         st = np.zeros((nb, 8), dtype=np.uint64)
         assert lib.pnp_dbg_gemm_stamps(st.ctypes.data, nb) == 0
         cyc = st[:, :4].astype(np.int64)

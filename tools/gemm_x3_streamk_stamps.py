@@ -1,7 +1,6 @@
-"""In-kernel clock stamps of the stream-K tail (DEV library: make -C pnp-ovss_amd/csrc DEV=1 OBJDIR=build_dev OUT=../pnp_ovss/libpnp_hip_dev.so;
-PNP_GEMM_STAMPS=1).  Per workgroup: start, end of the whole-tile part, producing part (main loop end -> partial tile stored and
+"""In-kernel clock stamps of the stream-K tail (pnp_set_tuning("gemm_stamps", 1) / pnp_dbg_gemm_stamps).  Per workgroup: start, end of the whole-tile part, producing part (main loop end -> partial tile stored and
 flag raised), owning part (main loop end -> partial tiles of the workgroups before it added), workgroup done.
-usage: PNP_GEMM_STAMPS=1 python tools/gemm_x3_streamk_stamps.py [M N K kind]"""
+usage: python tools/gemm_x3_streamk_stamps.py [M N K kind]"""
 import os
 import sys
 
@@ -12,8 +11,8 @@ import numpy as np
 import torch
 from pnp_ovss import hip
 
-hip.LIB_PATH = os.path.join(os.path.dirname(hip.LIB_PATH), "libpnp_hip_dev.so")
 lib = hip.load_library()
+hip.set_tuning("gemm_stamps", 1)
 args = [a for a in sys.argv[1:]]
 M, N, K = (int(args[0]), int(args[1]), int(args[2])) if len(args) >= 3 else (35 * 442, 3072, 1024)
 kind = args[3] if len(args) > 3 else "bias"
@@ -61,3 +60,4 @@ for mode in (0, 2):
             print(f"   workgroups with both: flag raised -> own main loop end {np.median(k[both, 2] - k[both, 1]):.1f} us")
         np.save(os.path.join(ROOT, "gpurun_out", f"sk_stamps_{M}_{N}_{K}.npy"), us)
 hip.set_tuning("streamk", 1)
+hip.set_tuning("gemm_stamps", 0)
