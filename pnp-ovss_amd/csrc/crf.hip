@@ -1010,29 +1010,25 @@ __global__ void set_segments_kernel(const int* __restrict__ new_start, int M, in
 // ------------------------------------------------------------------------------------------ host
 static inline int ok() { return hipGetLastError() == hipSuccess ? PNP_OK : PNP_ERR_HIP; }
 
-size_t crf_sort_temp_bytes(size_t max_entries, int max_images) {
-    (void)max_images;
-    return sort_temp_bytes(max_entries) + 256;
-}
+size_t crf_sort_temp_bytes(size_t max_entries) { return sort_temp_bytes(max_entries) + 256; }
 
-// Build one lattice (D = 2: Gaussian xy/sxy ; D = 5: bilateral xy/sxy, rgb/srgb) for images [0,B).
-// Scratch arrays (keys/vals double buffers, head, incl, temp) are caller-provided.
+// Build one lattice (D = 2: Gaussian xy/sxy ; D = 5: bilateral xy/sxy, rgb/srgb) for images [0,B).  The scratch arrays and the
+// roles each of them takes in turn: CrfBuildScratch (kernels.h).
 int crf_build_lattice(int D, const CrfLattice& L, const PostDesc* d_imgs, const PostDesc* h_imgs, const uint8_t* d_rgb, float sxy, float srgb,
-                      int B, size_t ent_total, int max_pixels,
-                      uint64_t* keys_a, uint64_t* keys_b, uint32_t* vals_a, int* head, int* incl, int* n1k, int* n2k,
-                      void* temp, size_t temp_bytes, int* d_range_err, int* h_range_err, int* h_points, hipStream_t s) {
+                      int B, size_t ent_total, int max_pixels, const CrfBuildScratch& sc, int* h_range_err, int* h_points,
+                      hipStream_t s) {
     const int nb = (max_pixels + 255) / 256 < 512 ? (max_pixels + 255) / 256 : 512;
     if (D == 2)
-        hipLaunchKernelGGL((lattice_embed_kernel<2>), dim3(nb, B), dim3(256), 0, s, d_imgs, d_rgb, sxy, srgb, L.bary, keys_a, vals_a, d_range_err);
+        hipLaunchKernelGGL((lattice_embed_kernel<2>), dim3(nb, B), dim3(256), 0, s, d_imgs, d_rgb, sxy, srgb, L.bary, sc.keys_a, sc.vals_a, sc.range_err);
     else if (D == 5)
-        hipLaunchKernelGGL((lattice_embed_kernel<5>), dim3(nb, B), dim3(256), 0, s, d_imgs, d_rgb, sxy, srgb, L.bary, keys_a, vals_a, d_range_err);
+        hipLaunchKernelGGL((lattice_embed_kernel<5>), dim3(nb, B), dim3(256), 0, s, d_imgs, d_rgb, sxy, srgb, L.bary, sc.keys_a, sc.vals_a, sc.range_err);
     else
         return PNP_ERR_ARG;
     if (B > (1 << IMG_BITS)) return PNP_ERR_ARG;
     // bits actually populated: coordinates (D * BITS, low) + image index (IMG_SHIFT..)
     // stable sort by (image, coordinates).  The entries of image b are the run [pix0 * (D+1), (pix0 + H W) * (D+1)) on entry, so
     // the sort is segmented by image over the coordinate bits [0, D * BITS) alone (sort.hip; the image bits at IMG_SHIFT stay in
-    // the keys for the kernels below; the inputs keys_a / vals_a are scratch from here on)
+    // the keys for the kernels below; the inputs sc.keys_a / sc.vals_a are scratch from here on)
     const int coord_bits = D == 2 ? 2 * KeyPack<2>::BITS : 5 * KeyPack<5>::BITS;
     size_t seg_off[(1 << IMG_BITS) + 1];
     for (int b = 0; b < B; b++) {
@@ -1042,53 +1038,53 @@ int crf_build_lattice(int D, const CrfLattice& L, const PostDesc* d_imgs, const 
     seg_off[B] = ent_total;
     if (B < 1 || seg_off[0] != 0 || seg_off[B - 1] + (size_t)h_imgs[B - 1].H * h_imgs[B - 1].W * (D + 1) != ent_total) return PNP_ERR_ARG;
     {
-        const int r = radix_sort_pairs(keys_a, keys_b, vals_a, L.vals, ent_total, 0, coord_bits, seg_off, B, temp, temp_bytes, s);
+        const int r = radix_sort_pairs(sc.keys_a, sc.keys_b, sc.vals_a, L.vals, ent_total, 0, coord_bits, seg_off, B, sc.temp, sc.temp_bytes, s);
         if (r != PNP_OK) return r;
     }
     const int nbe = 1024;
-    hipLaunchKernelGGL(mark_heads_kernel, dim3(nbe, B), dim3(256), 0, s, keys_b, d_imgs, D + 1, head);
-    if (const int r = device_scan_i32(head, incl, ent_total, true, temp, temp_bytes, s); r != PNP_OK) return r;
-    hipLaunchKernelGGL(scatter_ids_kernel, dim3(nbe, B), dim3(256), 0, s, keys_b, L.vals, head, incl, d_imgs, D + 1, B,
+    hipLaunchKernelGGL(mark_heads_kernel, dim3(nbe, B), dim3(256), 0, s, sc.keys_b, d_imgs, D + 1, sc.head);
+    if (const int r = device_scan_i32(sc.head, sc.incl, ent_total, true, sc.temp, sc.temp_bytes, s); r != PNP_OK) return r;
+    hipLaunchKernelGGL(scatter_ids_kernel, dim3(nbe, B), dim3(256), 0, s, sc.keys_b, L.vals, sc.head, sc.incl, d_imgs, D + 1, B,
                        ent_total, L.offset, L.seg_start, L.ukeys, L.idbase);
     if (D == 2)
-        hipLaunchKernelGGL((neighbors_kernel<2>), dim3(nbe, B), dim3(256), 0, s, L.ukeys, L.idbase, L.cap, n1k, n2k);
+        hipLaunchKernelGGL((neighbors_kernel<2>), dim3(nbe, B), dim3(256), 0, s, L.ukeys, L.idbase, L.cap, sc.n1k, sc.n2k);
     else
-        hipLaunchKernelGGL((neighbors_kernel<5>), dim3(nbe, B), dim3(256), 0, s, L.ukeys, L.idbase, L.cap, n1k, n2k);
+        hipLaunchKernelGGL((neighbors_kernel<5>), dim3(nbe, B), dim3(256), 0, s, L.ukeys, L.idbase, L.cap, sc.n1k, sc.n2k);
     // spatial renumbering (needs the lattice size on the host: one small read-back per build)
     int M = 0;
     int h_idbase[(1 << IMG_BITS) + 1];                    // first lattice id of every image (the second sort's segments)
     // (the key-range flag of the embed kernel rides on the same synchronisation)
     int err = 0;
     if (hipMemcpyAsync(h_idbase, L.idbase, sizeof(int) * (B + 1), hipMemcpyDeviceToHost, s) != hipSuccess) return PNP_ERR_HIP;
-    if (hipMemcpyAsync(&err, d_range_err, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess) return PNP_ERR_HIP;
+    if (hipMemcpyAsync(&err, sc.range_err, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess) return PNP_ERR_HIP;
     if (hipStreamSynchronize(s) != hipSuccess) return PNP_ERR_HIP;
     M = h_idbase[B];
     if (err && h_range_err) *h_range_err = 1;
     if (M <= 0 || (size_t)M > ent_total) return PNP_ERR_STATE;
     if (h_points) *h_points = M;                          // lattice points of the batch (bench.py: lattice term of the byte model)
-    uint64_t* fkey = keys_a;
-    uint64_t* skey = keys_b;
-    uint32_t* fid = vals_a;                               // (the first sort's input: free by now)
-    uint32_t* sid = reinterpret_cast<uint32_t*>(incl);    // (rewritten by the segment scan below)
-    int* rank = head;
+    uint64_t* fkey = sc.keys_a;
+    uint64_t* skey = sc.keys_b;
+    uint32_t* fid = sc.vals_a;
+    uint32_t* sid = reinterpret_cast<uint32_t*>(sc.incl);
+    int* rank = sc.head;
     hipLaunchKernelGGL(first_contrib_kernel, dim3(1024), dim3(256), 0, s, L.vals, L.seg_start, M, d_imgs, L.idbase, B, D + 1, fkey, fid);
     {   // lattice points are numbered image by image: segmented by image over (Z-order position, vertex) = bits [0, 40)
         size_t seg2[(1 << IMG_BITS) + 1];
         for (int b = 0; b <= B; b++) seg2[b] = (size_t)h_idbase[b];
-        if (const int r = radix_sort_pairs(fkey, skey, fid, sid, (size_t)M, 0, 40, seg2, B, temp, temp_bytes, s); r != PNP_OK) return r;
+        if (const int r = radix_sort_pairs(fkey, skey, fid, sid, (size_t)M, 0, 40, seg2, B, sc.temp, sc.temp_bytes, s); r != PNP_OK) return r;
     }
     hipLaunchKernelGGL(rank_kernel, dim3(1024), dim3(256), 0, s, sid, M, rank);
-    hipLaunchKernelGGL(renumber_points_kernel, dim3(1024), dim3(256), 0, s, rank, L.seg_start, n1k, n2k, L.cap, M, D + 1,
+    hipLaunchKernelGGL(renumber_points_kernel, dim3(1024), dim3(256), 0, s, rank, L.seg_start, sc.n1k, sc.n2k, L.cap, M, D + 1,
                        L.seg_lo, L.seg_hi, L.n1, L.n2);
     hipLaunchKernelGGL(renumber_entries_kernel, dim3(2048), dim3(256), 0, s, rank, ent_total, L.offset);
     hipLaunchKernelGGL(nbr8_kernel, dim3(256, B), dim3(256), 0, s, L.n1, L.n2, L.cap, L.idbase, (D + 1) / 2, L.nbr8);
-    // contributor segments into lattice-id order (scratch: keys_a = lengths, incl = new starts, keys_b = moved list)
-    int* len = reinterpret_cast<int*>(keys_a);
-    uint32_t* vals2 = reinterpret_cast<uint32_t*>(keys_b);
+    // contributor segments into lattice-id order
+    int* len = reinterpret_cast<int*>(sc.keys_a);
+    uint32_t* vals2 = reinterpret_cast<uint32_t*>(sc.keys_b);
     hipLaunchKernelGGL(seg_len_kernel, dim3(1024), dim3(256), 0, s, L.seg_lo, L.seg_hi, M, len);
-    if (const int r = device_scan_i32(len, incl, (size_t)M, false, temp, temp_bytes, s); r != PNP_OK) return r;
-    hipLaunchKernelGGL(move_segments_kernel, dim3(4096), dim3(256), 0, s, L.vals, incl, M, D + 1, L.bary, L.seg_lo, L.seg_hi, vals2, L.ent);
-    hipLaunchKernelGGL(set_segments_kernel, dim3(1024), dim3(256), 0, s, incl, M, L.seg_lo, L.seg_hi);
+    if (const int r = device_scan_i32(len, sc.incl, (size_t)M, false, sc.temp, sc.temp_bytes, s); r != PNP_OK) return r;
+    hipLaunchKernelGGL(move_segments_kernel, dim3(4096), dim3(256), 0, s, L.vals, sc.incl, M, D + 1, L.bary, L.seg_lo, L.seg_hi, vals2, L.ent);
+    hipLaunchKernelGGL(set_segments_kernel, dim3(1024), dim3(256), 0, s, sc.incl, M, L.seg_lo, L.seg_hi);
     if (hipMemcpyAsync(L.vals, vals2, ent_total * sizeof(uint32_t), hipMemcpyDeviceToDevice, s) != hipSuccess) return PNP_ERR_HIP;
     return ok();
 }
@@ -1173,7 +1169,7 @@ int crf_filter(const CrfLattice& L, const PostDesc* d_imgs, int img0, int nimg, 
 // Q <- softmax(-U - pairwise terms) (pairwise != 0) or softmax(-U) (pairwise == 0)
 int crf_update(const CrfLattice& Lg, const CrfLattice& Lb, const PostDesc* d_imgs, int img0, int nimg, const float* vg,
                const float* vb, const float* norm_g, const float* norm_b, const float* unary, float* Q, float w_g,
-               float w_b, int pairwise, int max_pixels, int max_kp, int groups, hipStream_t s, const CrfLabelOut& labels) {
+               float w_b, int pairwise, int max_kp, int groups, hipStream_t s, const CrfLabelOut& labels) {
     // tile + per-pixel slice records; wide rows (150 classes) take fewer pixels per tile to stay inside the CU's 160 KB
     size_t tp = (size_t)(CRF_TP / (groups > 0 ? groups : 1));
     const size_t per_pixel = ((size_t)max_kp + 1 + 20) * sizeof(float);
@@ -1191,7 +1187,6 @@ int crf_update(const CrfLattice& Lg, const CrfLattice& Lb, const PostDesc* d_img
     if (smem > 64 * 1024) {
         if (hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return PNP_ERR_HIP;
     }
-    (void)max_pixels;
     // (the occupancy depends on the tile's LDS bytes: queried per distinct size, a handful per process)
     static size_t grid_smem[16];
     static int grid_dev[16], grid_nb[16], grid_wide[16], grid_n = 0;

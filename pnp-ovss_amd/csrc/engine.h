@@ -1,0 +1,249 @@
+// Internal to csrc/ (not installed, never included from include/): the engine's state and the few helpers its translation
+// units share -- engine.hip (lifetime, weights, model, introspection, operator shims) and post.hip (post-processing).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdarg>
+#include <cstdio>
+#include <map>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "../../include/pnp_hip.h"
+#include "common.h"
+#include "kernels.h"
+
+namespace pnp {
+
+struct Buf {
+    void* p = nullptr;
+    size_t bytes = 0;
+};
+
+// A GEMM weight [rows, cols] in the engine's compute mode.  bf16x3 keeps the wide Linears' weights as a (hi | lo) bf16 pair in the
+// bytes of the fp32 copy: the hi array, then the lo array.  Only this type and new_weight / fill_weight know it.
+struct Weight {
+    void* p = nullptr;
+    int rows = 0, cols = 0;
+    int esz = 0;               // bytes per stored element
+    bool pair = false;
+    void* hi(int r0 = 0) const { return (char*)p + (size_t)r0 * cols * esz; }      // row r0 on: a layer of the layer-major ck_w / cv_w
+    void* lo(int r0 = 0) const { return pair ? (char*)p + ((size_t)rows + r0) * cols * esz : nullptr; }
+};
+
+// An activation buffer of the ViT side: one array of the compute type, or in bf16x3 a (hi, lo) bf16 pair whose lo array starts
+// at the buffer's row capacity, whatever batch is in flight (alloc_act)
+struct Act {
+    void* hi = nullptr;
+    void* lo = nullptr;        // null outside bf16x3
+};
+
+struct TextLayerW {
+    // forward (T = compute dtype)
+    Weight qkv_w, so_w, cq_w, co_w, i_w, o_w;
+    float *qkv_b = nullptr, *so_b = nullptr, *sln_w = nullptr, *sln_b = nullptr, *cq_b = nullptr, *co_b = nullptr,
+          *cln_w = nullptr, *cln_b = nullptr, *i_b = nullptr, *o_b = nullptr, *oln_w = nullptr, *oln_b = nullptr;
+    // backward (transposed copies, layers >= stash_layer)
+    Weight o_wT, i_wT, co_wT, cq_wT, so_wT, qkv_wT;
+};
+
+struct TextLayerA {
+    void* qkv = nullptr;       // T [R,3H]
+    float* Ps = nullptr;       // [B,nh,L,L]
+    float *a_hat = nullptr, *a_rstd = nullptr, *a_out = nullptr;
+    void* a_outT = nullptr;
+    void* qc = nullptr;        // T [R,H]
+    float* Pc = nullptr;       // [B,nh,L,Nst]  (layers >= stash only)
+    float *c_hat = nullptr, *c_rstd = nullptr, *c_out = nullptr;
+    void* c_outT = nullptr;
+    float* u = nullptr;        // [R,I]
+    float *o_hat = nullptr, *o_rstd = nullptr, *h_out = nullptr;
+    void* h_outT = nullptr;
+};
+
+struct VitLayerW {
+    float *n1w, *n1b, *n2w, *n2b, *qkv_b, *proj_b, *fc1_b, *fc2_b;
+    Weight qkv_w, proj_w, fc1_w, fc2_w;
+};
+
+// Device allocations that hold WEIGHTS (converted GEMM weights, biases, LayerNorm parameters, embeddings): read-only once
+// finalized, so several engines of a process may use one copy (pnp_create_shared); freed with the last engine that holds it.
+struct WeightStore {
+    int device = 0;
+    std::vector<void*> allocs;
+    size_t bytes = 0;
+    ~WeightStore() {
+        (void)hipSetDevice(device);
+        for (void* p : allocs) (void)hipFree(p);
+    }
+};
+
+// One layout of the prepared batch's CRF rows: [0] one channel group per row, [1] the paired run's two (1-drop | N-drop)
+struct PostView {
+    const PostDesc* d_desc;    // device descriptors of this layout
+    int kp_max;                // widest row of the prepared batch, floats
+    int groups;
+};
+
+}  // namespace pnp
+
+struct pnp_engine {
+    pnp_config c{};
+    std::shared_ptr<pnp::WeightStore> wstore;  // owner(s) of every weight allocation below
+    bool to_store = false;                     // dalloc target: the weight store (true) or this engine's own list
+    bool shares_weights = false;               // created by pnp_create_shared: the weights belong to a donor's store
+    int bf = 0;                // 1: bf16 storage / bf16 MFMA everywhere
+    int x3 = 0;                // 1: split-bf16 ("bf16x3") ViT Linears + cross K/V projections, everything else as fp32 mode
+    size_t esz = 4;
+    int P = 0, PP = 0, N = 0, Npad = 0, D = 0, H = 0, I = 0, TL = 0, nh = 0, Nst = 0, SL = 0;
+    char err[512] = {0};
+    std::vector<void*> allocs;
+    size_t alloc_bytes = 0;
+    std::map<std::string, pnp::Buf> named;     // raw fp32 device copies of small params + test buffers
+    std::map<std::string, bool> loaded;
+    bool finalized = false;
+
+    // ---- weights
+    float *cls = nullptr, *pos = nullptr, *patch_b = nullptr, *vnorm_w = nullptr, *vnorm_b = nullptr;
+    pnp::Weight patch_w;
+    std::vector<pnp::VitLayerW> vit;
+    float *word = nullptr, *tpos = nullptr, *eln_w = nullptr, *eln_b = nullptr, *itm_w = nullptr, *itm_b = nullptr;
+    std::vector<pnp::TextLayerW> txt;
+    // optional ITC projections, [0] vision_proj (D -> E), [1] text_proj (H -> E) (B/blip_image_text_matching.py:54-55): present when
+    // the state dict carried weight and bias; E is read from the weight's first dimension
+    pnp::Weight proj_w[2];
+    float* proj_b[2] = {nullptr, nullptr};
+    int proj_E[2] = {0, 0};
+    pnp::Weight ck_w, cv_w;                    // cross K / V weights of all layers: [TL*H, D]
+    float *ck_b = nullptr, *cv_b = nullptr;    // [TL*H]
+    std::vector<pnp::Buf> staging;             // fp32 staging of GEMM weights until finalize
+
+    // ---- activations
+    int ldq = 0;               // row stride (elements) of the fused q|k|v buffer
+    float* x0 = nullptr;       // [M, D] token embeddings of drop iteration 0 (patch embed + pos, cls row): later iterations reuse them
+    // what the reusable state was computed from (embed == 1 call): an embed == 2 call that does not match recomputes instead.
+    // CONTRACT: the record catches stale POINTERS and SHAPES, not stale CONTENTS -- a caller that refills the same image / id
+    // buffers in place between an embed == 1 and an embed == 2 call gets the old embeddings (the one caller, pnp_drop_loop_layer,
+    // always starts a batch with embed == 1; pnp_vit_forward / pnp_text_forward_xattn invalidate the record)
+    struct { const float* images = nullptr; const int64_t* ids = nullptr; const int64_t* mask = nullptr; int B = 0, L = 0, ld = 0;
+             bool vit = false, text = false; } reuse;
+    void *patches = nullptr, *vt = nullptr;
+    pnp::Act xn, qk, ctx, h1, embT;
+    float *x = nullptr, *emb32 = nullptr;
+    void *Knat = nullptr, *Vnat = nullptr, *Kt = nullptr, *Vt = nullptr;
+    std::vector<pnp::TextLayerA> ta;
+    float *temb = nullptr, *h0 = nullptr, *tmp = nullptr;
+    void *h0T = nullptr, *ctx_s = nullptr, *ctx_c = nullptr, *g = nullptr;
+    // backward
+    float *dh = nullptr, *d_pre = nullptr, *dc = nullptr, *d_cpre = nullptr, *da = nullptr, *d_apre = nullptr,
+          *dctx_s = nullptr, *dS = nullptr, *dPc = nullptr;
+    void *d_preT = nullptr, *dg = nullptr, *d_cpreT = nullptr, *dctxc = nullptr, *dqc = nullptr, *d_apreT = nullptr,
+         *dqkv = nullptr;
+    int grad_layer = -1;       // text layer whose dL/dP the dPc buffer currently holds (-1: none)
+    bool acts_text_only = false;   // the text activations in place are those of pnp_text_forward_text (no cross-attention: no backward)
+    // drop loop
+    float* G = nullptr;
+    uint8_t* dropped = nullptr;
+    float* logits_scratch = nullptr;
+
+    // ---- post-process state (post.hip)
+    struct Post {
+        bool reserved = false, prepared = false, has_crf = false;
+        // -- fixed by pnp_post_reserve: bounds, capacities (elements) and the device arrays
+        int groups_cap = 1;                   // 2: the CRF arrays were sized for the paired (two-group) run
+        int maxB = 0, maxK = 0, maxKp = 0, max_pix_img = 0, chunk = 0;
+        int64_t max_total_pix = 0;
+        int lut_cap = 0, cls_cap = 0, tok_cap = 0, wts_cap = 0;
+        size_t val_cap = 0, valg_cap = 0;
+        int32_t *d_img_cls_off = nullptr, *d_cls_off = nullptr, *d_tok_idx = nullptr, *d_cls_div = nullptr, *d_lut = nullptr;
+        size_t* d_label_off = nullptr;
+        double* d_wts = nullptr;
+        int32_t* d_wt_off = nullptr;
+        float *merged = nullptr, *thr = nullptr, *maps = nullptr, *maps2 = nullptr, *maps3 = nullptr, *stats = nullptr;
+        float *unary = nullptr, *Q = nullptr, *va = nullptr, *vb = nullptr, *vga = nullptr, *vgb = nullptr, *norm[2] = {nullptr, nullptr};
+        pnp::CrfLattice lat[2]{};             // [0] Gaussian, [1] bilateral
+        pnp::CrfBuildScratch scratch{};
+        // -- the batch of the last pnp_post_prepare
+        int B = 0, Cmax = 0, Kmax = 0, maxHW = 0, maxH = 0, maxW = 0, max_radius = 0;
+        int64_t total_pix = 0;
+        int lut_stride = 0;
+        std::vector<pnp::PostDesc> desc[2];   // host copies of the two layouts; [0] is the batch's geometry for every host loop
+        pnp::PostView view[2]{};              // (d_desc and groups are fixed by reserve, kp_max is the batch's)
+        // host staging of the per-batch tables: lives in the engine until the next prepare (pageable memory: the runtime copies
+        // it into its own staging buffer at enqueue time, so rewriting it on the next call is safe without a synchronisation)
+        std::vector<size_t> h_label_off;
+        std::vector<int32_t> h_wt_off;
+        std::vector<double> h_wts;
+        const uint8_t* d_rgb = nullptr;
+        const float* d_gt = nullptr;
+        std::vector<int> gauss_sig;           // (H, W) list the Gaussian lattice was last built for
+        int range_err_host = 0;               // key-range flag of the lattices built by the last prepare
+        int lat_points[2] = {0, 0};           // lattice points of the prepared batch (Gaussian, bilateral)
+        bool maps_in_2 = false;               // where the current maps live after blur
+    } post;
+
+    pnp::GemmProfile* gemm_prof = nullptr;     // live timing ring of this engine's dense GEMM launches (allocated on first enable)
+    pnp::StreamKWs sk_ws;                      // partial tiles + flags of the in-launch reductions (split-bf16 mode: gemm_x3.hip)
+    // live timing of one pipeline stage (bench.py's hbm roofline record for the DenseCRF mean-field): event pairs
+    // on the launch stream around the stage, algorithmic bytes summed beside them
+    struct StageProfile {
+        bool on = false;
+        std::vector<hipEvent_t> ev0, ev1;
+        int used = 0;
+        long long launches = 0;
+        double work = 0;                       // SURVEY.md 8d bytes of the bracketed iterations
+        double lattice = 0;                    // lattice-blur term of the same brackets (reported separately)
+    } crf_prof;
+};
+
+namespace pnp {
+
+inline int fail(pnp_engine* e, int code, const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(e->err, sizeof(e->err), fmt, ap);
+    va_end(ap);
+    return code;
+}
+
+#define HIPCHK(e, call)                                                                      \
+    do {                                                                                     \
+        hipError_t _s = (call);                                                              \
+        if (_s != hipSuccess) return fail(e, PNP_ERR_HIP, "%s: %s", #call, hipGetErrorString(_s)); \
+    } while (0)
+#define KCHK(e, call)                                                         \
+    do {                                                                      \
+        int _r = (call);                                                      \
+        if (_r != PNP_OK) return fail(e, _r, "%s failed (%d): %s", #call, _r, hipGetErrorString(hipGetLastError())); \
+    } while (0)
+
+template <typename T>
+inline int dalloc(pnp_engine* e, T** out, size_t count, bool zero = false) {
+    void* p = nullptr;
+    const size_t bytes = (count * sizeof(T) + 255) / 256 * 256;
+    if (hipMalloc(&p, bytes ? bytes : 256) != hipSuccess) return fail(e, PNP_ERR_NOMEM, "hipMalloc(%zu) failed", bytes);
+    if (zero && hipMemset(p, 0, bytes ? bytes : 256) != hipSuccess) return fail(e, PNP_ERR_HIP, "hipMemset failed");
+    if (e->to_store && e->wstore) {
+        e->wstore->allocs.push_back(p);
+        e->wstore->bytes += bytes;
+    } else {
+        e->allocs.push_back(p);
+    }
+    e->alloc_bytes += bytes;
+    *out = reinterpret_cast<T*>(p);
+    return PNP_OK;
+}
+inline int dalloc_t(pnp_engine* e, void** out, size_t count, bool zero = false) {   // `count` elements of the compute type
+    char* p = nullptr;
+    int r = dalloc<char>(e, &p, count * e->esz, zero);
+    *out = p;
+    return r;
+}
+// a raw kernel launch: KCHK(e, launched()) right behind it
+inline int launched() { return hipPeekAtLastError() == hipSuccess ? PNP_OK : PNP_ERR_HIP; }   // (KCHK reads and clears the error)
+
+// post.hip's share of pnp_get_buffer: the post-process arrays by name (false: not one of them, or nothing reserved yet)
+bool post_get_buffer(pnp_engine* e, const std::string& name, void** d_ptr, size_t* bytes);
+
+}  // namespace pnp

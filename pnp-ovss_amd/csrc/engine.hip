@@ -1,254 +1,23 @@
 // The engine behind include/pnp_hip.h: owns weights + workspace on one MI355X, sequences the
-// hand-written kernels of this directory on the caller's stream.  Host logic only; every FLOP and
-// byte of the hot path is in the .hip kernels.  No allocation / sync inside hot-path calls.
-#include <hip/hip_runtime.h>
-
+// hand-written kernels of this directory on the caller's stream: lifetime, weights, model, introspection and the operator
+// shims (the post-processing entry points are in post.hip; the state both share is engine.h).  Host logic, but for four small
+// layout kernels (transpose_cast_kernel_f32, feat_to_tok_kernel, tok_to_feat_kernel, embed_reuse_kernel); every FLOP of the
+// hot path is in the other .hip files.  No allocation / sync inside hot-path calls.
 #include <cmath>
-#include <cstdarg>
 #include <cstring>
-#include <map>
-#include <memory>
-#include <string>
 #include <utility>
-#include <vector>
 
-#include "../../include/pnp_hip.h"
-#include "common.h"
-#include "kernels.h"
+#include "engine.h"
 
 using namespace pnp;
 
 namespace {
 
-struct Buf {
-    void* p = nullptr;
-    size_t bytes = 0;
-};
-
-// A GEMM weight [rows, cols] in the engine's compute mode.  bf16x3 keeps the wide Linears' weights as a (hi | lo) bf16 pair in the
-// bytes of the fp32 copy: the hi array, then the lo array.  Only this type and new_weight / fill_weight know it.
-struct Weight {
-    void* p = nullptr;
-    int rows = 0, cols = 0;
-    int esz = 0;               // bytes per stored element
-    bool pair = false;
-    void* hi(int r0 = 0) const { return (char*)p + (size_t)r0 * cols * esz; }      // row r0 on: a layer of the layer-major ck_w / cv_w
-    void* lo(int r0 = 0) const { return pair ? (char*)p + ((size_t)rows + r0) * cols * esz : nullptr; }
-};
-
-// An activation buffer of the ViT side: one array of the compute type, or in bf16x3 a (hi, lo) bf16 pair whose lo array starts
-// at the buffer's row capacity, whatever batch is in flight (alloc_act)
-struct Act {
-    void* hi = nullptr;
-    void* lo = nullptr;        // null outside bf16x3
-};
-
-struct TextLayerW {
-    // forward (T = compute dtype)
-    Weight qkv_w, so_w, cq_w, co_w, i_w, o_w;
-    float *qkv_b = nullptr, *so_b = nullptr, *sln_w = nullptr, *sln_b = nullptr, *cq_b = nullptr, *co_b = nullptr,
-          *cln_w = nullptr, *cln_b = nullptr, *i_b = nullptr, *o_b = nullptr, *oln_w = nullptr, *oln_b = nullptr;
-    // backward (transposed copies, layers >= stash_layer)
-    Weight o_wT, i_wT, co_wT, cq_wT, so_wT, qkv_wT;
-};
-
-struct TextLayerA {
-    void* qkv = nullptr;       // T [R,3H]
-    float* Ps = nullptr;       // [B,nh,L,L]
-    float *a_hat = nullptr, *a_rstd = nullptr, *a_out = nullptr;
-    void* a_outT = nullptr;
-    void* qc = nullptr;        // T [R,H]
-    float* Pc = nullptr;       // [B,nh,L,Nst]  (layers >= stash only)
-    float *c_hat = nullptr, *c_rstd = nullptr, *c_out = nullptr;
-    void* c_outT = nullptr;
-    float* u = nullptr;        // [R,I]
-    float *o_hat = nullptr, *o_rstd = nullptr, *h_out = nullptr;
-    void* h_outT = nullptr;
-};
-
-struct VitLayerW {
-    float *n1w, *n1b, *n2w, *n2b, *qkv_b, *proj_b, *fc1_b, *fc2_b;
-    Weight qkv_w, proj_w, fc1_w, fc2_w;
-};
-
-// Device allocations that hold WEIGHTS (converted GEMM weights, biases, LayerNorm parameters, embeddings): read-only once
-// finalized, so several engines of a process may use one copy (pnp_create_shared); freed with the last engine that holds it.
-struct WeightStore {
-    int device = 0;
-    std::vector<void*> allocs;
-    size_t bytes = 0;
-    ~WeightStore() {
-        (void)hipSetDevice(device);
-        for (void* p : allocs) (void)hipFree(p);
-    }
-};
-
-}  // namespace
-
-struct pnp_engine {
-    pnp_config c{};
-    std::shared_ptr<WeightStore> wstore;       // owner(s) of every weight allocation below
-    bool to_store = false;                     // dalloc target: the weight store (true) or this engine's own list
-    bool shares_weights = false;               // created by pnp_create_shared: the weights belong to a donor's store
-    int bf = 0;                // 1: bf16 storage / bf16 MFMA everywhere
-    int x3 = 0;                // 1: split-bf16 ("bf16x3") ViT Linears + cross K/V projections, everything else as fp32 mode
-    size_t esz = 4;
-    int P = 0, PP = 0, N = 0, Npad = 0, D = 0, H = 0, I = 0, TL = 0, nh = 0, Nst = 0, SL = 0;
-    char err[512] = {0};
-    std::vector<void*> allocs;
-    size_t alloc_bytes = 0;
-    std::map<std::string, Buf> named;          // raw fp32 device copies of small params + test buffers
-    std::map<std::string, bool> loaded;
-    bool finalized = false;
-
-    // ---- weights
-    float *cls = nullptr, *pos = nullptr, *patch_b = nullptr, *vnorm_w = nullptr, *vnorm_b = nullptr;
-    Weight patch_w;
-    std::vector<VitLayerW> vit;
-    float *word = nullptr, *tpos = nullptr, *eln_w = nullptr, *eln_b = nullptr, *itm_w = nullptr, *itm_b = nullptr;
-    std::vector<TextLayerW> txt;
-    // optional ITC projections, [0] vision_proj (D -> E), [1] text_proj (H -> E) (B/blip_image_text_matching.py:54-55): present when
-    // the state dict carried weight and bias; E is read from the weight's first dimension
-    Weight proj_w[2];
-    float* proj_b[2] = {nullptr, nullptr};
-    int proj_E[2] = {0, 0};
-    Weight ck_w, cv_w;                         // cross K / V weights of all layers: [TL*H, D]
-    float *ck_b = nullptr, *cv_b = nullptr;    // [TL*H]
-    std::vector<Buf> staging;                  // fp32 staging of GEMM weights until finalize
-
-    // ---- activations
-    int ldq = 0;               // row stride (elements) of the fused q|k|v buffer
-    float* x0 = nullptr;       // [M, D] token embeddings of drop iteration 0 (patch embed + pos, cls row): later iterations reuse them
-    // what the reusable state was computed from (embed == 1 call): an embed == 2 call that does not match recomputes instead.
-    // CONTRACT: the record catches stale POINTERS and SHAPES, not stale CONTENTS -- a caller that refills the same image / id
-    // buffers in place between an embed == 1 and an embed == 2 call gets the old embeddings (the one caller, pnp_drop_loop_layer,
-    // always starts a batch with embed == 1; pnp_vit_forward / pnp_text_forward_xattn invalidate the record)
-    struct { const float* images = nullptr; const int64_t* ids = nullptr; const int64_t* mask = nullptr; int B = 0, L = 0, ld = 0;
-             bool vit = false, text = false; } reuse;
-    void *patches = nullptr, *vt = nullptr;
-    Act xn, qk, ctx, h1, embT;
-    float *x = nullptr, *emb32 = nullptr;
-    void *Knat = nullptr, *Vnat = nullptr, *Kt = nullptr, *Vt = nullptr;
-    std::vector<TextLayerA> ta;
-    float *temb = nullptr, *h0 = nullptr, *tmp = nullptr;
-    void *h0T = nullptr, *ctx_s = nullptr, *ctx_c = nullptr, *g = nullptr;
-    // backward
-    float *dh = nullptr, *d_pre = nullptr, *dc = nullptr, *d_cpre = nullptr, *da = nullptr, *d_apre = nullptr,
-          *dctx_s = nullptr, *dS = nullptr, *dPc = nullptr;
-    void *d_preT = nullptr, *dg = nullptr, *d_cpreT = nullptr, *dctxc = nullptr, *dqc = nullptr, *d_apreT = nullptr,
-         *dqkv = nullptr;
-    int grad_layer = -1;       // text layer whose dL/dP the dPc buffer currently holds (-1: none)
-    bool acts_text_only = false;   // the text activations in place are those of pnp_text_forward_text (no cross-attention: no backward)
-    // drop loop
-    float* G = nullptr;
-    uint8_t* dropped = nullptr;
-    float* logits_scratch = nullptr;
-
-    // ---- post-process state
-    struct Post {
-        bool reserved = false, prepared = false, has_crf = false;
-        int groups_cap = 1;                   // 2: the CRF arrays were sized for the paired (two-group) run
-        int maxB = 0, maxK = 0, max_pix_img = 0, chunk = 0;
-        int64_t max_total_pix = 0;
-        int B = 0, Cmax = 0, Kmax = 0, maxHW = 0;
-        int64_t total_pix = 0;
-        std::vector<PostDesc> desc, desc_pair;
-        PostDesc* d_desc = nullptr;
-        PostDesc* d_desc_pair = nullptr;      // same batch with two channel groups per row (1-drop | N-drop)
-        int32_t *d_img_cls_off = nullptr, *d_cls_off = nullptr, *d_tok_idx = nullptr, *d_cls_div = nullptr, *d_lut = nullptr;
-        int lut_stride = 0;
-        size_t* d_label_off = nullptr;
-        double* d_wts = nullptr;
-        int32_t* d_wt_off = nullptr;
-        float *merged = nullptr, *thr = nullptr, *maps = nullptr, *maps2 = nullptr, *maps3 = nullptr, *stats = nullptr;
-        float *unary = nullptr, *Q = nullptr, *va = nullptr, *vb = nullptr, *vga = nullptr, *vgb = nullptr, *norm[2] = {nullptr, nullptr};
-        int Kpmax = 0, Kpmax_pair = 0, maxH = 0, maxW = 0, max_radius = 0, maxKp = 0;
-        size_t valg_cap = 0;
-        std::vector<int> gauss_sig;      // (H, W) list the Gaussian lattice was last built for
-        const uint8_t* d_rgb = nullptr;
-        const float* d_gt = nullptr;
-        CrfLattice lat[2]{};
-        uint64_t *keys_a = nullptr, *keys_b = nullptr;
-        uint32_t* vals_a = nullptr;
-        int *n1k = nullptr, *n2k = nullptr;
-        int *head = nullptr, *incl = nullptr, *range_err = nullptr;
-        int range_err_host = 0;                // key-range flag of the lattices built by the last prepare
-        int lat_points[2] = {0, 0};            // lattice points of the prepared batch (Gaussian, bilateral)
-        std::vector<size_t> h_label_off;       // host staging of the per-batch tables (see pnp_post_prepare)
-        std::vector<int32_t> h_wt_off;
-        std::vector<double> h_wts;
-        void* sort_tmp = nullptr;
-        size_t sort_tmp_bytes = 0;
-        size_t cap[2] = {0, 0};
-        size_t val_cap = 0;
-        int lut_cap = 0, cls_cap = 0, tok_cap = 0, wts_cap = 0;
-        bool maps_in_2 = false;   // where the current maps live after blur
-    } post;
-
-    GemmProfile* gemm_prof = nullptr;          // live timing ring of this engine's dense GEMM launches (allocated on first enable)
-    StreamKWs sk_ws;                           // partial tiles + flags of the in-launch reductions (split-bf16 mode: gemm_x3.hip)
-    // live timing of one pipeline stage (bench.py's hbm roofline record for the DenseCRF mean-field): event pairs
-    // on the launch stream around the stage, algorithmic bytes summed beside them
-    struct StageProfile {
-        bool on = false;
-        std::vector<hipEvent_t> ev0, ev1;
-        int used = 0;
-        long long launches = 0;
-        double work = 0;                       // SURVEY.md 8d bytes of the bracketed iterations
-        double lattice = 0;                    // lattice-blur term of the same brackets (reported separately)
-    } crf_prof;
-};
-
-namespace {
-
-int fail(pnp_engine* e, int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(e->err, sizeof(e->err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-#define HIPCHK(e, call)                                                                      \
-    do {                                                                                     \
-        hipError_t _s = (call);                                                              \
-        if (_s != hipSuccess) return fail(e, PNP_ERR_HIP, "%s: %s", #call, hipGetErrorString(_s)); \
-    } while (0)
-#define KCHK(e, call)                                                         \
-    do {                                                                      \
-        int _r = (call);                                                      \
-        if (_r != PNP_OK) return fail(e, _r, "%s failed (%d): %s", #call, _r, hipGetErrorString(hipGetLastError())); \
-    } while (0)
-
-template <typename T>
-int dalloc(pnp_engine* e, T** out, size_t count, bool zero = false) {
-    void* p = nullptr;
-    const size_t bytes = (count * sizeof(T) + 255) / 256 * 256;
-    if (hipMalloc(&p, bytes ? bytes : 256) != hipSuccess) return fail(e, PNP_ERR_NOMEM, "hipMalloc(%zu) failed", bytes);
-    if (zero && hipMemset(p, 0, bytes ? bytes : 256) != hipSuccess) return fail(e, PNP_ERR_HIP, "hipMemset failed");
-    if (e->to_store && e->wstore) {
-        e->wstore->allocs.push_back(p);
-        e->wstore->bytes += bytes;
-    } else {
-        e->allocs.push_back(p);
-    }
-    e->alloc_bytes += bytes;
-    *out = reinterpret_cast<T*>(p);
-    return PNP_OK;
-}
-int dalloc_t(pnp_engine* e, void** out, size_t count, bool zero = false) {   // `count` elements of the compute type
-    char* p = nullptr;
-    int r = dalloc<char>(e, &p, count * e->esz, zero);
-    *out = p;
-    return r;
-}
 int alloc_act(pnp_engine* e, Act* a, size_t rows, size_t ld) {   // the pair's two bf16 arrays fill the bytes of the fp32 rows
     KCHK(e, dalloc_t(e, &a->hi, rows * ld));
     a->lo = e->x3 ? (char*)a->hi + rows * ld * 2 : nullptr;
     return PNP_OK;
 }
-// a raw kernel launch: KCHK(e, launched()) right behind it
-int launched() { return hipPeekAtLastError() == hipSuccess ? PNP_OK : PNP_ERR_HIP; }   // (KCHK reads and clears the error)
 
 bool ends_with(const std::string& s, const char* suf) {
     const size_t n = strlen(suf);
@@ -1290,443 +1059,12 @@ extern "C" int pnp_drop_loop_layer(pnp_engine* e, const float* d_images, const i
     return PNP_OK;
 }
 
-// =========================================================================================== post-process
-
-extern "C" int pnp_post_reserve(pnp_engine* e, int32_t max_batch, int64_t max_total_pixels, int32_t max_pixels_per_image,
-                                int32_t max_channels, int32_t crf_chunk) {
-    if (!e) return PNP_ERR_ARG;
-    if (e->post.reserved) return fail(e, PNP_ERR_STATE, "post-process workspace already reserved");
-    if (max_batch <= 0 || max_batch > 64 || max_total_pixels <= 0 || max_pixels_per_image <= 0 || max_channels <= 0 ||
-        max_channels > 255)
-        return fail(e, PNP_ERR_ARG, "bad post-process bounds (at most 64 images per batch, 255 channels)");
-    HIPCHK(e, hipSetDevice(e->c.device));
-    auto& p = e->post;
-    p.maxB = max_batch;
-    p.max_total_pix = max_total_pixels;
-    p.max_pix_img = max_pixels_per_image;
-    p.maxK = max_channels;
-    p.chunk = crf_chunk > 0 ? crf_chunk : max_batch;
-    const size_t TP = (size_t)max_total_pixels, K = max_channels, B = max_batch;
-    KCHK(e, dalloc(e, &p.d_desc, B));
-    KCHK(e, dalloc(e, &p.d_desc_pair, B));
-    KCHK(e, dalloc(e, &p.d_img_cls_off, B + 1));
-    p.cls_cap = (int)(B * K + 1);
-    p.tok_cap = (int)(B * e->c.max_text_len + 1);
-    KCHK(e, dalloc(e, &p.d_cls_off, p.cls_cap + 1));
-    KCHK(e, dalloc(e, &p.d_cls_div, p.cls_cap));
-    KCHK(e, dalloc(e, &p.d_tok_idx, p.tok_cap));
-    p.lut_cap = (int)(B * (K + 1));
-    KCHK(e, dalloc(e, &p.d_lut, p.lut_cap));
-    KCHK(e, dalloc(e, &p.d_label_off, B + 1));
-    p.wts_cap = (int)(B * 4096);
-    KCHK(e, dalloc(e, &p.d_wts, p.wts_cap));
-    KCHK(e, dalloc(e, &p.d_wt_off, B + 1));
-    KCHK(e, dalloc(e, &p.merged, B * K * e->PP));
-    KCHK(e, dalloc(e, &p.thr, B * K * e->PP));
-    KCHK(e, dalloc(e, &p.maps, TP * K));
-    KCHK(e, dalloc(e, &p.maps2, TP * K));
-    KCHK(e, dalloc(e, &p.maps3, TP * K));
-    KCHK(e, dalloc(e, &p.stats, B * K * 2));
-    // CRF
-    const size_t Kp = (K + 3) / 4 * 4;
-    p.maxKp = (int)Kp;
-    // the paired 1-drop | N-drop run keeps two channel groups per row: size the CRF arrays for it unless that would
-    // take more than a third of the free device memory (many classes x large images); pnp_postprocess_pair then runs
-    // the two branches one after the other
-    {
-        const size_t chunk_pix0 = (size_t)std::min<int64_t>((int64_t)(crf_chunk > 0 ? crf_chunk : B) * max_pixels_per_image, max_total_pixels);
-        const size_t single = (2 * TP * Kp + 2 * chunk_pix0 * 6 * Kp + 2 * chunk_pix0 * 3 * Kp) * sizeof(float);
-        // ... of what the device has free right now (the rest of this function needs about as much again for maps and lattices)
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = (size_t)96 << 30;
-        p.groups_cap = 2 * single <= free_b / 3 ? 2 : 1;
-    }
-    const size_t G2 = (size_t)p.groups_cap;
-    KCHK(e, dalloc(e, &p.unary, TP * Kp * G2));
-    KCHK(e, dalloc(e, &p.Q, TP * Kp * G2));
-    KCHK(e, dalloc(e, &p.norm[0], TP));
-    KCHK(e, dalloc(e, &p.norm[1], TP));
-    for (int t = 0; t < 2; t++) {
-        const int D1 = t == 0 ? 3 : 6;
-        const size_t cap = TP * D1;
-        p.cap[t] = cap;
-        CrfLattice& L = p.lat[t];
-        L.D1 = D1;
-        L.which = t;
-        L.cap = cap;
-        KCHK(e, dalloc(e, &L.bary, cap));
-        KCHK(e, dalloc(e, &L.vals, cap));
-        KCHK(e, dalloc(e, &L.ent, cap));
-        KCHK(e, dalloc(e, &L.offset, cap));
-        KCHK(e, dalloc(e, &L.seg_start, cap + 1));
-        KCHK(e, dalloc(e, &L.seg_lo, cap));
-        KCHK(e, dalloc(e, &L.seg_hi, cap));
-        KCHK(e, dalloc(e, &L.ukeys, cap));
-        KCHK(e, dalloc(e, &L.idbase, B + 1));
-        KCHK(e, dalloc(e, &L.n1, cap * D1));
-        KCHK(e, dalloc(e, &L.n2, cap * D1));
-        KCHK(e, dalloc(e, &L.nbr8, cap * (D1 / 2)));
-    }
-    const size_t cap6 = p.cap[1];
-    KCHK(e, dalloc(e, &p.keys_a, cap6));
-    KCHK(e, dalloc(e, &p.keys_b, cap6));
-    KCHK(e, dalloc(e, &p.vals_a, cap6));
-    KCHK(e, dalloc(e, &p.head, cap6));
-    KCHK(e, dalloc(e, &p.incl, cap6));
-    KCHK(e, dalloc(e, &p.n1k, cap6 * 6));
-    KCHK(e, dalloc(e, &p.n2k, cap6 * 6));
-    KCHK(e, dalloc(e, &p.range_err, 1, true));
-    p.sort_tmp_bytes = crf_sort_temp_bytes(cap6, max_batch);
-    char* st = nullptr;
-    KCHK(e, dalloc(e, &st, p.sort_tmp_bytes));
-    p.sort_tmp = st;
-    // lattice value buffers: the images of one chunk, bilateral upper bound (6 entries per pixel) x K
-    const size_t chunk_pix = (size_t)std::min<int64_t>((int64_t)p.chunk * max_pixels_per_image, max_total_pixels);
-    p.val_cap = std::max(chunk_pix * 6 * Kp * G2, cap6);
-    KCHK(e, dalloc(e, &p.va, p.val_cap));
-    KCHK(e, dalloc(e, &p.vb, p.val_cap));
-    p.valg_cap = chunk_pix * 3 * Kp * G2;
-    KCHK(e, dalloc(e, &p.vga, p.valg_cap));
-    KCHK(e, dalloc(e, &p.vgb, p.valg_cap));
-    p.reserved = true;
-    return PNP_OK;
-}
-
-extern "C" int pnp_post_prepare(pnp_engine* e, const pnp_post_batch* b, int32_t want_crf, void* stream) {
-    if (!e || !b) return PNP_ERR_ARG;
-    auto& p = e->post;
-    if (!p.reserved) return fail(e, PNP_ERR_STATE, "call pnp_post_reserve first");
-    if (b->B <= 0 || b->B > p.maxB) return fail(e, PNP_ERR_ARG, "post batch %d out of range", b->B);
-    if (!b->H || !b->W || !b->n_classes || !b->has_bg || !b->img_cls_off || !b->cls_off || !b->tok_idx || !b->cls_div || !b->lut)
-        return fail(e, PNP_ERR_ARG, "post batch has null tables");
-    if (want_crf && !b->d_rgb) return fail(e, PNP_ERR_ARG, "CRF needs d_rgb");
-    hipStream_t s = (hipStream_t)stream;
-    const int B = b->B;
-    p.prepared = false;
-    p.desc.assign(B, PostDesc{});
-    // host staging of the small tables lives in the engine until the next prepare (pageable memory: the runtime copies it
-    // into its own staging buffer at enqueue time, so rewriting it on the next call is safe without a synchronisation)
-    std::vector<size_t>& label_off = p.h_label_off;
-    std::vector<int32_t>& wt_off = p.h_wt_off;
-    std::vector<double>& wts = p.h_wts;
-    label_off.assign(B + 1, 0);
-    wt_off.assign(B + 1, 0);
-    wts.clear();
-    size_t off = 0, qoff = 0;
-    int64_t pix = 0;
-    p.Cmax = p.Kmax = p.maxHW = p.Kpmax = p.maxH = p.maxW = p.max_radius = 0;
-    for (int i = 0; i < B; i++) {
-        PostDesc& d = p.desc[i];
-        d.H = b->H[i]; d.W = b->W[i]; d.C = b->n_classes[i]; d.has_bg = b->has_bg[i] ? 1 : 0; d.K = d.C + d.has_bg;
-        if (d.H <= 0 || d.W <= 0 || d.C <= 0 || d.K > p.maxK) return fail(e, PNP_ERR_ARG, "image %d: bad H/W/classes (K=%d max %d)", i, d.K, p.maxK);
-        if ((int64_t)d.H * d.W > p.max_pix_img) return fail(e, PNP_ERR_ARG, "image %d: %dx%d exceeds max_pixels_per_image", i, d.H, d.W);
-        if (b->img_cls_off[i + 1] - b->img_cls_off[i] != d.C) return fail(e, PNP_ERR_ARG, "image %d: merge plan has %d classes, expected %d", i, b->img_cls_off[i + 1] - b->img_cls_off[i], d.C);
-        d.pix0 = (int)pix;
-        d.off = off;
-        d.Kp = (d.K + 3) / 4 * 4;
-        d.G = 1;
-        d.Kg = d.K;
-        d.qoff = qoff;
-        label_off[i] = (size_t)pix;
-        off += (size_t)d.K * d.H * d.W;
-        qoff += (size_t)d.Kp * d.H * d.W;
-        p.Kpmax = std::max(p.Kpmax, d.Kp);
-        p.maxH = std::max(p.maxH, d.H);
-        p.maxW = std::max(p.maxW, d.W);
-        pix += (int64_t)d.H * d.W;
-        p.Cmax = std::max(p.Cmax, d.C);
-        p.Kmax = std::max(p.Kmax, d.K);
-        p.maxHW = std::max(p.maxHW, d.H * d.W);
-        // scipy _gaussian_kernel1d(sigma = 0.05 * max(H, W)), truncate 4.0  (PnP.py:1150, scale=0.05)
-        const double sigma = 0.05 * (double)std::max(d.H, d.W);
-        const int radius = (int)(4.0 * sigma + 0.5);
-        std::vector<double> phi(2 * radius + 1);
-        double sum = 0;
-        for (int x = -radius; x <= radius; x++) {
-            phi[x + radius] = std::exp(-0.5 / (sigma * sigma) * (double)(x * x));
-            sum += phi[x + radius];
-        }
-        p.max_radius = std::max(p.max_radius, (b->blur_wts && b->blur_wt_off) ? b->blur_wt_off[i + 1] - b->blur_wt_off[i] - 1 : radius);
-        wt_off[i] = (int32_t)wts.size();
-        if (b->blur_wts && b->blur_wt_off) {
-            for (int j = b->blur_wt_off[i]; j < b->blur_wt_off[i + 1]; j++) wts.push_back(b->blur_wts[j]);
-        } else {
-            for (int j = 0; j <= radius; j++) wts.push_back(phi[radius - j] / sum);   // weight at distance j (w[-j] == w[j])
-        }
-    }
-    wt_off[B] = (int32_t)wts.size();
-    label_off[B] = (size_t)pix;
-    if (pix > p.max_total_pix) return fail(e, PNP_ERR_ARG, "batch has %lld pixels, reserved %lld", (long long)pix, (long long)p.max_total_pix);
-    if ((int)wts.size() > p.wts_cap) return fail(e, PNP_ERR_ARG, "blur taps exceed reserved capacity");
-    const int ncls = b->img_cls_off[B], ntok = b->cls_off[ncls];
-    if (ncls > p.cls_cap || ntok > p.tok_cap) return fail(e, PNP_ERR_ARG, "merge plan exceeds reserved capacity");
-    if (b->lut_stride < p.Kmax || B * b->lut_stride > p.lut_cap) return fail(e, PNP_ERR_ARG, "bad lut_stride");
-    // lattice value offsets per chunk (upper bound: entries * K)
-    // the paired run (two channel groups per row, 1-drop | N-drop) packs the groups back to back: rows of
-    // 4 * ceil(2 K / 4) floats (K = 21: 44 instead of 2 x 24), its own row-strided offsets
-    std::vector<size_t> voff_pair(2 * (size_t)B, 0);
-    for (int c0 = 0; c0 < B; c0 += p.chunk) {
-        size_t v[2] = {0, 0}, v2[2] = {0, 0};
-        for (int i = c0; i < std::min(B, c0 + p.chunk); i++)
-            for (int t = 0; t < 2; t++) {
-                p.desc[i].voff[t] = v[t];
-                v[t] += (size_t)p.desc[i].H * p.desc[i].W * (t == 0 ? 3 : 6) * p.desc[i].Kp;
-                voff_pair[2 * (size_t)i + t] = v2[t];
-                v2[t] += (size_t)p.desc[i].H * p.desc[i].W * (t == 0 ? 3 : 6) * ((2 * p.desc[i].K + 3) / 4 * 4);
-            }
-        if (p.groups_cap * v[1] > p.val_cap || p.groups_cap * v[0] > p.valg_cap)     // incl. room for the paired run
-            return fail(e, PNP_ERR_ARG, "CRF chunk needs %zu value floats, reserved %zu", p.groups_cap * v[1], p.val_cap);
-    }
-    p.B = B;
-    p.total_pix = pix;
-    p.lut_stride = b->lut_stride;
-    p.d_rgb = b->d_rgb;
-    p.d_gt = b->d_gt;
-    HIPCHK(e, hipMemcpyAsync(p.d_desc, p.desc.data(), sizeof(PostDesc) * B, hipMemcpyHostToDevice, s));
-    p.desc_pair = p.desc;
-    p.Kpmax_pair = 0;
-    {
-        size_t qoff2 = 0;
-        for (int i = 0; i < B; i++) {          // rows of two groups
-            PostDesc& d = p.desc_pair[i];
-            d.G = 2;
-            d.Kp = (2 * d.K + 3) / 4 * 4;
-            d.qoff = qoff2;
-            qoff2 += (size_t)d.Kp * d.H * d.W;
-            d.voff[0] = voff_pair[2 * (size_t)i];
-            d.voff[1] = voff_pair[2 * (size_t)i + 1];
-            p.Kpmax_pair = std::max(p.Kpmax_pair, d.Kp);
-        }
-    }
-    HIPCHK(e, hipMemcpyAsync(p.d_desc_pair, p.desc_pair.data(), sizeof(PostDesc) * B, hipMemcpyHostToDevice, s));
-    HIPCHK(e, hipMemcpyAsync(p.d_img_cls_off, b->img_cls_off, 4 * (B + 1), hipMemcpyHostToDevice, s));
-    HIPCHK(e, hipMemcpyAsync(p.d_cls_off, b->cls_off, 4 * (ncls + 1), hipMemcpyHostToDevice, s));
-    HIPCHK(e, hipMemcpyAsync(p.d_cls_div, b->cls_div, 4 * std::max(ncls, 1), hipMemcpyHostToDevice, s));
-    HIPCHK(e, hipMemcpyAsync(p.d_tok_idx, b->tok_idx, 4 * std::max(ntok, 1), hipMemcpyHostToDevice, s));
-    HIPCHK(e, hipMemcpyAsync(p.d_lut, b->lut, 4 * (size_t)B * b->lut_stride, hipMemcpyHostToDevice, s));
-    HIPCHK(e, hipMemcpyAsync(p.d_label_off, label_off.data(), sizeof(size_t) * (B + 1), hipMemcpyHostToDevice, s));
-    HIPCHK(e, hipMemcpyAsync(p.d_wts, wts.data(), 8 * wts.size(), hipMemcpyHostToDevice, s));
-    HIPCHK(e, hipMemcpyAsync(p.d_wt_off, wt_off.data(), 4 * (B + 1), hipMemcpyHostToDevice, s));
-    p.has_crf = false;
-    // the table copies above read caller / engine host memory asynchronously: they are complete behind the lattice build's own
-    // read-back (one synchronisation per batch, inside crf_build_lattice); without a lattice to build, wait here
-    bool synced = false;
-    if (want_crf) {
-        // PnP.py:1036-1041: POS_XY_STD = 3, Bi_XY_STD = 50, Bi_RGB_STD = 5 (features are fixed per batch)
-        std::vector<int> sig;
-        for (int i = 0; i < B; i++) { sig.push_back(p.desc[i].H); sig.push_back(p.desc[i].W); }
-        for (int t = 0; t < 2; t++) {
-            // the Gaussian (xy-only) lattice depends on the image sizes alone: keep it across batches
-            if (t == 0 && sig == p.gauss_sig) continue;
-            const int D1 = t == 0 ? 3 : 6;
-            KCHK(e, crf_build_lattice(D1 - 1, p.lat[t], p.d_desc, p.desc.data(), p.d_rgb, t == 0 ? 3.0f : 50.0f, 5.0f, B, (size_t)pix * D1,
-                                      p.maxHW, p.keys_a, p.keys_b, p.vals_a, p.head, p.incl,
-                                      p.n1k, p.n2k, p.sort_tmp, p.sort_tmp_bytes, p.range_err, &p.range_err_host, &p.lat_points[t], s));
-            KCHK(e, crf_lattice_norm(p.lat[t], p.d_desc, B, p.maxHW, (size_t)pix * D1, p.va, p.vb, p.norm[t], s));
-            synced = true;
-        }
-        if (p.range_err_host) {                // (read back with the lattice size inside crf_build_lattice: no extra sync)
-            p.range_err_host = 0;                           // leave no stale state behind: the next prepare rebuilds both lattices
-            p.gauss_sig.clear();
-            (void)hipMemsetAsync(p.range_err, 0, 4, s);
-            return fail(e, PNP_ERR_ARG, "lattice key out of packing range (image too large for the 64-bit key)");
-        }
-        p.gauss_sig = sig;
-        p.has_crf = true;
-    }
-    if (!synced) HIPCHK(e, hipStreamSynchronize(s));
-    p.prepared = true;
-    return PNP_OK;
-}
-
-#define POST_READY(e)                                                                     \
-    if (!(e)) return PNP_ERR_ARG;                                                         \
-    if (!(e)->post.prepared) return fail(e, PNP_ERR_STATE, "call pnp_post_prepare first");
-
-extern "C" int pnp_merge_tokens(pnp_engine* e, const float* d_gradcam, int32_t T, void* stream) {
-    POST_READY(e);
-    auto& p = e->post;
-    if (!d_gradcam || T < 5) return fail(e, PNP_ERR_ARG, "bad gradcam / T");
-    KCHK(e, merge_tokens(d_gradcam, p.d_cls_off, p.d_tok_idx, p.d_cls_div, p.d_img_cls_off, p.merged, p.B, T, e->PP, p.Cmax,
-                         (hipStream_t)stream));
-    return PNP_OK;
-}
-
-extern "C" int pnp_threshold_upsample(pnp_engine* e, float threshold, int32_t scale01, void* stream) {
-    POST_READY(e);
-    auto& p = e->post;
-    hipStream_t s = (hipStream_t)stream;
-    KCHK(e, threshold_maps(p.merged, p.d_img_cls_off, p.thr, threshold, p.B, e->PP, p.Cmax, s));
-    KCHK(e, upsample_maps(p.thr, p.d_desc, p.maps, p.B, e->P, p.Cmax, p.maxHW, s));
-    if (scale01) KCHK(e, minmax_normalize(p.maps, p.d_desc, p.stats, p.B, p.Cmax, p.maxHW, 1, s));
-    KCHK(e, background_channel(p.maps, p.d_desc, p.B, p.maxHW, s));
-    p.maps_in_2 = false;
-    return PNP_OK;
-}
-
-extern "C" int pnp_blur_minmax(pnp_engine* e, void* stream) {
-    POST_READY(e);
-    auto& p = e->post;
-    hipStream_t s = (hipStream_t)stream;
-    KCHK(e, blur_maps(p.maps, p.maps3, p.maps2, p.d_desc, p.d_wts, p.d_wt_off, p.B, p.Kmax, p.maxH, p.maxW, p.max_radius, s));
-    KCHK(e, minmax_normalize(p.maps2, p.d_desc, p.stats, p.B, p.Kmax, p.maxHW, 0, s));
-    p.maps_in_2 = true;
-    return PNP_OK;
-}
-
-// mean-field iterations over the unary rows already in p.unary; desc = single- or two-group descriptors
-static int crf_iterate_body(pnp_engine* e, const PostDesc* desc, int kp_max, int32_t iters, float pos_w, float bi_w, hipStream_t s,
-                            const CrfLabelOut& labels);
-
-// labels: when set, the last update also writes the label maps (argmax + LUT fused into it: no separate pass over Q)
-static int crf_iterate(pnp_engine* e, const PostDesc* desc, int kp_max, int32_t iters, float pos_w, float bi_w, hipStream_t s,
-                       const CrfLabelOut& labels = CrfLabelOut()) {
-    auto& pf = e->crf_prof;
-    const bool timed = pf.on && pf.used < 4096;
-    if (timed) {
-        if ((int)pf.ev0.size() <= pf.used) {
-            hipEvent_t a, b;
-            if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) return fail(e, PNP_ERR_HIP, "hipEventCreate failed");
-            pf.ev0.push_back(a);
-            pf.ev1.push_back(b);
-        }
-        (void)hipEventRecord(pf.ev0[pf.used], s);
-    }
-    const int r = crf_iterate_body(e, desc, kp_max, iters, pos_w, bi_w, s, labels);
-    if (timed) {
-        (void)hipEventRecord(pf.ev1[pf.used], s);
-        pf.used++;
-        pf.launches++;
-        // `work` = SURVEY.md 8d, nothing else: per mean-field iteration splat + slice of (3 + 6) simplex vertices per pixel and
-        // channel, each a 4-byte read or write, plus Q read and written once: (2 * 9 + 2) * K * H * W * 4 bytes.  The term that grows
-        // with the lattice instead of the pixels is kept BESIDE it (`lattice`, stage 2 of pnp_profile_read_stage): the axis blurs
-        // read and write the value array of every lattice point (M_g + M_b points of K floats) once per PASS of two axes -- 2 passes
-        // for the Gaussian lattice (d + 1 = 3 axes), 3 for the bilateral one (6 axes).  Neither figure is what the HBM counters
-        // see (part of both is served by L2: the kernels are gather-bound)
-        const auto& p = e->post;
-        const int groups = desc == p.d_desc_pair ? 2 : 1;
-        double kpix = 0, pix = 0;
-        for (int i = 0; i < p.B; i++) {
-            kpix += (double)p.desc[i].K * p.desc[i].H * p.desc[i].W;
-            pix += (double)p.desc[i].H * p.desc[i].W;
-        }
-        const double kavg = pix > 0 ? kpix / pix : 0;
-        pf.work += (double)iters * 20.0 * 4.0 * groups * kpix;
-        pf.lattice += (double)iters * 2.0 * 4.0 * groups * kavg * (2.0 * p.lat_points[0] + 3.0 * p.lat_points[1]);
-    }
-    return r;
-}
-
-static int crf_iterate_body(pnp_engine* e, const PostDesc* desc, int kp_max, int32_t iters, float pos_w, float bi_w, hipStream_t s,
-                            const CrfLabelOut& labels) {
-    auto& p = e->post;
-    const int groups = desc == p.d_desc_pair ? 2 : 1;
-    for (int c0 = 0; c0 < p.B; c0 += p.chunk) {
-        const int n = std::min(p.chunk, p.B - c0);
-        KCHK(e, crf_update(p.lat[0], p.lat[1], desc, c0, n, p.vga, p.va, p.norm[0], p.norm[1], p.unary, p.Q, pos_w, bi_w, 0,
-                           p.maxHW, kp_max, groups, s));
-        for (int it = 0; it < iters; it++) {
-            const float *rg = nullptr, *rb = nullptr;
-            KCHK(e, crf_filter(p.lat[0], desc, c0, n, p.Q, p.vga, p.vgb, &rg, kp_max, s));
-            KCHK(e, crf_filter(p.lat[1], desc, c0, n, p.Q, p.va, p.vb, &rb, kp_max, s));
-            KCHK(e, crf_update(p.lat[0], p.lat[1], desc, c0, n, rg, rb, p.norm[0], p.norm[1], p.unary, p.Q, pos_w, bi_w, 1,
-                               p.maxHW, kp_max, groups, s, it == iters - 1 ? labels : CrfLabelOut()));
-        }
-    }
-    return PNP_OK;
-}
-
-extern "C" int pnp_densecrf(pnp_engine* e, int32_t iters, float pos_w, float pos_xy, float bi_w, float bi_xy, float bi_rgb,
-                            void* stream) {
-    POST_READY(e);
-    auto& p = e->post;
-    if (!p.has_crf) return fail(e, PNP_ERR_STATE, "batch was prepared without CRF lattices");
-    if (pos_xy != 3.0f || bi_xy != 50.0f || bi_rgb != 5.0f)
-        return fail(e, PNP_ERR_ARG, "lattices are built for sxy=3 / sxy=50, srgb=5 (PnP.py:1036-1041)");
-    hipStream_t s = (hipStream_t)stream;
-    const float* maps = p.maps_in_2 ? p.maps2 : p.maps;
-    KCHK(e, unary_from_maps(maps, p.d_desc, p.unary, p.B, p.maxHW, p.maxKp, 0, s));
-    return crf_iterate(e, p.d_desc, p.Kpmax, iters, pos_w, bi_w, s);
-}
-
-extern "C" int pnp_remap_hist(pnp_engine* e, int32_t from_crf, uint8_t* d_labels, unsigned long long* d_hist, int32_t n_class,
-                              void* stream) {
-    POST_READY(e);
-    auto& p = e->post;
-    if (!d_labels) return fail(e, PNP_ERR_ARG, "d_labels is null");
-    hipStream_t s = (hipStream_t)stream;
-    const float* src = from_crf ? p.Q : (p.maps_in_2 ? p.maps2 : p.maps);
-    KCHK(e, argmax_remap(src, p.d_desc, p.d_lut, p.lut_stride, d_labels, p.d_label_off, from_crf ? 1 : 0, 0, p.B, p.maxHW, s));
-    if (d_hist && p.d_gt) KCHK(e, confusion_hist(d_labels, p.d_gt, p.d_desc, p.d_label_off, d_hist, n_class, p.B, p.maxHW, s));
-    return PNP_OK;
-}
-
-extern "C" int pnp_postprocess(pnp_engine* e, const float* d_gradcam, int32_t T, float threshold, int32_t scale01, int32_t mode,
-                               uint8_t* d_labels, unsigned long long* d_hist, int32_t n_class, void* stream) {
-    int r = pnp_merge_tokens(e, d_gradcam, T, stream);
-    if (r) return r;
-    r = pnp_threshold_upsample(e, threshold, scale01, stream);
-    if (r) return r;
-    if (mode & 1) {
-        r = pnp_blur_minmax(e, stream);
-        if (r) return r;
-    }
-    if (mode & 2) {
-        r = pnp_densecrf(e, 10, 7.0f, 3.0f, 10.0f, 50.0f, 5.0f, stream);
-        if (r) return r;
-    }
-    return pnp_remap_hist(e, (mode & 2) ? 1 : 0, d_labels, d_hist, n_class, stream);
-}
-
-// 1-drop and N-drop "blur+crf" post-processing of one batch in ONE mean-field run (PnP.py:348-403 and 424-481 run the
-// same DenseCRF twice per image on the same RGB image): the two problems become two channel groups of every row, so the
-// lattice index walks -- contributor lists, neighbour ids, simplex offsets -- are shared.  Per-channel arithmetic is
-// untouched: labels and histograms equal two pnp_postprocess calls bit for bit.
-extern "C" int pnp_postprocess_pair(pnp_engine* e, const float* d_gradcam_1drop, const float* d_gradcam_ndrop, int32_t T,
-                                    float threshold, int32_t scale01_mask, uint8_t* d_labels_1drop, unsigned long long* d_hist_1drop,
-                                    uint8_t* d_labels_ndrop, unsigned long long* d_hist_ndrop, int32_t n_class, void* stream) {
-    POST_READY(e);
-    auto& p = e->post;
-    if (!p.has_crf) return fail(e, PNP_ERR_STATE, "batch was prepared without CRF lattices");
-    if (!d_labels_1drop || !d_labels_ndrop) return fail(e, PNP_ERR_ARG, "label outputs are null");
-    if (p.groups_cap < 2) {                     // arrays sized for one group only: same results, two passes
-        int r = pnp_postprocess(e, d_gradcam_1drop, T, threshold, scale01_mask & 1, 3, d_labels_1drop, d_hist_1drop, n_class, stream);
-        if (r) return r;
-        return pnp_postprocess(e, d_gradcam_ndrop, T, threshold, (scale01_mask >> 1) & 1, 3, d_labels_ndrop, d_hist_ndrop, n_class, stream);
-    }
-    hipStream_t s = (hipStream_t)stream;
-    for (int grp = 0; grp < 2; grp++) {
-        int r = pnp_merge_tokens(e, grp == 0 ? d_gradcam_1drop : d_gradcam_ndrop, T, stream);
-        if (r) return r;
-        r = pnp_threshold_upsample(e, threshold, (scale01_mask >> grp) & 1, stream);   // PnP.py: Scale_0_1 in the 1-drop branch only; PnPc.py: both
-        if (r) return r;
-        r = pnp_blur_minmax(e, stream);
-        if (r) return r;
-        KCHK(e, unary_from_maps(p.maps2, p.d_desc_pair, p.unary, p.B, p.maxHW, p.maxKp, grp, s));
-    }
-    CrfLabelOut lout;
-    lout.lab[0] = d_labels_1drop;
-    lout.lab[1] = d_labels_ndrop;
-    lout.lut = p.d_lut;
-    lout.lut_stride = p.lut_stride;
-    lout.label_off = p.d_label_off;
-    int r = crf_iterate(e, p.d_desc_pair, p.Kpmax_pair, 10, 7.0f, 10.0f, s, lout);
-    if (r) return r;
-    for (int grp = 0; grp < 2; grp++) {
-        uint8_t* lab = grp == 0 ? d_labels_1drop : d_labels_ndrop;
-        unsigned long long* hist = grp == 0 ? d_hist_1drop : d_hist_ndrop;
-        if (hist && p.d_gt) KCHK(e, confusion_hist(lab, p.d_gt, p.d_desc, p.d_label_off, hist, n_class, p.B, p.maxHW, s));
-    }
-    return PNP_OK;
-}
-
 // =========================================================================================== introspection
 
 extern "C" int pnp_get_buffer(pnp_engine* e, const char* name, void** d_ptr, size_t* bytes) {
     if (!e || !name || !d_ptr || !bytes) return PNP_ERR_ARG;
     const std::string n(name);
     const size_t B = e->c.max_batch, L = e->c.max_text_len;
-    auto& p = e->post;
     auto set = [&](void* ptr, size_t b) { *d_ptr = ptr; *bytes = b; return PNP_OK; };
     if (n == "image_embeds") return set(e->emb32, B * e->N * (size_t)e->D * 4);
     if (n == "image_embeds_t") return set(e->embT.hi, B * e->N * (size_t)e->D * e->esz);
@@ -1741,23 +1079,7 @@ extern "C" int pnp_get_buffer(pnp_engine* e, const char* name, void** d_ptr, siz
     if (n == "Vt") return set(e->Vt, (size_t)e->TL * e->H * B * e->Npad * e->esz);
     if (n == "dq_xattn") return set(e->dqc, B * L * (size_t)e->H * e->esz);
     if (n == "dctx_xattn") return set(e->dctxc, B * L * (size_t)e->H * e->esz);
-    if (p.reserved) {
-        const size_t mk = (size_t)p.max_total_pix * p.maxK * 4;
-        const size_t mq = (size_t)p.max_total_pix * p.maxKp * 4 * p.groups_cap;   // as allocated: a paired run fills two groups per row
-        if (n == "merged") return set(p.merged, (size_t)p.maxB * p.maxK * e->PP * 4);
-        if (n == "maps") return set(p.maps_in_2 ? p.maps2 : p.maps, mk);
-        if (n == "maps_pre_blur") return set(p.maps, mk);
-        if (n == "unary") return set(p.unary, mq);
-        if (n == "crf_q") return set(p.Q, mq);
-        if (n == "crf_idbase_gauss") return set(p.lat[0].idbase, ((size_t)p.maxB + 1) * 4);
-        if (n == "crf_idbase_bilateral") return set(p.lat[1].idbase, ((size_t)p.maxB + 1) * 4);
-        if (n == "crf_norm_gauss") return set(p.norm[0], (size_t)p.max_total_pix * 4);
-        if (n == "crf_norm_bilateral") return set(p.norm[1], (size_t)p.max_total_pix * 4);
-        if (n == "crf_offset_gauss") return set(p.lat[0].offset, (size_t)p.max_total_pix * 3 * 4);          // per pixel: 3 lattice ids
-        if (n == "crf_offset_bilateral") return set(p.lat[1].offset, (size_t)p.max_total_pix * 6 * 4);  // per pixel: 6 lattice ids
-        if (n == "crf_nbr8_gauss") return set(p.lat[0].nbr8, (size_t)(p.lat[0].D1 / 2) * p.lat[0].cap * sizeof(CrfNbr8));
-        if (n == "crf_nbr8_bilateral") return set(p.lat[1].nbr8, (size_t)(p.lat[1].D1 / 2) * p.lat[1].cap * sizeof(CrfNbr8));
-    }
+    if (post_get_buffer(e, n, d_ptr, bytes)) return PNP_OK;
     return fail(e, PNP_ERR_ARG, "unknown buffer %s", name);
 }
 

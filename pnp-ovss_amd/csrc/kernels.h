@@ -151,11 +151,30 @@ size_t sort_temp_bytes(size_t n);
 int radix_sort_pairs(uint64_t* keys_in, uint64_t* keys_out, uint32_t* vals_in, uint32_t* vals_out, size_t n, int begin_bit, int end_bit,
                      const size_t* seg_off, int nseg, void* temp, size_t temp_bytes, hipStream_t s);
 int device_scan_i32(const int* in, int* out, size_t n, bool inclusive, void* temp, size_t temp_bytes, hipStream_t s);
-size_t crf_sort_temp_bytes(size_t max_entries, int max_images);
+size_t crf_sort_temp_bytes(size_t max_entries);
+// Device scratch of crf_build_lattice, sized once for the largest build: E = (pixels of a batch) x 6 entries of the bilateral
+// lattice (the Gaussian one has 3 per pixel), M <= E lattice points.  The build reuses the arrays as it goes:
+//   keys_a  [E] u64   packed (pixel, vertex) keys, the first sort's input; then the second sort's input keys [M];
+//                     then, as int [M], the contributor-list lengths
+//   keys_b  [E] u64   the first sort's output; then the second sort's output keys [M]; then, as u32 [E], the moved contributor list
+//   vals_a  [E] u32   entry indices, the first sort's input; then the second sort's input ids [M]
+//   head    [E] int   segment-head flags; then the spatial rank of every lattice point [M]
+//   incl    [E] int   inclusive scan of `head`; then, as u32 [M], the second sort's output ids; then the new list starts [M]
+//   n1k/n2k [6 E] int neighbour ids in key order, (d + 1) rows of stride CrfLattice::cap
+//   temp              sort / scan workspace of temp_bytes >= crf_sort_temp_bytes(E)
+//   range_err   int   device flag, zero on entry: set when a coordinate does not fit the packed key
+struct CrfBuildScratch {
+    uint64_t *keys_a, *keys_b;
+    uint32_t* vals_a;
+    int *head, *incl, *n1k, *n2k;
+    char* temp;
+    size_t temp_bytes;
+    int* range_err;
+};
+// h_range_err: set to 1 when the flag was raised (read back with the lattice size: the build's one synchronisation)
 int crf_build_lattice(int D, const CrfLattice& L, const PostDesc* d_imgs, const PostDesc* h_imgs, const uint8_t* d_rgb, float sxy, float srgb,
-                      int B, size_t ent_total, int max_pixels,
-                      uint64_t* keys_a, uint64_t* keys_b, uint32_t* vals_a, int* head, int* incl, int* n1k, int* n2k,
-                      void* temp, size_t temp_bytes, int* d_range_err, int* h_range_err, int* h_points, hipStream_t s);
+                      int B, size_t ent_total, int max_pixels, const CrfBuildScratch& scratch, int* h_range_err, int* h_points,
+                      hipStream_t s);
 int crf_lattice_norm(const CrfLattice& L, const PostDesc* d_imgs, int B, int max_pixels, size_t ent_total, float* va, float* vb,
                      float* norm_out, hipStream_t s);
 int crf_filter(const CrfLattice& L, const PostDesc* d_imgs, int img0, int nimg, const float* Q,
@@ -170,6 +189,6 @@ struct CrfLabelOut {
 };
 int crf_update(const CrfLattice& Lg, const CrfLattice& Lb, const PostDesc* d_imgs, int img0, int nimg, const float* vg,
                const float* vb, const float* norm_g, const float* norm_b, const float* unary, float* Q, float w_g,
-               float w_b, int pairwise, int max_pixels, int max_kp, int groups, hipStream_t s, const CrfLabelOut& labels = CrfLabelOut());
+               float w_b, int pairwise, int max_kp, int groups, hipStream_t s, const CrfLabelOut& labels = CrfLabelOut());
 
 }  // namespace pnp

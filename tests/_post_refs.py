@@ -1,5 +1,5 @@
 """Case generators, references and planted faults for the post-processing operator tests (test_post_ops_cpu.py,
-test_post_ops_gpu.py): pipeline_kernels.hip, crf.hip and the post-processing entry points of engine.hip.
+test_post_ops_gpu.py): pipeline_kernels.hip, crf.hip and the post-processing entry points of post.hip.
 
 The reference is the oracle alone (oracle/pipeline_np.py, `OP.*`): threshold / upsample, blur and labels are compared bit for
 bit, DenseCRF marginals to atol = 1e-6 (the criterion of test_hip_parity.test_postprocess_stages_bit_exact_vs_oracle).
