@@ -525,11 +525,15 @@ __global__ __launch_bounds__(256) void crf_blur4_kernel(const CrfLattice L, cons
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
     int b, part, parts;
     for (int wi = 0; xcd_work(wi, xcd, img0, nimg, b, part, parts); wi++) {
-        const PostDesc im = imgs[b];
+        // The descriptor's fields are read where they are needed (scalar loads).  A by-value copy indexed with L.which is kept
+        // per lane in LDS (18 KB per workgroup), and what is derived from it -- K4, the bases, the item range -- then sits in
+        // vector registers although it is the same in all lanes: 41 -> 29 registers here, 72 -> 60 in crf_blur4x2_kernel.
+        const PostDesc& im = imgs[b];
         const int K4 = im.Kp >> 2;
         const int lo = L.idbase[b], hi = L.idbase[b + 1];
-        const f32x4* S4 = reinterpret_cast<const f32x4*>(src + im.voff[L.which]);
-        f32x4* D4 = reinterpret_cast<f32x4*>(dst + im.voff[L.which]);
+        const size_t voff = L.which ? im.voff[1] : im.voff[0];
+        const f32x4* S4 = reinterpret_cast<const f32x4*>(src + voff);
+        f32x4* D4 = reinterpret_cast<f32x4*>(dst + voff);
         const int first = (int)((long)(hi - lo) * part / parts) * K4;
         const int nitem = (int)((long)(hi - lo) * (part + 1) / parts) * K4, stride = bpx * 256;
         for (int it0 = first + slot * 256 + threadIdx.x; it0 < nitem; it0 += 2 * stride) {
@@ -571,19 +575,22 @@ __device__ __forceinline__ f32x4 crf_blur1(const f32x4& old, const f32x4& va, co
 // built once per lattice) instead of two dependent rounds of index loads; rows are addressed with 32-bit byte offsets; the
 // record of the thread's next item is requested behind the row gathers of the current one and the previous result is
 // stored there too, so an item exposes one memory latency (the kernel is bound by latency x occupancy and by the 64 B/clk
-// of the CU's vector memory path -- nine rows in, one out -- not by HBM bytes).
-__global__ __launch_bounds__(256) void crf_blur4x2_kernel(const CrfLattice L, const PostDesc* __restrict__ imgs,
+// of the CU's vector memory path -- nine rows in, one out -- not by HBM bytes).  60 registers: eight waves per SIMD (seven at
+// the 72 of the by-value descriptor: 300 -> 281 us per launch on the headline batch, profiles/crf_occupancy.txt).
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8)))
+void crf_blur4x2_kernel(const CrfLattice L, const PostDesc* __restrict__ imgs,
                                                           const float* __restrict__ src, float* __restrict__ dst, int pair,
                                                           int img0, int nimg) {
     const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, bpx = gridDim.x >> 3;
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
     int b, part, parts;
     for (int wi = 0; xcd_work(wi, xcd, img0, nimg, b, part, parts); wi++) {
-        const PostDesc im = imgs[b];
+        const PostDesc& im = imgs[b];                                   // (fields read one by one: see crf_blur4_kernel)
         const int K4 = im.Kp >> 2;
         const int lo = L.idbase[b], hi = L.idbase[b + 1];
-        const char* const Sb = reinterpret_cast<const char*>(src + im.voff[L.which]);
-        f32x4* const D4 = reinterpret_cast<f32x4*>(dst + im.voff[L.which]);
+        const size_t voff = L.which ? im.voff[1] : im.voff[0];
+        const char* const Sb = reinterpret_cast<const char*>(src + voff);
+        f32x4* const D4 = reinterpret_cast<f32x4*>(dst + voff);
         const CrfNbr8* const T = L.nbr8 + (size_t)pair * L.cap + lo;
         const uint32_t rowb = (uint32_t)K4 * 16u;
         const int first = (int)((long)(hi - lo) * part / parts) * K4;
@@ -640,9 +647,11 @@ constexpr int CRF_TP = 256;
 constexpr int CRF_WAVE_SOFTMAX_K = 128;
 __host__ __device__ inline int crf_tile_w(int tp) { return tp >= 128 ? 16 : tp >= 32 ? 8 : 4; }
 // WIDE (rows of >= CRF_WAVE_SOFTMAX_K channels per group): the wave-parallel softmax below; such tiles are LDS-bound to three
-// workgroups per CU, so the kernel may use 128 registers (the narrow form is held to 96 for five waves per SIMD)
+// workgroups per CU, so the kernel may use 128 registers (the narrow form is held to 80 for six waves per SIMD: 714 -> 607 us
+// per launch on the headline batch, of which 714 -> 648 at five waves from the leaner record staging and store loop below)
 template <bool WIDE>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WIDE ? 4 : 5))) void crf_update_kernel(const CrfLattice Lg, const CrfLattice Lb, const PostDesc* __restrict__ imgs,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WIDE ? 4 : 6)))
+void crf_update_kernel(const CrfLattice Lg, const CrfLattice Lb, const PostDesc* __restrict__ imgs,
                                                          const float* __restrict__ vg, const float* __restrict__ vb,
                                                          const float* __restrict__ norm_g, const float* __restrict__ norm_b,
                                                          const float* __restrict__ unary, float* __restrict__ Q, float w_g,
@@ -658,7 +667,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WIDE ? 4 : 
         const PostDesc im = imgs[b];
         const int K = im.K, Kp = im.Kp, K4 = Kp >> 2, ldt = Kp + 1;
         f32x4* Q4 = reinterpret_cast<f32x4*>(Q + im.qoff);
-        const int lo_g = pairwise ? Lg.idbase[b] : 0, lo_b = pairwise ? Lb.idbase[b] : 0;
+        // (the same in every lane; said so, because a load under a condition is a per-lane load to the compiler)
+        const int lo_g = __builtin_amdgcn_readfirstlane(pairwise ? Lg.idbase[b] : 0);
+        const int lo_b = __builtin_amdgcn_readfirstlane(pairwise ? Lb.idbase[b] : 0);
         const int TPe = CRF_TP / im.G < tp_cap ? CRF_TP / im.G : tp_cap; // one softmax thread per (pixel, group)
         const int TW = tile_w > 0 ? tile_w : crf_tile_w(TPe), TH = TPe / TW, TP = TW * TH;   // TW: a power of two
         const int tw_shift = __ffs(TW) - 1;
@@ -688,23 +699,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WIDE ? 4 : 
             };
             auto inside = [&](int pl) { return x0 + (pl & (TW - 1)) < im.W && y0 + (pl >> tw_shift) < im.H; };
             // the tile's per-pixel slice records -- 6 + 3 image-local lattice ids and barycentric weights, two normalisers --
-            // are staged once through LDS (coalesced loads) instead of being fetched by every channel-chunk lane of the
-            // pixel: 10 vector-memory instructions per (pixel, chunk) item instead of 30 (the kernel is issue-bound there)
+            // are staged once through LDS instead of being fetched by every channel-chunk lane of the pixel: 10 vector-memory
+            // instructions per (pixel, chunk) item instead of 30 (the kernel is issue-bound there).  One thread per pixel: its
+            // 6 + 6 + 3 + 3 words are consecutive (wide loads), and no per-thread division by 6 / 3 is carried through the tile
+            // loop in registers
             if (pairwise) {
-                for (int i = tid; i < TP * 6; i += 256) {
-                    const int pl = i / 6;
-                    const size_t g = ((size_t)im.pix0 + pixel_of(pl)) * 6 + (i - pl * 6);
-                    rec_ob[i] = Lb.offset[g] - lo_b;
-                    rec_wb[i] = Lb.bary[g];
-                }
-                for (int i = tid; i < TP * 3; i += 256) {
-                    const int pl = i / 3;
-                    const size_t g = ((size_t)im.pix0 + pixel_of(pl)) * 3 + (i - pl * 3);
-                    rec_og[i] = Lg.offset[g] - lo_g;
-                    rec_wg[i] = Lg.bary[g];
-                }
-                for (int pl = tid; pl < TP; pl += 256) {
+                for (int pl = tid; pl < TP; pl += 256) {                 // (TP <= 256: one pixel per thread)
                     const size_t g = (size_t)im.pix0 + pixel_of(pl);
+#pragma unroll
+                    for (int v = 0; v < 6; v++) {
+                        rec_ob[pl * 6 + v] = Lb.offset[g * 6 + v] - lo_b;
+                        rec_wb[pl * 6 + v] = Lb.bary[g * 6 + v];
+                    }
+#pragma unroll
+                    for (int v = 0; v < 3; v++) {
+                        rec_og[pl * 3 + v] = Lg.offset[g * 3 + v] - lo_g;
+                        rec_wg[pl * 3 + v] = Lg.bary[g * 3 + v];
+                    }
                     rec_nb[pl] = norm_b[g];
                     rec_ng[pl] = norm_g[g];
                 }
@@ -878,11 +889,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WIDE ? 4 : 
                 }
             }
             __syncthreads();
-            for (int item = tid; item < TP * K4; item += 256) {
-                const int pl = item / K4, c = item - pl * K4;
-                if (inside(pl)) {
-                    const float* r = tile + pl * ldt + 4 * c;
-                    st_stream(Q4 + (size_t)pixel_of(pl) * K4 + c, f32x4{r[0], r[1], r[2], r[3]});
+            {
+                int pl = pl0, c = c0;
+                for (int item = tid; item < TP * K4; item += 256) {
+                    if (inside(pl)) {
+                        const float* r = tile + pl * ldt + 4 * c;
+                        st_stream(Q4 + (size_t)pixel_of(pl) * K4 + c, f32x4{r[0], r[1], r[2], r[3]});
+                    }
+                    pl += q256;
+                    c += r256;
+                    if (c >= K4) {
+                        c -= K4;
+                        pl++;
+                    }
                 }
             }
             __syncthreads();
