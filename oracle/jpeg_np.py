@@ -3,8 +3,9 @@ reference's input side gets from Pillow: `Image.open(path).convert('RGB')` (Data
 PnP_OVSS_0514_updated_segmentation.py:929-955 load_OrgImage).  Pillow decodes with libjpeg(-turbo) defaults, an
 un-vendored third-party library, so this follows its published algorithm: sequential Huffman baseline (ITU T.81), the
 "islow" integer inverse DCT (jidctint.c: 13-bit constants, two passes, DESCALE rounding), "fancy" triangle-filter chroma
-upsampling (jdsample.c h2v1 / h2v2) and the fixed-point YCbCr -> RGB tables of jdcolor.c.  Pinned bit-exact against Pillow
-itself on JPEGs encoded here (tests/test_oracle_golden.py::test_jpeg_oracle_matches_pillow).
+upsampling (jdsample.c h2v1 / h2v2; plain replication when the downsampled chroma width is at most 2) and the fixed-point
+YCbCr -> RGB tables of jdcolor.c.  Pinned bit-exact against Pillow itself on JPEGs encoded here
+(tests/test_oracle_golden.py::test_jpeg_oracle_matches_pillow, tests/test_jpeg_streams_cpu.py).
 
 The parser half (`parse_jpeg`) is shared with the product host code path through pnp_ovss.jpeg (same tables go to the
 device kernels); the arithmetic half below is only the checker.
@@ -320,6 +321,8 @@ def decode(data: bytes):
     y = planes[0][:H, :W]
     if (c0["h"], c0["v"]) == (1, 1):
         cb, cr = planes[1][:H, :W], planes[2][:H, :W]
+    elif -(-W // 2) <= 2:                 # jdsample.c: fancy upsampling only when downsampled_width > 2, else replication
+        cb, cr = [np.repeat(np.repeat(p, c0["v"], axis=0), 2, axis=1)[:H, :W] for p in planes[1:]]
     elif (c0["h"], c0["v"]) == (2, 1):
         cb, cr = upsample_h2v1_fancy(planes[1][:H], W), upsample_h2v1_fancy(planes[2][:H], W)
     else:

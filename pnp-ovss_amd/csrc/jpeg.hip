@@ -14,7 +14,9 @@
 //                        Look-ahead tables (10 bits) are built in LDS from the file's own DHT bytes.
 //   jpeg_idct_kernel     one thread per 8 x 8 block: dequantise + jidctint.c "islow" (13-bit constants, DESCALE)
 //   jpeg_color_kernel    one thread per pixel: jdsample.c "fancy" h2v1 / h2v2 chroma upsampling + jdcolor.c fixed-point
-//                        YCbCr -> RGB, written as the concatenated HWC uint8 buffer the resize and the CRF read
+//                        YCbCr -> RGB, written as the concatenated HWC uint8 buffer the resize and the CRF read.  As in
+//                        jdsample.c, the fancy filters apply only when the chroma plane's downsampled width (W + 1) >> 1
+//                        exceeds 2; images of width <= 4 get plain replication in both directions
 // Integer / byte work, HBM-trivial (a 500 x 375 image: ~85 KB in, 0.56 MB out).
 #include "common.h"
 #include "kernels.h"
@@ -409,6 +411,8 @@ __global__ __launch_bounds__(256) void jpeg_color_kernel(const JpegImage* __rest
             const uint8_t* P = planes + im.plane_off[1 + k];
             if (im.hmax == 1) {
                 cc[k] = P[(long)y * cs + x];
+            } else if (((W + 1) >> 1) <= 2) {   // jdsample.c: fancy only when downsampled_width > 2, else replication
+                cc[k] = P[(long)(y >> (im.vmax - 1)) * cs + (x >> 1)];
             } else if (im.vmax == 1) {          // h2v1 fancy
                 const int w = (W + 1) >> 1, cx = x >> 1;
                 const int cur = P[(long)y * cs + cx];
