@@ -328,7 +328,8 @@ int pnp_profile_read_stage(pnp_engine* e, int32_t stage, int64_t* launches, doub
  *              model says it pays, 2 = whenever a launch has a partial last round.  Results are deterministic in every
  *              mode (fixed-order fix-up, no atomics) and differ between modes only by fp32 summation order.  Launches on a
  *              stream that is being captured into a hipGraph always take whole tiles (the tail's one-launch-at-a-time event
- *              chain reaches across streams).
+ *              chain reaches across streams).  That chain -- at most one launch with a tail in flight per device, whatever the
+ *              streams, host threads and epilogues -- holds within one process: several processes on one device are outside it.
  *   "text_rows": workgroups per (head, image) of the text self-attention launches for captions of 65..192 tokens (B/med.py:
  *              229-283 self-attention forward and its backward): 0 (default) = chosen per launch from B * heads, L and the CU
  *              count, 1..4 = that many wherever the choice is made.  The split decides which workgroup computes a row, not one

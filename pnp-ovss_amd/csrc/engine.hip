@@ -1180,7 +1180,7 @@ extern "C" int pnp_op_gemm_x3(const void* d_A_hi, const void* d_A_lo, int32_t ld
     g.bias = d_bias; g.bias_on_rows = bias_on_rows; g.resid = d_resid; g.ldr = ldr; g.out_f32 = d_out_f32; g.ldo = ldo;
     g.out_t = d_out_hi; g.out_lo = d_out_lo; g.ldo_t = ldo_t; g.col_div = col_div; g.col_pad = col_pad;
     g.mode = gelu ? GEMM_EPI_GELU : GEMM_EPI_LINEAR;
-    g.sk = streamk_mode() ? streamk_ws_default() : nullptr;     // op level: the per-device workspace (calls on one stream at a time)
+    g.sk = streamk_mode() ? streamk_ws_default() : nullptr;     // op level: the per-device workspace (shared by all callers: the launcher serialises)
     return gemm_nt(1, g, (hipStream_t)stream);
 }
 

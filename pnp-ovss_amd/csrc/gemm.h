@@ -20,7 +20,9 @@ struct StreamKWs {
 int streamk_ws_create(StreamKWs* ws, int wgs);
 void streamk_ws_destroy(StreamKWs* ws);
 int streamk_ws_timeouts(StreamKWs* ws, unsigned* out);     // synchronises the device; *out = give-up word (0 = none)
-StreamKWs* streamk_ws_default();                          // per-device workspace of the op-level entry points (one stream at a time)
+StreamKWs* streamk_ws_default();                          // per-device workspace of the op-level entry points: launches from several streams
+                                                           // and host threads may share it, the launcher serialises them device-wide
+                                                           // (gemm_x3.hip streamk_chain_launch; tests/test_streamk_chain_gpu.py)
 void set_streamk_mode(int mode);
 int streamk_mode();
 

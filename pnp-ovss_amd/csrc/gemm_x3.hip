@@ -40,8 +40,10 @@
 // of its own launch with lower block ids.  Those were handed to the dispatcher before it, but each XCD deals its share of the
 // grid at its own pace, so "lower id" means "started, or waiting for a CU that something else holds": progress then depends on
 // that something not being another launch of this kind waiting the other way round.  The launcher therefore keeps ONE
-// stream-K launch in flight per device (an event chain across streams, launch_x3), beside which only kernels that never
-// spin can hold CUs; and every spin is bounded all the same, a give-up recorded in a word the host reads
+// stream-K launch in flight per device and process, for all five epilogues together (ONE event chain across streams and host
+// threads, streamk_chain_launch; tests/test_streamk_chain_gpu.py checks the ordering itself for every pair of epilogues,
+// test_gemm_stream_k_launches_from_two_streams_do_not_meet and ..._with_mixed_epilogues_... the results), beside which only
+// kernels that never spin can hold CUs; and every spin is bounded all the same, a give-up recorded in a word the host reads
 // (pnp_streamk_status) instead of a hung device.  The hand-off is the guide's
 // write-through form (cdna_hip_programming.md Guideline 16, R1): every payload store `sc1`, every storing wave drains
 // vmcnt, one lane stores the flag `sc1`; the consumer polls that word with `sc1` loads, joins a workgroup barrier, and every
@@ -622,6 +624,31 @@ static bool streamk_pays(int tail, int cap, int nk2, int upw, int np) {
     return sk * 1.05 + 0.5 < whole;                 // at least 5 % of the tail round, or it is not worth a second code path
 }
 
+// ONE stream-K launch in flight per device, WHATEVER its epilogue: an owner spins on workgroups of its own launch with lower ids,
+// which the dispatcher started before it -- true within a launch, but two such launches from two streams, each resident on part
+// of the chip, could hold the CUs the other's missing producers need.  Every launch waits for the event behind the previous one
+// (whatever stream it was on, whichever instantiation of launch_x3 issued it) and leaves its own; kernels that never spin overlap
+// with it as before.  The chain's state lives HERE, once per process, and not in the launcher template (a function-local static
+// of a template exists once per instantiation: five chains, and launches with different epilogues unordered).  The lock is held
+// over wait, launch and record -- and over the workspace's launch count, which op-level callers on several threads share.
+static std::mutex g_sk_chain_mu;
+static hipEvent_t g_sk_chain_last[kMaxDevices];
+static int streamk_chain_launch(void (*kernel)(const GemmArgs), const GemmArgs& g, int grid, StreamKWs* ws, hipStream_t s) {
+    const int d = current_device();
+    if (d < 0) return PNP_ERR_HIP;
+    std::lock_guard<std::mutex> lk(g_sk_chain_mu);
+    hipEvent_t& last = g_sk_chain_last[d];
+    ws->launches++;
+    if (!last) {
+        if (hipEventCreateWithFlags(&last, hipEventDisableTiming) != hipSuccess) return PNP_ERR_HIP;
+    } else if (hipStreamWaitEvent(s, last, 0) != hipSuccess) {
+        return PNP_ERR_HIP;
+    }
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(512), kWideSmem, s, g);
+    const bool ok = hipGetLastError() == hipSuccess && hipEventRecord(last, s) == hipSuccess;
+    return ok ? PNP_OK : PNP_ERR_HIP;
+}
+
 template <int EPI>
 static int launch_x3(GemmArgs g, hipStream_t s) {
     const int nbm = (g.M + 255) / 256, nbn = g.N / 256;
@@ -637,7 +664,7 @@ static int launch_x3(GemmArgs g, hipStream_t s) {
         if (tail > 0) {
             const int upw = (int)(((long)tail * nk2 + cap - 1) / cap);
             const int np = (nk2 - 1 + upw - 1) / upw;                    // parts in front of the last one of a tile, at most
-            // (a stream that is being captured into a graph keeps whole tiles: the event chain below reaches across streams, which
+            // (a stream that is being captured into a graph keeps whole tiles: the event chain above reaches across streams, which
             // a capture must not, and one-launch-at-a-time cannot be promised for replays)
             hipStreamCaptureStatus cap_st = hipStreamCaptureStatusNone;
             const bool capturing = hipStreamIsCapturing(s, &cap_st) == hipSuccess && cap_st != hipStreamCaptureStatusNone;
@@ -648,24 +675,7 @@ static int launch_x3(GemmArgs g, hipStream_t s) {
                 g.sk_tmo = ws->flag + ws->wgs;
                 g.sk_full = rounds * cap;
                 g.sk_upw = upw;
-                ws->launches++;
-                // ONE stream-K launch in flight per device: an owner spins on workgroups of its own launch with lower ids, which
-                // the dispatcher started before it -- true within a launch, but two such launches from two streams, each resident on
-                // part of the chip, could hold the CUs the other's missing producers need.  Every launch waits for the event behind the
-                // previous one (whatever stream it was on) and leaves its own; kernels that never spin overlap with it as before
-                static std::mutex mu;
-                static hipEvent_t last[kMaxDevices];
-                const int d = current_device();
-                if (d < 0) return PNP_ERR_HIP;
-                std::lock_guard<std::mutex> lk(mu);
-                if (!last[d]) {
-                    if (hipEventCreateWithFlags(&last[d], hipEventDisableTiming) != hipSuccess) return PNP_ERR_HIP;
-                } else if (hipStreamWaitEvent(s, last[d], 0) != hipSuccess) {
-                    return PNP_ERR_HIP;
-                }
-                hipLaunchKernelGGL((gemm_nt_x3_kernel<EPI, true>), dim3(cap), dim3(512), kWideSmem, s, g);
-                const bool ok = hipGetLastError() == hipSuccess && hipEventRecord(last[d], s) == hipSuccess;
-                return ok ? PNP_OK : PNP_ERR_HIP;
+                return streamk_chain_launch(gemm_nt_x3_kernel<EPI, true>, g, cap, ws, s);
             }
         }
     }
