@@ -210,6 +210,43 @@ int pnp_postprocess_pair(pnp_engine* e, const float* d_gradcam_1drop, const floa
                          int32_t scale01_mask, uint8_t* d_labels_1drop, unsigned long long* d_hist_1drop, uint8_t* d_labels_ndrop,
                          unsigned long long* d_hist_ndrop, int32_t n_class, void* stream);
 
+/* ---- stand-alone DenseCRF: replaces pydensecrf's DenseCRF2D as the reference's densecrf() drives it (PnP.py:1063-1073) ----
+ * The mean-field of pnp_densecrf on unary energies the caller brings and with kernel widths the caller chooses, in a solver
+ * that owns its workspace and needs no pnp_engine: setUnaryEnergy + addPairwiseGaussian(sxy = pos_xy, compat = pos_w) +
+ * addPairwiseBilateral(sxy = bi_xy, srgb = bi_rgb, compat = bi_w) + inference(iters) for a batch of images of any sizes and
+ * label counts.  Potts compatibility, isotropic widths, DIAG_KERNEL / NORMALIZE_SYMMETRIC (pydensecrf's defaults).
+ * pnp_crf_create allocates every device byte the solver will use (what pnp_post_reserve allocates for the CRF stage):
+ * at most 64 images per batch and 255 labels per image, PNP_ERR_ARG beyond (and nothing is allocated).  On a later failure
+ * (out of memory) *out is still a handle: pnp_crf_last_error says why, pnp_crf_destroy frees it.
+ * A solver is not thread-safe; distinct solvers are independent.  Null pointers, B < 1, K < 2, non-positive widths and
+ * iters < 0 are refused before any HIP call. */
+typedef struct pnp_crf pnp_crf;
+int pnp_crf_create(int32_t device, int32_t max_batch, int64_t max_total_pixels, int32_t max_pixels_per_image, int32_t max_labels,
+                   pnp_crf** out);
+void pnp_crf_destroy(pnp_crf* c);
+size_t pnp_crf_allocated_bytes(const pnp_crf* c);
+const char* pnp_crf_last_error(const pnp_crf* c);         /* valid until the next call on c; "null solver" for NULL */
+typedef struct pnp_crf_batch {
+    int32_t B;
+    const int32_t* H;            /* [B] host */
+    const int32_t* W;            /* [B] host */
+    const int32_t* K;            /* [B] host: labels of image b, 2..max_labels */
+    const uint8_t* d_rgb;        /* device: concatenated (H, W, 3) uint8 images */
+    const float* d_unary;        /* device: concatenated (K_b, H_b * W_b) channel-major blocks (pydensecrf's setUnaryEnergy layout) */
+} pnp_crf_batch;
+/* Lays the batch out, copies the unary energies into the solver (d_unary may be reused once the stream has passed this call)
+ * and builds both permutohedral lattices and their normalisers for these widths; the Gaussian lattice is kept while the image
+ * sizes and pos_xy stay the same.  Synchronises (lattice size + key-range flag, once per lattice built).  A batch beyond the
+ * reserved bounds is PNP_ERR_ARG with the numbers in pnp_crf_last_error; so is a colour (or position) width so small that a
+ * lattice coordinate leaves the packed key -- the message names bi_rgb and the limit.  After a failed call the solver holds no
+ * batch: pnp_crf_infer returns PNP_ERR_STATE until a pnp_crf_set_batch succeeds. */
+int pnp_crf_set_batch(pnp_crf* c, const pnp_crf_batch* batch, float pos_xy, float bi_xy, float bi_rgb, void* stream);
+/* Q0 = softmax(-U), then `iters` mean-field updates with weights pos_w / bi_w (a weight of 0 drops that kernel's term
+ * arithmetically; both lattices are filtered all the same).  d_q (may be NULL): the marginals as (K_b, H_b * W_b) blocks, laid
+ * out like d_unary; d_labels (may be NULL): uint8 argmax over the labels -- first maximum, a NaN wins, as np.argmax --
+ * concatenated H_b * W_b.  May be called repeatedly on one batch; allocates nothing and does not synchronise. */
+int pnp_crf_infer(pnp_crf* c, int32_t iters, float pos_w, float bi_w, float* d_q, uint8_t* d_labels, void* stream);
+
 /* ---- input side ("next" row: the tensors the reference's datasets hand to the model) -------
  * Dataset.py:434-443: transforms.Resize((S, S), BICUBIC) on the PIL image -> ToTensor -> Normalize(mean, std).
  * Pillow's 8-bit two-pass resampler (src/libImaging/Resample.c) in integer arithmetic, bit-exact: per axis and

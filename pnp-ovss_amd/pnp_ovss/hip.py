@@ -34,6 +34,12 @@ class PnpPostBatch(C.Structure):
                 ("blur_wts", C.POINTER(C.c_double)), ("blur_wt_off", C.POINTER(C.c_int32))]
 
 
+class PnpCrfBatch(C.Structure):
+    _fields_ = [("B", C.c_int32),
+                ("H", C.POINTER(C.c_int32)), ("W", C.POINTER(C.c_int32)), ("K", C.POINTER(C.c_int32)),
+                ("d_rgb", C.c_void_p), ("d_unary", C.c_void_p)]
+
+
 _lib = None
 
 
@@ -114,6 +120,12 @@ def load_library():
         "pnp_op_patchify": (i32, [i32, vp, vp, vp, i32, i32, i32, vp]),
         "pnp_op_cls_rows": (i32, [vp, vp, vp, i32, i32, i32, vp]),
         "pnp_streamk_status": (i32, [vp, C.POINTER(i64), C.POINTER(C.c_uint32)]),
+        "pnp_crf_create": (i32, [i32, i32, i64, i32, i32, C.POINTER(vp)]),
+        "pnp_crf_destroy": (None, [vp]),
+        "pnp_crf_allocated_bytes": (C.c_size_t, [vp]),
+        "pnp_crf_last_error": (C.c_char_p, [vp]),
+        "pnp_crf_set_batch": (i32, [vp, C.POINTER(PnpCrfBatch), f32, f32, f32, vp]),
+        "pnp_crf_infer": (i32, [vp, i32, f32, f32, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)          # AttributeError here = ABI drift, fail loudly
@@ -134,7 +146,9 @@ EXPORTED = ["pnp_create", "pnp_create_shared", "pnp_destroy", "pnp_last_error", 
             "pnp_streamk_status", "pnp_text_forward_text", "pnp_project_normalize", "pnp_itc_similarity",
             "pnp_op_text_self_attn", "pnp_op_text_self_attn_bwd", "pnp_op_layernorm_ex", "pnp_op_layernorm_bwd",
             "pnp_op_text_embed", "pnp_op_itm_head", "pnp_op_itm_grad_seed", "pnp_op_patchify", "pnp_op_cls_rows",
-            "pnp_op_gemm_args", "pnp_overlay_labels", "pnp_jpeg_encode"]
+            "pnp_op_gemm_args", "pnp_overlay_labels", "pnp_jpeg_encode",
+            "pnp_crf_create", "pnp_crf_destroy", "pnp_crf_allocated_bytes", "pnp_crf_last_error", "pnp_crf_set_batch",
+            "pnp_crf_infer"]
 
 
 PROJ_NAMES = ("vision_proj.weight", "vision_proj.bias", "text_proj.weight", "text_proj.bias")      # the optional ITC projections

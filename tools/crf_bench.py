@@ -1,0 +1,182 @@
+"""Time of the stand-alone DenseCRF (pnp_ovss.crf, the pydensecrf shim) on the bench-shaped problem (GPU box only).
+
+    timeout 900 python tools/crf_bench.py [--images 35] [--size 375x500] [--labels 21] [--reps 30] [--out profiles/crf_standalone.json]
+
+Warm, then `reps` repetitions, device work between HIP events:
+  one image through the shim      the host-to-host call (numpy in, numpy out: DenseCRF2D ... inference(10)), and separately the
+                                  device-event time of set_batch (unary ingest + both lattice builds) and of infer
+  `images` images in one run      DenseCRF.run, set_batch and infer likewise
+  oracle/densecrf_ref.c           the same single-image problem on ONE host core: the only stand-in for pydensecrf that can run
+                                  where pydensecrf is not installed -- it is the project's own C restatement, not pydensecrf
+  the engine's own CRF stage      the same images and maps through Engine.densecrf(), timed by its stage profile
+                                  (pnp_profile_read_stage 1: the mean-field iterations alone)
+The maps come from the engine's own merge / upsample / blur stages on random patch-grid maps; the stand-alone runs get the
+unary energies the engine computed from exactly those maps, so both paths must give the same bits (`agreement`).  Prints one
+JSON line and writes it to --out.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "pnp-ovss_amd"))
+
+
+def synth_photo(rng, H, W):
+    yy, xx = np.mgrid[0:H, 0:W].astype(np.float32)
+    img = np.zeros((H, W, 3), np.float32)
+    for c in range(3):
+        for _ in range(6):
+            fx, fy, ph = rng.uniform(0.002, 0.05), rng.uniform(0.002, 0.05), rng.uniform(0, 6.28)
+            img[..., c] += rng.uniform(10, 40) * np.sin(fx * xx + fy * yy + ph)
+    img += 128 + rng.normal(0, 12, (H, W, 1)).astype(np.float32) + rng.normal(0, 4, (H, W, 3)).astype(np.float32)
+    return np.clip(img, 0, 255).astype(np.uint8)
+
+
+def events_ms(torch, fn, reps):
+    """median device time of fn() between two events (fn may synchronise inside: the events are on the same stream)."""
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    out = []
+    for _ in range(reps):
+        torch.cuda.synchronize()
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        out.append(e0.elapsed_time(e1))
+    return float(np.median(out))
+
+
+def main():
+    import torch
+    from oracle import pipeline_np as OP
+    from pnp_ovss import config as C, crf
+    from pnp_ovss.hip import Engine
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--images", type=int, default=35)
+    ap.add_argument("--size", default="375x500")
+    ap.add_argument("--labels", type=int, default=21)
+    ap.add_argument("--reps", type=int, default=30)
+    ap.add_argument("--oracle_reps", type=int, default=1)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "crf_standalone.json"))
+    a = ap.parse_args()
+    H, W = map(int, a.size.split("x"))
+    B, K, IMG = a.images, a.labels, 336
+    rng = np.random.default_rng(0)
+    imgs = [synth_photo(rng, H, W) for _ in range(B)]
+    d_rgb = torch.from_numpy(np.concatenate([im.reshape(-1) for im in imgs])).cuda()
+    sizes = [(H, W)] * B
+
+    # ---- the engine's CRF stage on maps of its own making
+    e = Engine(C.blip_itm_small(IMG), max_batch=B, max_text_len=max(32, K + 8), stash_layer=7, bf16=True)
+    e.post_reserve(B, B * H * W, H * W, K, 0)
+    grid = IMG // 16
+    cam = rng.random((B, K + 3, grid, grid), dtype=np.float32) ** 4
+    cam[:, :, :, 2 * grid // 3:] = 0                    # a third of every image belongs to no class: the background channel is
+    d_cam = torch.from_numpy(cam).cuda()                 # neither empty nor full, and min-max leaves no 0 / 0 = NaN channel
+    e.post_prepare(sizes, [[([i], 1) for i in range(K - 1)]] * B, [list(range(K))] * B, [True] * B, rgb=d_rgb, gt=None, want_crf=True)
+    e.merge_tokens(d_cam)
+    e.threshold_upsample(0.15, False)
+    e.blur_minmax()
+    maps = [m.clone() for m in e.post_maps("maps")]
+    if any(bool(torch.isnan(m).any()) for m in maps):
+        raise SystemExit("the engine's maps hold NaN: the timings would be those of NaN arithmetic")
+    e.densecrf()                                                                  # warm
+    # the engine's own unary rows (pixel-major, Kp floats) as (K, H*W) planes: the stand-alone runs start from the same bits
+    rows, kp = e.buffer("unary"), (K + 3) // 4 * 4
+    d_unary = torch.cat([rows[b * kp * H * W:(b + 1) * kp * H * W].view(H * W, kp)[:, :K].t().contiguous().reshape(-1) for b in range(B)])
+    torch.cuda.synchronize()
+    e.profile_enable(True)
+    for _ in range(a.reps):
+        e.densecrf()
+    n_eng, _, ms_eng = e.profile_read_stage(1)
+    e.profile_enable(False)
+    eng_call_ms = events_ms(torch, e.densecrf, a.reps)                            # unary stage + mean-field
+    q_eng = [q.clone() for q in e.post_q()]
+    lab_eng = e.split_labels(e.remap_hist(True))
+    e.close()
+
+    # ---- the same problem through the stand-alone solver
+    solver = crf.DenseCRF(B, B * H * W, H * W, K)
+
+    def set_all():
+        solver.set_batch(d_unary, d_rgb, sizes, [K] * B)
+    set_all()
+    lab, q = solver.infer()                                                       # warm
+    # same unary bits, same kernels, same order: the marginals and labels of the two paths must be identical
+    q_err = max(float((q[b].reshape(K, -1).t() - q_eng[b]).abs().max()) for b in range(B))
+    lab_diff = sum(int((lab[b] != lab_eng[b]).sum()) for b in range(B))
+    batch_set_ms = events_ms(torch, set_all, a.reps)
+    batch_infer_ms = events_ms(torch, lambda: solver.infer(want_q=True), a.reps)
+    batch_infer_labels_ms = events_ms(torch, lambda: solver.infer(want_q=False), a.reps)
+    batch_meanfield_ms = events_ms(torch, lambda: solver.infer(want_q=False, want_labels=False), a.reps)
+    U0 = d_unary[:K * H * W].reshape(K, H * W).cpu().numpy()
+    t0 = time.perf_counter()
+    for _ in range(a.reps):
+        solver.run([U0.reshape(K, H, W)] * B, imgs)[0][0].cpu()
+    batch_run_wall_ms = (time.perf_counter() - t0) / a.reps * 1e3
+    bytes_batch = solver.allocated_bytes()
+    solver.close()
+
+    # ---- one image: through the shim (host to host), and the two device phases by events
+    sys.path.insert(0, os.path.join(ROOT, "pnp-ovss_amd", "shims"))
+    import pydensecrf.densecrf as dcrf
+    assert sys.modules["pydensecrf"].__pnp_ovss_shim__
+
+    def shim_call():
+        d = dcrf.DenseCRF2D(W, H, K)
+        d.setUnaryEnergy(U0)
+        d.addPairwiseGaussian(sxy=3, compat=7)
+        d.addPairwiseBilateral(sxy=50, srgb=5, rgbim=imgs[0], compat=10)
+        Q = np.array(d.inference(10)).reshape((K, H, W))
+        return np.argmax(Q, axis=0)
+    shim_call()                                                                   # warm (creates the module's solver)
+    t0 = time.perf_counter()
+    for _ in range(a.reps):
+        shim_call()
+    shim_wall_ms = (time.perf_counter() - t0) / a.reps * 1e3
+    one = crf.DenseCRF(1, H * W, H * W, K)
+    d_u0, d_rgb0 = d_unary[:K * H * W], d_rgb[:3 * H * W]
+    one.set_batch(d_u0, d_rgb0, [(H, W)], [K])
+    one.infer()
+    one_set_ms = events_ms(torch, lambda: one.set_batch(d_u0, d_rgb0, [(H, W)], [K]), a.reps)
+    one_infer_ms = events_ms(torch, lambda: one.infer(want_q=True), a.reps)
+    one.close()
+
+    # ---- the oracle on one host core, same single image
+    zeros = np.zeros((K, H, W), np.float32)
+    t0 = time.perf_counter()
+    for _ in range(a.oracle_reps):
+        OP.densecrf_variant(imgs[0], zeros, variant=0, unary=U0.reshape(K, H, W))
+    oracle_ms = (time.perf_counter() - t0) / a.oracle_reps * 1e3
+
+    rec = dict(images=B, size=[H, W], labels=K, iters=10, reps=a.reps,
+               one_image=dict(shim_host_to_host_ms=shim_wall_ms, set_batch_events_ms=one_set_ms, infer_events_ms=one_infer_ms),
+               batch=dict(run_wall_ms=batch_run_wall_ms, set_batch_events_ms=batch_set_ms, infer_events_ms=batch_infer_ms,
+                          infer_labels_only_events_ms=batch_infer_labels_ms, meanfield_only_events_ms=batch_meanfield_ms,
+                          allocated_bytes=bytes_batch),
+               engine=dict(meanfield_stage_ms=ms_eng / max(n_eng, 1), densecrf_call_events_ms=eng_call_ms, runs=int(n_eng)),
+               oracle_one_core_one_image_ms=oracle_ms,
+               agreement=dict(max_abs_q_standalone_vs_engine=q_err, labels_differing=lab_diff, pixels=B * H * W,
+                              bit_identical=bool(q_err == 0.0 and lab_diff == 0)),
+               note="oracle_one_core_one_image_ms is oracle/densecrf_ref.c, the project's own C restatement of the mean-field, on "
+                    "one host core: the only stand-in for pydensecrf that runs where pydensecrf cannot be installed; it is NOT "
+                    "pydensecrf.  set_batch_events_ms spans the unary ingest and both lattice builds with their read-backs "
+                    "(the Gaussian lattice is reused after the first call); infer_events_ms = mean-field + fused labels + "
+                    "marginals out; meanfield_only = infer with neither output; engine.meanfield_stage_ms = the engine's stage "
+                    "profile around the same iteration kernels; run_wall_ms = DenseCRF.run from numpy inputs to the first "
+                    "label map on the host")
+    line = json.dumps(rec)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
