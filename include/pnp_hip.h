@@ -246,6 +246,44 @@ int pnp_crf_set_batch(pnp_crf* c, const pnp_crf_batch* batch, float pos_xy, floa
  * out like d_unary; d_labels (may be NULL): uint8 argmax over the labels -- first maximum, a NaN wins, as np.argmax --
  * concatenated H_b * W_b.  May be called repeatedly on one batch; allocates nothing and does not synchronise. */
 int pnp_crf_infer(pnp_crf* c, int32_t iters, float pos_w, float bi_w, float* d_q, uint8_t* d_labels, void* stream);
+/* ---- beyond the reference's own call: per-axis widths, label-compatibility matrices, stepwise inference, KL divergence ----
+ * What pydensecrf users do besides (sxy = (sx, sy), srgb = (sr, sg, sb); compat as a vector or matrix; startInference /
+ * stepInference / klDivergence).  Still one Gaussian and one bilateral term, DIAG_KERNEL, NORMALIZE_SYMMETRIC.
+ *
+ * pnp_crf_set_batch_aniso: pnp_crf_set_batch with one width per feature axis -- Gaussian features (x / pos_xy[0],
+ * y / pos_xy[1]), bilateral (x / bi_xy[0], y / bi_xy[1], r / bi_rgb[0], g / bi_rgb[1], b / bi_rgb[2]).  Equal widths build the
+ * lattices of pnp_crf_set_batch bit for bit.  The Gaussian lattice is kept while the sizes and BOTH its widths stay the same. */
+int pnp_crf_set_batch_aniso(pnp_crf* c, const pnp_crf_batch* batch, const float pos_xy[2], const float bi_xy[2], const float bi_rgb[3],
+                            void* stream);
+/* Label compatibility of term 0 (Gaussian) or 1 (bilateral), as MESSAGE WEIGHTS, used as given: with msg_t[k] the term's
+ * filtered, normalised marginal of label k at a pixel, the update is
+ *     logit[l] = (-U[l] + sum_k Mg[l][k] msg_g[k]) + sum_k Mb[l][k] msg_b[k],   Q = softmax(logit)
+ * each sum in one fp32 accumulator, k ascending, products and sums rounded separately.  PNP_CRF_COMPAT_SCALAR: M = w I with the
+ * w of the call (pos_w / bi_w; Potts, the default; host_values and K are not read); _DIAGONAL: host_values[K], M = diag(v);
+ * _MATRIX: host_values[K * K] row-major, M[l][k] = host_values[l * K + k].  M = w I gives the scalar kind's marginals bit for
+ * bit.  The values are copied into the solver (synchronises the device) and hold until changed, across batches.  A vector or
+ * matrix needs K labels in every image of the batch: otherwise pnp_crf_infer / _step / _kl return PNP_ERR_ARG, and the solver
+ * stays usable.  While both terms are scalar the Potts kernel runs and nothing differs from before.
+ * Sign and symmetry are the caller's: densecrf's PottsCompatibility(w) is M = w I here; its DiagonalCompatibility(v) and
+ * MatrixCompatibility(m) are M = diag(-v) and M = -(m + m^T) / 2 as this project reads densecrf (shims/general/pydensecrf converts) --
+ * pinned by nothing the reference holds (oracle/README.md). */
+enum { PNP_CRF_COMPAT_SCALAR = 0, PNP_CRF_COMPAT_DIAGONAL = 1, PNP_CRF_COMPAT_MATRIX = 2 };
+int pnp_crf_set_compat(pnp_crf* c, int32_t term, int32_t kind, const float* host_values, int32_t K);
+/* Stepwise inference on the batch of the last set_batch.  pnp_crf_start: Q = softmax(-U).  pnp_crf_step: n >= 0 more mean-field
+ * updates from the current Q (start + step(a) + step(b) leaves the Q of pnp_crf_infer(a + b), bit for bit).  pnp_crf_read: the
+ * current marginals (d_q) and their argmax (d_labels), laid out as pnp_crf_infer's outputs; either may be NULL.
+ * pnp_crf_infer leaves the stepwise state equal to its result.  PNP_ERR_STATE while no batch is set, and from step / read /
+ * kl while neither start nor infer has run on this batch.  None of them allocates; start / step / read do not synchronise. */
+int pnp_crf_start(pnp_crf* c, void* stream);
+int pnp_crf_step(pnp_crf* c, int32_t n, float pos_w, float bi_w, void* stream);
+int pnp_crf_read(pnp_crf* c, float* d_q, uint8_t* d_labels, void* stream);
+/* KL divergence of the current Q, one value per image into h_out_per_image[B] (host):
+ *     sum_il Q log(max(Q, 1e-20)) + sum_il Q U - sum_t sum_il Q[i][l] acc_t[i][l],   acc_t[l] = sum_k M_t[l][k] msg_t[k] at this Q
+ * Costs one filter pass per term; Q is not changed.  Products in fp32, the sum in fp64 in a fixed order (per pixel; then runs
+ * of 256 pixels in pixel order; then the runs of an image in order), so the value is deterministic and does not depend on the
+ * launch grid.  Synchronises.  This is densecrf's klDivergence as this project reads it (up to the constant densecrf leaves
+ * out as well); like the rest of the CRF it is pinned by nothing the reference holds (oracle/README.md). */
+int pnp_crf_kl(pnp_crf* c, float pos_w, float bi_w, double* h_out_per_image, void* stream);
 
 /* ---- input side ("next" row: the tensors the reference's datasets hand to the model) -------
  * Dataset.py:434-443: transforms.Resize((S, S), BICUBIC) on the PIL image -> ToTensor -> Normalize(mean, std).

@@ -69,8 +69,8 @@ __device__ __forceinline__ void unpack_key(uint64_t k, int* c) {
 // Mirrors oracle/densecrf_ref.c::lattice_init statement by statement (fp contraction is off for
 // this translation unit) so barycentric weights and keys are bit-identical.
 template <int D>
-__global__ void lattice_embed_kernel(const PostDesc* __restrict__ imgs, const uint8_t* __restrict__ rgb, float sxy, float srgb,
-                                     float* __restrict__ bary, uint64_t* __restrict__ keys, uint32_t* __restrict__ vals,
+__global__ void lattice_embed_kernel(const PostDesc* __restrict__ imgs, const uint8_t* __restrict__ rgb, float sx, float sy, float sr,
+                                     float sg, float sb, float* __restrict__ bary, uint64_t* __restrict__ keys, uint32_t* __restrict__ vals,
                                      int* __restrict__ range_err) {
     const int b = blockIdx.y;
     const PostDesc im = imgs[b];
@@ -84,13 +84,13 @@ __global__ void lattice_embed_kernel(const PostDesc* __restrict__ imgs, const ui
     for (int pix = blockIdx.x * blockDim.x + threadIdx.x; pix < n; pix += gridDim.x * blockDim.x) {
         const int y = pix / im.W, x = pix - y * im.W;
         float f[D];
-        f[0] = __fdiv_rn((float)x, sxy);
-        f[1] = __fdiv_rn((float)y, sxy);
+        f[0] = __fdiv_rn((float)x, sx);
+        f[1] = __fdiv_rn((float)y, sy);
         if constexpr (D == 5) {
             const uint8_t* c = rgb + ((size_t)im.pix0 + pix) * 3;
-            f[2] = __fdiv_rn((float)c[0], srgb);
-            f[3] = __fdiv_rn((float)c[1], srgb);
-            f[4] = __fdiv_rn((float)c[2], srgb);
+            f[2] = __fdiv_rn((float)c[0], sr);
+            f[3] = __fdiv_rn((float)c[1], sg);
+            f[4] = __fdiv_rn((float)c[2], sb);
         }
         float elevated[D + 1], rem0[D + 1], barycentric[D + 2];
         int rank[D + 1];
@@ -909,6 +909,272 @@ void crf_update_kernel(const CrfLattice Lg, const CrfLattice Lb, const PostDesc*
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// The update with label-compatibility MATRICES (the stand-alone solver, crf_op.hip; the engine's Potts runs never come here):
+//   acc_t[l] = sum_k M_t[l][k] * msg_t[k]   (one fp32 accumulator per output, k ascending, multiply and add rounded
+//                                            separately: no FMA, no MFMA -- the order of the sum is part of the contract)
+//   logit[l] = (-U[l] + acc_g[l]) + acc_b[l],   Q = softmax(logit)
+// msg_t[k] is what crf_update_kernel forms per term -- (sum_v (bary_v * val_v[k]) * alpha_t) * norm_t, same instruction
+// sequence and vertex order -- so M_t = w * I gives the Potts kernel's logits value for value (the other products are exact
+// zeros).  Same TW x TH block tiles, LDS-staged slice records, XCD-affine sweep and 16-byte global I/O as crf_update_kernel.
+// Phase 1 (lanes over (pixel, 16-byte chunk) items, as there) puts -U into the logit tile and the two message rows of every
+// pixel into LDS (row stride Kp + 1: odd, so the per-pixel reads of phase 2 hit 32 distinct banks per half wave).  Phase 2 does
+// the two K x K products with lane = pixel: a wave owns 64 pixels (32 where a tile has only 32: half the lanes idle) and a
+// block of CRF_CL labels l at a time, so every M_t[l][k] is the same in all lanes and is read with scalar loads from global
+// memory (two 150 x 150 matrices are 180 KB: not LDS material), and one LDS read of msg_t[k] feeds CRF_CL accumulators.  The
+// matrices arrive TRANSPOSED (MgT[k * ldm + l] = M_g[l][k]; ldm a multiple of CRF_CL, zero beyond K), so the CRF_CL weights a
+// block needs for one k are 32 consecutive bytes -- one scalar load and one pointer per term -- and a block that reaches past K
+// multiplies by the pad's zeros into accumulators nobody reads.  The
+// blocks of l are dealt round the 4 / (TP / 64) waves that share a pixel set.  Then softmax, labels and the zeroing of the pad
+// floats with crf_update_kernel's thread-per-row arithmetic, and the same store loop.
+// Tile size (crf_update_compat): 256 / 128 pixels while the three LDS rows per pixel stay under 64 KB (Kp <= 12 / <= 32), 64
+// up to Kp = 200, 32 beyond (three rows of 257 floats x 64 pixels would pass the CU's 160 KB).
+// KL = true: no update.  The tile holds Q instead of -U and a fourth row per pixel holds U; phase 2 ends in the pixel's term of
+// pnp_crf_kl, sum_l q log(max(q, 1e-20)) + q U[l] - q acc_g[l] - q acc_b[l] (products fp32, summed in fp64 in this order: l
+// ascending inside a wave's label blocks, then the waves of the pixel in order), written to kl_pix[pixel].
+// Compiler's resource report for gfx950 (-Rpass-analysis=kernel-resource-usage): update form 92 VGPRs, 106 SGPRs, no scratch
+// (101 scalar registers spilled to vector-register lanes); KL form 99 / 106, no scratch.  Five (KL: four)
+// waves per SIMD by registers, but the tile's LDS decides: 35 KB at K = 3
+// (256 pixels) and 33 KB at K = 33 (64 pixels) leave four workgroups = four waves per SIMD, 48 KB at K = 21 (128 pixels) three,
+// 120 KB at K = 150 (64 pixels) one.  The inner loop is packed fp32 multiplies and adds (v_pk_mul_f32 / v_pk_add_f32, each
+// rounded on its own) fed by s_load_dwordx8 and ds_read2_b32.  No rate is claimed: tools/crf_bench.py --compat matrix measures.
+constexpr int CRF_CL = 8;
+template <bool KL>
+__global__ __launch_bounds__(256) void crf_update_compat_kernel(const CrfLattice Lg, const CrfLattice Lb, const PostDesc* __restrict__ imgs,
+                                                                const float* __restrict__ vg, const float* __restrict__ vb,
+                                                                const float* __restrict__ norm_g, const float* __restrict__ norm_b,
+                                                                const float* __restrict__ unary, float* Q, const float* __restrict__ MgT,
+                                                                const float* __restrict__ MbT, int ldm, float alpha_g, float alpha_b,
+                                                                int img0, int nimg, int TP, const CrfLabelOut lout,
+                                                                double* __restrict__ kl_pix) {
+    extern __shared__ __attribute__((aligned(16))) float tile[];        // [TP][Kp + 1] x 3 (KL: x 4), then the slice records [TP][20]
+    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, bpx = gridDim.x >> 3;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int TW = crf_tile_w(TP), TH = TP / TW;                        // TP = 32 .. 256, a power of two
+    const int tw_shift = __ffs(TW) - 1;
+    // phase 2: WPS waves cover the pixels of a tile, NG = 4 / WPS waves share a pixel set and split the labels
+    const int WPS = TP > 64 ? TP >> 6 : 1, NG = 4 / WPS;
+    const int px2 = (wave % WPS) * 64 + lane, lg = wave / WPS;
+    const bool act = px2 < TP;
+    const int pxc = act ? px2 : TP - 1;                                 // idle lanes read a valid row and write nothing
+    int b, part, parts;
+    for (int wi = 0; xcd_work(wi, xcd, img0, nimg, b, part, parts); wi++) {
+        const PostDesc im = imgs[b];
+        const int K = im.K, Kp = im.Kp, K4 = Kp >> 2, ldt = Kp + 1;
+        f32x4* Q4 = reinterpret_cast<f32x4*>(Q + im.qoff);
+        const int lo_g = Lg.idbase[b], lo_b = Lb.idbase[b];
+        const int tiles_x = (im.W + TW - 1) / TW, tiles_y = (im.H + TH - 1) / TH, ntiles = tiles_x * tiles_y;
+        const int tfirst = (int)((long)ntiles * part / parts), tend = (int)((long)ntiles * (part + 1) / parts);
+        const char* const Ub = reinterpret_cast<const char*>(unary + im.qoff);
+        const char* const Gb = reinterpret_cast<const char*>(vg + im.voff[0]);
+        const char* const Bb = reinterpret_cast<const char*>(vb + im.voff[1]);
+        const uint32_t rowb = (uint32_t)K4 * 16u;
+        float* const msg_g = tile + TP * ldt;
+        float* const msg_b = msg_g + TP * ldt;
+        float* const ubuf = msg_b + TP * ldt;                                          // (KL only)
+        int* const rec_ob = reinterpret_cast<int*>(msg_b + (KL ? 2 : 1) * TP * ldt);   // [TP][6] bilateral ids, then ...
+        float* const rec_wb = reinterpret_cast<float*>(rec_ob + TP * 6);
+        int* const rec_og = reinterpret_cast<int*>(rec_wb + TP * 6);
+        float* const rec_wg = reinterpret_cast<float*>(rec_og + TP * 3);
+        float* const rec_nb = rec_wg + TP * 3;
+        float* const rec_ng = rec_nb + TP;
+        const int q256 = 256 / K4, r256 = 256 - q256 * K4;
+        const int pl0 = tid / K4, c0 = tid - pl0 * K4;
+        for (int tl = tfirst + slot; tl < tend; tl += bpx) {
+            const int ty = tl / tiles_x, tx = tl - ty * tiles_x;
+            const int x0 = tx * TW, y0 = ty * TH;
+            auto pixel_of = [&](int pl) {
+                const int x = x0 + (pl & (TW - 1)), y = y0 + (pl >> tw_shift);
+                return (y < im.H ? y : im.H - 1) * im.W + (x < im.W ? x : im.W - 1);
+            };
+            auto inside = [&](int pl) { return x0 + (pl & (TW - 1)) < im.W && y0 + (pl >> tw_shift) < im.H; };
+            for (int pl = tid; pl < TP; pl += 256) {                     // slice records, one pixel per thread
+                const size_t g = (size_t)im.pix0 + pixel_of(pl);
+#pragma unroll
+                for (int v = 0; v < 6; v++) {
+                    rec_ob[pl * 6 + v] = Lb.offset[g * 6 + v] - lo_b;
+                    rec_wb[pl * 6 + v] = Lb.bary[g * 6 + v];
+                }
+#pragma unroll
+                for (int v = 0; v < 3; v++) {
+                    rec_og[pl * 3 + v] = Lg.offset[g * 3 + v] - lo_g;
+                    rec_wg[pl * 3 + v] = Lg.bary[g * 3 + v];
+                }
+                rec_nb[pl] = norm_b[g];
+                rec_ng[pl] = norm_g[g];
+            }
+            __syncthreads();
+            {   // phase 1: -U (KL: Q, U) and the two message rows of every pixel -> LDS
+                int pl = pl0, c = c0;
+                for (int item = tid; item < TP * K4; item += 256) {
+                    const int px = pixel_of(pl);
+                    const uint32_t cofs = (uint32_t)c * 16u;
+                    const f32x4 u = ld_stream(reinterpret_cast<const f32x4*>(Ub + (__umul24((uint32_t)px, rowb) + cofs)));
+                    f32x4 t = {-u[0], -u[1], -u[2], -u[3]};
+                    if (KL) t = Q4[(size_t)px * K4 + c];
+                    f32x4 vg3[3], vb6[6];
+#pragma unroll
+                    for (int v = 0; v < 3; v++)
+                        vg3[v] = *reinterpret_cast<const f32x4*>(Gb + (__umul24((uint32_t)rec_og[pl * 3 + v], rowb) + cofs));
+#pragma unroll
+                    for (int v = 0; v < 6; v++)
+                        vb6[v] = *reinterpret_cast<const f32x4*>(Bb + (__umul24((uint32_t)rec_ob[pl * 6 + v], rowb) + cofs));
+                    f32x4 og = {0.f, 0.f, 0.f, 0.f}, ob = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                    for (int v = 0; v < 3; v++) {
+                        const float wv = rec_wg[pl * 3 + v];
+#pragma unroll
+                        for (int i = 0; i < 4; i++) og[i] = __fadd_rn(og[i], __fmul_rn(__fmul_rn(wv, vg3[v][i]), alpha_g));
+                    }
+#pragma unroll
+                    for (int v = 0; v < 6; v++) {
+                        const float wv = rec_wb[pl * 6 + v];
+#pragma unroll
+                        for (int i = 0; i < 4; i++) ob[i] = __fadd_rn(ob[i], __fmul_rn(__fmul_rn(wv, vb6[v][i]), alpha_b));
+                    }
+                    const float nrg = rec_ng[pl], nrb = rec_nb[pl];
+#pragma unroll
+                    for (int i = 0; i < 4; i++) {
+                        tile[pl * ldt + 4 * c + i] = t[i];
+                        msg_g[pl * ldt + 4 * c + i] = __fmul_rn(og[i], nrg);
+                        msg_b[pl * ldt + 4 * c + i] = __fmul_rn(ob[i], nrb);
+                        if (KL) ubuf[pl * ldt + 4 * c + i] = u[i];
+                    }
+                    pl += q256;
+                    c += r256;
+                    if (c >= K4) {
+                        c -= K4;
+                        pl++;
+                    }
+                }
+            }
+            __syncthreads();
+            // phase 2: lane = pixel, CRF_CL labels per pass over k; M rows through scalar loads (l0, K, ldm are wave-uniform)
+            double kl = 0.0;
+            {
+                const float* const xg = msg_g + pxc * ldt;
+                const float* const xb = msg_b + pxc * ldt;
+                for (int l0 = lg * CRF_CL; l0 < K; l0 += NG * CRF_CL) {
+                    float ag[CRF_CL], ab[CRF_CL];
+#pragma unroll
+                    for (int i = 0; i < CRF_CL; i++) ag[i] = ab[i] = 0.f;
+                    // the block's weights of one k: 32 consecutive bytes of the transposed matrix (labels past K: its zero pad)
+                    const float* tg = MgT + l0;
+                    const float* tb = MbT + l0;
+#pragma unroll 4
+                    for (int k = 0; k < K; k++) {
+                        const float mg = xg[k], mb = xb[k];
+#pragma unroll
+                        for (int i = 0; i < CRF_CL; i++) {
+                            ag[i] = __fadd_rn(ag[i], __fmul_rn(tg[i], mg));
+                            ab[i] = __fadd_rn(ab[i], __fmul_rn(tb[i], mb));
+                        }
+                        tg += ldm;
+                        tb += ldm;
+                    }
+#pragma unroll
+                    for (int i = 0; i < CRF_CL; i++) {
+                        if (act && l0 + i < K) {
+                            float* const t = tile + px2 * ldt + l0 + i;
+                            if (KL) {
+                                const float q = *t, qc = q > 1e-20f ? q : 1e-20f;
+                                kl += (double)__fmul_rn(q, pnp_logf(qc));
+                                kl += (double)__fmul_rn(q, ubuf[px2 * ldt + l0 + i]);
+                                kl -= (double)__fmul_rn(q, ag[i]);
+                                kl -= (double)__fmul_rn(q, ab[i]);
+                            } else {
+                                *t = __fadd_rn(__fadd_rn(*t, ag[i]), ab[i]);
+                            }
+                        }
+                    }
+                }
+            }
+            __syncthreads();
+            if (KL) {
+                double* const part_kl = reinterpret_cast<double*>(msg_g);      // [NG][TP]: the message rows are spent
+                if (act) part_kl[lg * TP + px2] = kl;
+                __syncthreads();
+                if (tid < TP && inside(tid)) {
+                    double e = 0.0;
+                    for (int g = 0; g < NG; g++) e += part_kl[g * TP + tid];
+                    kl_pix[(size_t)im.pix0 + pixel_of(tid)] = e;
+                }
+                __syncthreads();
+                continue;
+            }
+            // softmax, label, pad: element by element the arithmetic of crf_update_kernel's thread-per-row form.  The two steps
+            // that depend on the order along a row -- the maximum as that form finds it (a NaN wins) and the sum, k ascending --
+            // stay with one thread per row; the exponentials and the divisions, pure functions of one element, go to the lanes of
+            // phase 2 (pixel, wave of the pixel set), so a 64-pixel tile keeps four waves busy with them, not one.  Row maximum
+            // and sum pass through the spent normaliser slots of the slice records
+            if (tid < TP) {
+                const float* row = tile + tid * ldt;
+                float m = row[0];
+                for (int k = 1; k < K; k++) {
+                    const float v = row[k];
+                    if (v > m || v != v) m = v;
+                }
+                rec_ng[tid] = m;
+            }
+            __syncthreads();
+            if (act) {
+                float* row = tile + px2 * ldt;
+                const float m = rec_ng[px2];
+                for (int k = lg; k < K; k += NG) row[k] = pnp_expf(__fsub_rn(row[k], m));
+            }
+            __syncthreads();
+            if (tid < TP) {
+                const float* row = tile + tid * ldt;
+                float s = 0.f;
+                for (int k = 0; k < K; k++) s = __fadd_rn(s, row[k]);
+                rec_ng[tid] = s;
+            }
+            __syncthreads();
+            if (act) {
+                float* row = tile + px2 * ldt;
+                const float s = rec_ng[px2];
+                for (int k = lg; k < K; k += NG) row[k] = __fdiv_rn(row[k], s);
+            }
+            __syncthreads();
+            if (tid < TP) {
+                const int px = tid;
+                float* row = tile + px * ldt;
+                if (lout.lab[0]) {                                       // first maximum, NaN counts as maximum (np.argmax)
+                    int best = 0;
+                    float bv = row[0];
+                    for (int k = 1; k < K; k++) {
+                        const float v = row[k];
+                        if (bv == bv && (v > bv || v != v)) {
+                            best = k;
+                            bv = v;
+                        }
+                    }
+                    if (inside(px)) lout.lab[0][lout.label_off[b] + pixel_of(px)] = (uint8_t)lout.lut[b * lout.lut_stride + best];
+                }
+                for (int k = K; k < Kp; k++) row[k] = 0.f;               // pad floats stay zero
+            }
+            __syncthreads();
+            {
+                int pl = pl0, c = c0;
+                for (int item = tid; item < TP * K4; item += 256) {
+                    if (inside(pl)) {
+                        const float* r = tile + pl * ldt + 4 * c;
+                        st_stream(Q4 + (size_t)pixel_of(pl) * K4 + c, f32x4{r[0], r[1], r[2], r[3]});
+                    }
+                    pl += q256;
+                    c += r256;
+                    if (c >= K4) {
+                        c -= K4;
+                        pl++;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
+
 // ---- spatial renumbering.  The key sort numbers lattice points in (colour-major) key order; the
 // iteration kernels are gather-bound, so the points of each image are renumbered by the position of their
 // FIRST contributor pixel along a Z-order curve over the image: contributors, simplex vertices of neighbouring
@@ -1031,16 +1297,17 @@ static inline int ok() { return hipGetLastError() == hipSuccess ? PNP_OK : PNP_E
 
 size_t crf_sort_temp_bytes(size_t max_entries) { return sort_temp_bytes(max_entries) + 256; }
 
-// Build one lattice (D = 2: Gaussian xy/sxy ; D = 5: bilateral xy/sxy, rgb/srgb) for images [0,B).  The scratch arrays and the
-// roles each of them takes in turn: CrfBuildScratch (kernels.h).
-int crf_build_lattice(int D, const CrfLattice& L, const PostDesc* d_imgs, const PostDesc* h_imgs, const uint8_t* d_rgb, float sxy, float srgb,
-                      int B, size_t ent_total, int max_pixels, const CrfBuildScratch& sc, int* h_range_err, int* h_points,
+// Build one lattice (D = 2: Gaussian x/sx, y/sy ; D = 5: bilateral x/sx, y/sy, r/sr, g/sg, b/sb) for images [0,B): sxy = (sx, sy),
+// srgb = (sr, sg, sb), one width per feature axis.  The scratch arrays and the roles each of them takes in turn: CrfBuildScratch
+// (kernels.h).
+int crf_build_lattice(int D, const CrfLattice& L, const PostDesc* d_imgs, const PostDesc* h_imgs, const uint8_t* d_rgb, const float sxy[2],
+                      const float srgb[3], int B, size_t ent_total, int max_pixels, const CrfBuildScratch& sc, int* h_range_err, int* h_points,
                       hipStream_t s) {
     const int nb = (max_pixels + 255) / 256 < 512 ? (max_pixels + 255) / 256 : 512;
     if (D == 2)
-        hipLaunchKernelGGL((lattice_embed_kernel<2>), dim3(nb, B), dim3(256), 0, s, d_imgs, d_rgb, sxy, srgb, L.bary, sc.keys_a, sc.vals_a, sc.range_err);
+        hipLaunchKernelGGL((lattice_embed_kernel<2>), dim3(nb, B), dim3(256), 0, s, d_imgs, d_rgb, sxy[0], sxy[1], srgb[0], srgb[1], srgb[2], L.bary, sc.keys_a, sc.vals_a, sc.range_err);
     else if (D == 5)
-        hipLaunchKernelGGL((lattice_embed_kernel<5>), dim3(nb, B), dim3(256), 0, s, d_imgs, d_rgb, sxy, srgb, L.bary, sc.keys_a, sc.vals_a, sc.range_err);
+        hipLaunchKernelGGL((lattice_embed_kernel<5>), dim3(nb, B), dim3(256), 0, s, d_imgs, d_rgb, sxy[0], sxy[1], srgb[0], srgb[1], srgb[2], L.bary, sc.keys_a, sc.vals_a, sc.range_err);
     else
         return PNP_ERR_ARG;
     if (B > (1 << IMG_BITS)) return PNP_ERR_ARG;
@@ -1232,6 +1499,42 @@ int crf_update(const CrfLattice& Lg, const CrfLattice& Lb, const PostDesc* d_img
     else
         hipLaunchKernelGGL(crf_update_kernel<false>, dim3(nbu), dim3(256), smem, s, Lg, Lb, d_imgs, vg, vb, norm_g, norm_b, unary, Q,
                            w_g, w_b, crf_alpha(2), crf_alpha(5), pairwise, img0, nimg, (int)tp, tile_w, labels);
+    return ok();
+}
+
+// Pixels per tile of crf_update_compat_kernel for rows of up to max_kp floats (see there): a multiple of the 64 pixels a wave
+// takes in phase 2 wherever the CU's LDS holds that many
+int crf_compat_tile_pixels(int max_kp, bool kl) {
+    const size_t per_pixel = ((size_t)(kl ? 4 : 3) * (max_kp + 1) + 20) * sizeof(float);
+    int tp = 256;
+    while (tp > 64 && tp * per_pixel > 64 * 1024) tp >>= 1;
+    if (tp * per_pixel > 158 * 1024) tp = 32;
+    return tp;
+}
+
+// Q <- softmax(-U + M_g msg_g + M_b msg_b) (kl_pix null), or the per-pixel terms of the KL divergence at the current Q into
+// kl_pix (Q is only read).  MgT / MbT: the matrices transposed, MgT[k * ldm + l] = M_g[l][k], ldm >= max_kp a multiple of
+// CRF_CL, zeros wherever l or k is not a label
+int crf_update_compat(const CrfLattice& Lg, const CrfLattice& Lb, const PostDesc* d_imgs, int img0, int nimg, const float* vg,
+                      const float* vb, const float* norm_g, const float* norm_b, const float* unary, float* Q, const float* MgT,
+                      const float* MbT, int ldm, int max_kp, hipStream_t s, const CrfLabelOut& labels, double* kl_pix) {
+    const bool kl = kl_pix != nullptr;
+    const int tp = crf_compat_tile_pixels(max_kp, kl);
+    const size_t smem = (size_t)tp * ((size_t)(kl ? 4 : 3) * (max_kp + 1) + 20) * sizeof(float);
+    if (max_kp < 4 || max_kp > 256 || ldm < max_kp || ldm % CRF_CL != 0 || smem > 160 * 1024) return PNP_ERR_ARG;
+    const void* const kern = kl ? reinterpret_cast<const void*>(crf_update_compat_kernel<true>)
+                                : reinterpret_cast<const void*>(crf_update_compat_kernel<false>);
+    if (smem > 64 * 1024) {
+        if (hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return PNP_ERR_HIP;
+    }
+    // resident workgroups for this tile's LDS bytes (a host-side calculation; the solver launches a handful of sizes)
+    const int nb = kl ? resident_grid(crf_update_compat_kernel<true>, 256, smem) : resident_grid(crf_update_compat_kernel<false>, 256, smem);
+    if (kl)
+        hipLaunchKernelGGL(crf_update_compat_kernel<true>, dim3(nb), dim3(256), smem, s, Lg, Lb, d_imgs, vg, vb, norm_g, norm_b, unary, Q,
+                           MgT, MbT, ldm, crf_alpha(2), crf_alpha(5), img0, nimg, tp, labels, kl_pix);
+    else
+        hipLaunchKernelGGL(crf_update_compat_kernel<false>, dim3(nb), dim3(256), smem, s, Lg, Lb, d_imgs, vg, vb, norm_g, norm_b, unary, Q,
+                           MgT, MbT, ldm, crf_alpha(2), crf_alpha(5), img0, nimg, tp, labels, kl_pix);
     return ok();
 }
 

@@ -5,8 +5,12 @@
 // Reused as they are (kernels.h): crf_build_lattice, crf_lattice_norm, crf_filter, crf_update and their PostDesc layout -- one
 // channel group per row, the whole batch as one chunk, driven exactly as post.hip's crf_iterate drives them.  New here: the
 // solver, and the two layout kernels between the caller's channel-major (K, H*W) planes (pydensecrf's layout) and the
-// pixel-major Kp-float rows the mean-field kernels work on.  No arithmetic happens in this file: the planes <-> rows kernels
-// move floats, and the labels come from the last update's own argmax (CrfLabelOut with an identity table).
+// pixel-major Kp-float rows the mean-field kernels work on.  The planes <-> rows kernels move floats, and the labels come from the
+// last update's own argmax (CrfLabelOut with an identity table).
+// Beyond the reference's call (include/pnp_hip.h): per-axis widths (pnp_crf_set_batch_aniso), label-compatibility vectors and
+// matrices (pnp_crf_set_compat: crf_update_compat of crf.hip takes the update over from crf_update as soon as a term is not
+// scalar), stepwise inference (pnp_crf_start / _step / _read; pnp_crf_infer is start + step + emit) and the KL divergence
+// (pnp_crf_kl), whose ordered fp64 sums over the per-pixel terms are the only arithmetic of this file.
 #include <algorithm>
 #include <cstdarg>
 #include <cstdio>
@@ -161,6 +165,39 @@ static int crf_planes_rows(bool to_rows, const PostDesc* desc, float* planes, fl
     return hipGetLastError() == hipSuccess ? PNP_OK : PNP_ERR_HIP;
 }
 
+// ------------------------------------------------------------------------------------------ KL divergence: the two-stage sum
+// kl_pix holds one fp64 term per pixel (crf_update_compat_kernel<true>).  Stage 1: one partial per run of 256 consecutive
+// pixels of an image, added in pixel order by one thread; stage 2: one thread per image adds its partials in order.  The
+// order is a function of the image alone, never of the grid.  Partials of image b start at pix0 / 256 + b (>= the runs of the
+// images before it).
+constexpr int CRF_KL_RUN = 256;
+__global__ __launch_bounds__(CRF_KL_RUN) void crf_kl_partial_kernel(const PostDesc* __restrict__ desc, const double* __restrict__ kl_pix,
+                                                                   double* __restrict__ part) {
+    __shared__ double sh[CRF_KL_RUN];
+    const int b = blockIdx.y, tid = threadIdx.x;
+    const int n = desc[b].H * desc[b].W, pix0 = desc[b].pix0;
+    for (int r = blockIdx.x; r * CRF_KL_RUN < n; r += gridDim.x) {
+        const int i = r * CRF_KL_RUN + tid;
+        sh[tid] = i < n ? kl_pix[(size_t)pix0 + i] : 0.0;
+        __syncthreads();
+        if (tid == 0) {
+            double s = 0.0;
+            for (int j = 0; j < CRF_KL_RUN; j++) s += sh[j];
+            part[pix0 / CRF_KL_RUN + b + r] = s;
+        }
+        __syncthreads();
+    }
+}
+__global__ void crf_kl_final_kernel(const PostDesc* __restrict__ desc, const double* __restrict__ part, double* __restrict__ out, int B) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const int runs = (desc[b].H * desc[b].W + CRF_KL_RUN - 1) / CRF_KL_RUN;
+    const double* p = part + desc[b].pix0 / CRF_KL_RUN + b;
+    double s = 0.0;
+    for (int r = 0; r < runs; r++) s += p[r];
+    out[b] = s;
+}
+
 }  // namespace pnp
 
 // ------------------------------------------------------------------------------------------ the solver
@@ -185,7 +222,21 @@ struct pnp_crf {
     std::vector<PostDesc> desc;
     std::vector<size_t> h_label_off;
     std::vector<int> gauss_sig;                   // (H, W) list and ...
-    float gauss_xy = 0.f;                         // ... width the Gaussian lattice was last built for
+    float gauss_xy[2] = {0.f, 0.f};               // ... (sx, sy) widths the Gaussian lattice was last built for
+    // -- label compatibility of the two terms (pnp_crf_set_compat; holds until changed).  d_M: two matrices, TRANSPOSED as
+    // crf_update_compat reads them (d_M[k * ldm + l] = M[l][k]), row stride ldm = maxKp rounded up to a multiple of 8, zero
+    // padded.  A term left scalar is Potts: it takes its weight from the call, and has a matrix (w * I) on the device only
+    // while the other term has one or the KL divergence is asked for -- m_scalar_w is the weight that matrix holds
+    int kind[2] = {PNP_CRF_COMPAT_SCALAR, PNP_CRF_COMPAT_SCALAR};
+    int compat_K[2] = {0, 0};
+    int ldm = 0;
+    float* d_M = nullptr;
+    std::vector<float> h_M;                       // staging of one matrix
+    bool m_scalar[2] = {false, false};
+    float m_scalar_w[2] = {0.f, 0.f};
+    // -- stepwise inference: Q holds the marginals of the last start / step / infer on this batch
+    bool started = false;
+    double *kl_pix = nullptr, *kl_part = nullptr, *kl_out = nullptr;
     char err[512] = {0};
 };
 
@@ -283,6 +334,12 @@ int crf_reserve(pnp_crf* c) {
     c->valg_cap = TP * 3 * Kp;
     CK(c, calloc_dev(c, &c->vga, c->valg_cap));
     CK(c, calloc_dev(c, &c->vgb, c->valg_cap));
+    // compatibility matrices, and the KL divergence's per-pixel terms, per-run partials and per-image results
+    c->ldm = (c->maxKp + 7) / 8 * 8;
+    CK(c, calloc_dev(c, &c->d_M, 2 * (size_t)c->ldm * c->ldm, true));
+    CK(c, calloc_dev(c, &c->kl_pix, TP));
+    CK(c, calloc_dev(c, &c->kl_part, TP / CRF_KL_RUN + B + 1));
+    CK(c, calloc_dev(c, &c->kl_out, B));
     return PNP_OK;
 }
 
@@ -361,15 +418,33 @@ extern "C" size_t pnp_crf_allocated_bytes(const pnp_crf* c) { return c ? c->allo
 
 extern "C" const char* pnp_crf_last_error(const pnp_crf* c) { return c ? c->err : "null solver"; }
 
-extern "C" int pnp_crf_set_batch(pnp_crf* c, const pnp_crf_batch* b, float pos_xy, float bi_xy, float bi_rgb, void* stream) {
-    if (!c) return PNP_ERR_ARG;
+namespace {
+
+// The width whose feature reaches furthest in lattice units over this batch (largest extent / width): the one a key-range
+// refusal names.  w: n widths; extent: the largest value of each feature.  Equal widths: the first such
+int widest_feature(const float* w, const float* extent, int n) {
+    int at = 0;
+    for (int i = 1; i < n; i++)
+        if (extent[i] / w[i] > extent[at] / w[at]) at = i;
+    return at;
+}
+
+// pnp_crf_set_batch / pnp_crf_set_batch_aniso: pos_xy = (sx, sy) of the Gaussian term, bi_xy / bi_rgb = (sx, sy) / (sr, sg, sb)
+// of the bilateral one
+int crf_set_batch(pnp_crf* c, const pnp_crf_batch* b, const float pos_xy[2], const float bi_xy[2], const float bi_rgb[3], void* stream) {
     c->ready = false;
-    if (!c->va || !c->vgb) return cfail(c, PNP_ERR_STATE, "the solver's workspace was not allocated (pnp_crf_create failed)");
+    c->started = false;
+    if (!c->va || !c->kl_out) return cfail(c, PNP_ERR_STATE, "the solver's workspace was not allocated (pnp_crf_create failed)");
     if (!b) return cfail(c, PNP_ERR_ARG, "batch is null");
     if (b->B < 1 || b->B > c->maxB) return cfail(c, PNP_ERR_ARG, "batch of %d images, the solver holds 1..%d", b->B, c->maxB);
     if (!b->H || !b->W || !b->K || !b->d_rgb || !b->d_unary) return cfail(c, PNP_ERR_ARG, "batch has null arrays (H, W, K, d_rgb, d_unary)");
-    if (!(pos_xy > 0.f) || !(bi_xy > 0.f) || !(bi_rgb > 0.f))
-        return cfail(c, PNP_ERR_ARG, "kernel widths must be positive (pos_xy=%g, bi_xy=%g, bi_rgb=%g)", pos_xy, bi_xy, bi_rgb);
+    const bool iso = pos_xy[0] == pos_xy[1] && bi_xy[0] == bi_xy[1] && bi_rgb[0] == bi_rgb[1] && bi_rgb[0] == bi_rgb[2];
+    if (!(pos_xy[0] > 0.f) || !(pos_xy[1] > 0.f) || !(bi_xy[0] > 0.f) || !(bi_xy[1] > 0.f) || !(bi_rgb[0] > 0.f) || !(bi_rgb[1] > 0.f) ||
+        !(bi_rgb[2] > 0.f)) {
+        if (iso) return cfail(c, PNP_ERR_ARG, "kernel widths must be positive (pos_xy=%g, bi_xy=%g, bi_rgb=%g)", pos_xy[0], bi_xy[0], bi_rgb[0]);
+        return cfail(c, PNP_ERR_ARG, "kernel widths must be positive (pos_xy=(%g, %g), bi_xy=(%g, %g), bi_rgb=(%g, %g, %g))", pos_xy[0],
+                     pos_xy[1], bi_xy[0], bi_xy[1], bi_rgb[0], bi_rgb[1], bi_rgb[2]);
+    }
     if (int r = crf_layout(c, b)) return r;
     hipStream_t s = (hipStream_t)stream;
     CHIP(c, hipSetDevice(c->device));
@@ -385,7 +460,7 @@ extern "C" int pnp_crf_set_batch(pnp_crf* c, const pnp_crf_batch* b, float pos_x
     for (const PostDesc& d : c->desc) { sig.push_back(d.H); sig.push_back(d.W); }
     int range_err = 0, points = 0;
     for (int t = 0; t < 2; t++) {
-        if (t == 0 && sig == c->gauss_sig && pos_xy == c->gauss_xy) continue;
+        if (t == 0 && sig == c->gauss_sig && pos_xy[0] == c->gauss_xy[0] && pos_xy[1] == c->gauss_xy[1]) continue;
         if (t == 0) c->gauss_sig.clear();
         const size_t entries = (size_t)c->total_pix * c->lat[t].D1;
         CK(c, crf_build_lattice(c->lat[t].D1 - 1, c->lat[t], c->d_desc, c->desc.data(), b->d_rgb, t == 0 ? pos_xy : bi_xy, bi_rgb, B,
@@ -394,29 +469,122 @@ extern "C" int pnp_crf_set_batch(pnp_crf* c, const pnp_crf_batch* b, float pos_x
         if (range_err) {                          // leave no stale state behind: the next set_batch rebuilds both lattices
             c->gauss_sig.clear();
             (void)hipMemsetAsync(c->scratch.range_err, 0, sizeof(int), s);
-            if (t == 0)
-                return cfail(c, PNP_ERR_ARG, "lattice key range exceeded: a Gaussian coordinate leaves the 16-bit key; pos_xy = %g is too small for these images", pos_xy);
+            // the flag says that a coordinate left the key, not which feature drove it there: named is the width whose feature
+            // spans the most lattice units over these images
+            float extent[5] = {0.f, 0.f, 255.f, 255.f, 255.f};
+            for (const PostDesc& d : c->desc) {
+                extent[0] = std::max(extent[0], (float)(d.W - 1));
+                extent[1] = std::max(extent[1], (float)(d.H - 1));
+            }
+            if (t == 0) {
+                if (iso)
+                    return cfail(c, PNP_ERR_ARG, "lattice key range exceeded: a Gaussian coordinate leaves the 16-bit key; pos_xy = %g is too small for these images", pos_xy[0]);
+                const int at = widest_feature(pos_xy, extent, 2);
+                return cfail(c, PNP_ERR_ARG, "lattice key range exceeded: a Gaussian coordinate leaves the 16-bit key; pos_xy[%d] = %g is too small for these images", at, pos_xy[at]);
+            }
+            if (iso)
+                return cfail(c, PNP_ERR_ARG,
+                             "lattice key range exceeded: a bilateral coordinate leaves the 11-bit key (|coordinate| must stay below %d); "
+                             "bi_rgb = %g (bi_xy = %g) is too small for these images",
+                             CRF_KEY_LIMIT, bi_rgb[0], bi_xy[0]);
+            const float w5[5] = {bi_xy[0], bi_xy[1], bi_rgb[0], bi_rgb[1], bi_rgb[2]};
+            const int at = widest_feature(w5, extent, 5);
             return cfail(c, PNP_ERR_ARG,
                          "lattice key range exceeded: a bilateral coordinate leaves the 11-bit key (|coordinate| must stay below %d); "
-                         "bi_rgb = %g (bi_xy = %g) is too small for these images",
-                         CRF_KEY_LIMIT, bi_rgb, bi_xy);
+                         "%s[%d] = %g is too small for these images (bi_xy = (%g, %g), bi_rgb = (%g, %g, %g))",
+                         CRF_KEY_LIMIT, at < 2 ? "bi_xy" : "bi_rgb", at < 2 ? at : at - 2, w5[at], w5[0], w5[1], w5[2], w5[3], w5[4]);
         }
         if (t == 0) {
             c->gauss_sig = sig;
-            c->gauss_xy = pos_xy;
+            c->gauss_xy[0] = pos_xy[0];
+            c->gauss_xy[1] = pos_xy[1];
         }
     }
     c->ready = true;
     return PNP_OK;
 }
 
-extern "C" int pnp_crf_infer(pnp_crf* c, int32_t iters, float pos_w, float bi_w, float* d_q, uint8_t* d_labels, void* stream) {
+}  // namespace
+
+extern "C" int pnp_crf_set_batch(pnp_crf* c, const pnp_crf_batch* b, float pos_xy, float bi_xy, float bi_rgb, void* stream) {
     if (!c) return PNP_ERR_ARG;
-    if (iters < 0) return cfail(c, PNP_ERR_ARG, "iters = %d", iters);
-    if (!c->ready) return cfail(c, PNP_ERR_STATE, "no batch is set: call pnp_crf_set_batch first (a failed call leaves none)");
-    hipStream_t s = (hipStream_t)stream;
+    const float p2[2] = {pos_xy, pos_xy}, b2[2] = {bi_xy, bi_xy}, b3[3] = {bi_rgb, bi_rgb, bi_rgb};
+    return crf_set_batch(c, b, p2, b2, b3, stream);
+}
+
+extern "C" int pnp_crf_set_batch_aniso(pnp_crf* c, const pnp_crf_batch* b, const float pos_xy[2], const float bi_xy[2],
+                                       const float bi_rgb[3], void* stream) {
+    if (!c) return PNP_ERR_ARG;
+    if (!pos_xy || !bi_xy || !bi_rgb) {
+        c->ready = c->started = false;
+        return cfail(c, PNP_ERR_ARG, "kernel widths are null (pos_xy[2], bi_xy[2], bi_rgb[3])");
+    }
+    return crf_set_batch(c, b, pos_xy, bi_xy, bi_rgb, stream);
+}
+
+extern "C" int pnp_crf_set_compat(pnp_crf* c, int32_t term, int32_t kind, const float* host_values, int32_t K) {
+    if (!c) return PNP_ERR_ARG;
+    if (term != 0 && term != 1) return cfail(c, PNP_ERR_ARG, "term = %d: 0 (Gaussian) or 1 (bilateral)", term);
+    if (kind == PNP_CRF_COMPAT_SCALAR) {          // back to Potts with the weight of the call; the values are not read
+        c->kind[term] = kind;
+        c->compat_K[term] = 0;
+        c->m_scalar[term] = false;
+        return PNP_OK;
+    }
+    if (kind != PNP_CRF_COMPAT_DIAGONAL && kind != PNP_CRF_COMPAT_MATRIX)
+        return cfail(c, PNP_ERR_ARG, "kind = %d: scalar (0), diagonal (1) or matrix (2)", kind);
+    if (!host_values) return cfail(c, PNP_ERR_ARG, "compatibility values are null");
+    if (K < 2 || K > c->maxK) return cfail(c, PNP_ERR_ARG, "compatibility for %d labels, the solver holds 2..%d", K, c->maxK);
+    if (!c->d_M) return cfail(c, PNP_ERR_STATE, "the solver's workspace was not allocated (pnp_crf_create failed)");
+    const size_t ld = (size_t)c->ldm;
+    c->h_M.assign(ld * ld, 0.f);
+    for (int l = 0; l < K; l++) {
+        if (kind == PNP_CRF_COMPAT_DIAGONAL) c->h_M[l * ld + l] = host_values[l];
+        else
+            for (int k = 0; k < K; k++) c->h_M[k * ld + l] = host_values[(size_t)l * K + k];      // (transposed)
+    }
     CHIP(c, hipSetDevice(c->device));
-    const int B = c->B;
+    // (synchronous: the matrix may not change under a step still in flight, and host_values may be freed on return)
+    CHIP(c, hipDeviceSynchronize());
+    CHIP(c, hipMemcpy(c->d_M + term * ld * ld, c->h_M.data(), sizeof(float) * ld * ld, hipMemcpyHostToDevice));
+    c->kind[term] = kind;
+    c->compat_K[term] = K;
+    c->m_scalar[term] = false;
+    return PNP_OK;
+}
+
+namespace {
+
+int crf_need_batch(pnp_crf* c) {
+    if (!c->ready) return cfail(c, PNP_ERR_STATE, "no batch is set: call pnp_crf_set_batch first (a failed call leaves none)");
+    return PNP_OK;
+}
+
+// Both terms as matrices on the device: a term left scalar as w * I.  Vector / matrix kinds fix the label count of the batch
+int crf_matrices(pnp_crf* c, float pos_w, float bi_w, hipStream_t s) {
+    const size_t ld = (size_t)c->ldm;
+    for (int t = 0; t < 2; t++) {
+        if (c->kind[t] != PNP_CRF_COMPAT_SCALAR) {
+            for (int i = 0; i < c->B; i++)
+                if (c->desc[i].K != c->compat_K[t])
+                    return cfail(c, PNP_ERR_ARG, "the %s term's compatibility is for %d labels, image %d of the batch has %d: a vector or "
+                                 "matrix compatibility needs that many labels in every image", t == 0 ? "Gaussian" : "bilateral",
+                                 c->compat_K[t], i, c->desc[i].K);
+            continue;
+        }
+        const float w = t == 0 ? pos_w : bi_w;
+        if (c->m_scalar[t] && c->m_scalar_w[t] == w) continue;
+        c->h_M.assign(ld * ld, 0.f);
+        for (size_t l = 0; l < ld; l++) c->h_M[l * ld + l] = w;
+        // (pageable host memory is staged at enqueue time: h_M may be rewritten by the next term)
+        CHIP(c, hipMemcpyAsync(c->d_M + t * ld * ld, c->h_M.data(), sizeof(float) * ld * ld, hipMemcpyHostToDevice, s));
+        c->m_scalar[t] = true;
+        c->m_scalar_w[t] = w;
+    }
+    return PNP_OK;
+}
+
+CrfLabelOut crf_labels(pnp_crf* c, uint8_t* d_labels) {
     // labels: the argmax the last update does on the marginals it has just normalised (first maximum, a NaN wins), through
     // the identity table (stride 0: the same table for every image)
     CrfLabelOut lab;
@@ -426,16 +594,101 @@ extern "C" int pnp_crf_infer(pnp_crf* c, int32_t iters, float pos_w, float bi_w,
         lab.lut_stride = 0;
         lab.label_off = c->d_label_off;
     }
-    // as post.hip's crf_iterate: Q0 = softmax(-U), then per iteration both filters and the update
-    CK(c, crf_update(c->lat[0], c->lat[1], c->d_desc, 0, B, c->vga, c->va, c->norm[0], c->norm[1], c->unary, c->Q, pos_w, bi_w, 0,
-                     c->kp_max, 1, s, iters == 0 ? lab : CrfLabelOut()));
-    for (int it = 0; it < iters; it++) {
+    return lab;
+}
+
+// Q0 = softmax(-U)
+int crf_start(pnp_crf* c, hipStream_t s, const CrfLabelOut& lab) {
+    CK(c, crf_update(c->lat[0], c->lat[1], c->d_desc, 0, c->B, c->vga, c->va, c->norm[0], c->norm[1], c->unary, c->Q, 0.f, 0.f, 0,
+                     c->kp_max, 1, s, lab));
+    c->started = true;
+    return PNP_OK;
+}
+
+// n mean-field updates from the current Q, as post.hip's crf_iterate: per iteration both filters and the update -- the Potts
+// kernel while both terms are scalar, the compatibility kernel otherwise.  lab: label output of the last update
+int crf_step(pnp_crf* c, int n, float pos_w, float bi_w, hipStream_t s, const CrfLabelOut& lab) {
+    const bool potts = c->kind[0] == PNP_CRF_COMPAT_SCALAR && c->kind[1] == PNP_CRF_COMPAT_SCALAR;
+    const size_t ld = (size_t)c->ldm;
+    if (!potts && n > 0)
+        if (int r = crf_matrices(c, pos_w, bi_w, s)) return r;
+    for (int it = 0; it < n; it++) {
         const float *rg = nullptr, *rb = nullptr;
-        CK(c, crf_filter(c->lat[0], c->d_desc, 0, B, c->Q, c->vga, c->vgb, &rg, c->kp_max, s));
-        CK(c, crf_filter(c->lat[1], c->d_desc, 0, B, c->Q, c->va, c->vb, &rb, c->kp_max, s));
-        CK(c, crf_update(c->lat[0], c->lat[1], c->d_desc, 0, B, rg, rb, c->norm[0], c->norm[1], c->unary, c->Q, pos_w, bi_w, 1,
-                         c->kp_max, 1, s, it == iters - 1 ? lab : CrfLabelOut()));
+        CK(c, crf_filter(c->lat[0], c->d_desc, 0, c->B, c->Q, c->vga, c->vgb, &rg, c->kp_max, s));
+        CK(c, crf_filter(c->lat[1], c->d_desc, 0, c->B, c->Q, c->va, c->vb, &rb, c->kp_max, s));
+        const CrfLabelOut out = it == n - 1 ? lab : CrfLabelOut();
+        if (potts)
+            CK(c, crf_update(c->lat[0], c->lat[1], c->d_desc, 0, c->B, rg, rb, c->norm[0], c->norm[1], c->unary, c->Q, pos_w, bi_w, 1,
+                             c->kp_max, 1, s, out));
+        else
+            CK(c, crf_update_compat(c->lat[0], c->lat[1], c->d_desc, 0, c->B, rg, rb, c->norm[0], c->norm[1], c->unary, c->Q, c->d_M,
+                                    c->d_M + ld * ld, (int)ld, c->kp_max, s, out, nullptr));
     }
-    if (d_q) CK(c, crf_planes_rows(false, c->d_desc, d_q, c->Q, B, c->maxHW, c->kp_max, s));
+    return PNP_OK;
+}
+
+}  // namespace
+
+extern "C" int pnp_crf_infer(pnp_crf* c, int32_t iters, float pos_w, float bi_w, float* d_q, uint8_t* d_labels, void* stream) {
+    if (!c) return PNP_ERR_ARG;
+    if (iters < 0) return cfail(c, PNP_ERR_ARG, "iters = %d", iters);
+    if (int r = crf_need_batch(c)) return r;
+    hipStream_t s = (hipStream_t)stream;
+    CHIP(c, hipSetDevice(c->device));
+    // pnp_crf_start + pnp_crf_step(iters) with the labels fused into the last update, then the marginals out
+    const CrfLabelOut lab = crf_labels(c, d_labels);
+    if (int r = crf_start(c, s, iters == 0 ? lab : CrfLabelOut())) return r;
+    if (int r = crf_step(c, iters, pos_w, bi_w, s, lab)) return r;
+    if (d_q) CK(c, crf_planes_rows(false, c->d_desc, d_q, c->Q, c->B, c->maxHW, c->kp_max, s));
+    return PNP_OK;
+}
+
+extern "C" int pnp_crf_start(pnp_crf* c, void* stream) {
+    if (!c) return PNP_ERR_ARG;
+    if (int r = crf_need_batch(c)) return r;
+    CHIP(c, hipSetDevice(c->device));
+    return crf_start(c, (hipStream_t)stream, CrfLabelOut());
+}
+
+extern "C" int pnp_crf_step(pnp_crf* c, int32_t n, float pos_w, float bi_w, void* stream) {
+    if (!c) return PNP_ERR_ARG;
+    if (n < 0) return cfail(c, PNP_ERR_ARG, "n = %d", n);
+    if (int r = crf_need_batch(c)) return r;
+    if (!c->started) return cfail(c, PNP_ERR_STATE, "no inference was started on this batch: call pnp_crf_start (or pnp_crf_infer) first");
+    CHIP(c, hipSetDevice(c->device));
+    return crf_step(c, n, pos_w, bi_w, (hipStream_t)stream, CrfLabelOut());
+}
+
+extern "C" int pnp_crf_read(pnp_crf* c, float* d_q, uint8_t* d_labels, void* stream) {
+    if (!c) return PNP_ERR_ARG;
+    if (int r = crf_need_batch(c)) return r;
+    if (!c->started) return cfail(c, PNP_ERR_STATE, "no inference was started on this batch: call pnp_crf_start (or pnp_crf_infer) first");
+    hipStream_t s = (hipStream_t)stream;
+    CHIP(c, hipSetDevice(c->device));
+    if (d_q) CK(c, crf_planes_rows(false, c->d_desc, d_q, c->Q, c->B, c->maxHW, c->kp_max, s));
+    if (d_labels) CK(c, argmax_remap(c->Q, c->d_desc, c->d_lut, 0, d_labels, c->d_label_off, 1, 0, c->B, c->maxHW, s));
+    return PNP_OK;
+}
+
+extern "C" int pnp_crf_kl(pnp_crf* c, float pos_w, float bi_w, double* h_out_per_image, void* stream) {
+    if (!c) return PNP_ERR_ARG;
+    if (!h_out_per_image) return cfail(c, PNP_ERR_ARG, "h_out_per_image is null");
+    if (int r = crf_need_batch(c)) return r;
+    if (!c->started) return cfail(c, PNP_ERR_STATE, "no inference was started on this batch: call pnp_crf_start (or pnp_crf_infer) first");
+    hipStream_t s = (hipStream_t)stream;
+    CHIP(c, hipSetDevice(c->device));
+    if (int r = crf_matrices(c, pos_w, bi_w, s)) return r;
+    const size_t ld = (size_t)c->ldm;
+    const float *rg = nullptr, *rb = nullptr;                // one filter pass per term at the current Q, which stays as it is
+    CK(c, crf_filter(c->lat[0], c->d_desc, 0, c->B, c->Q, c->vga, c->vgb, &rg, c->kp_max, s));
+    CK(c, crf_filter(c->lat[1], c->d_desc, 0, c->B, c->Q, c->va, c->vb, &rb, c->kp_max, s));
+    CK(c, crf_update_compat(c->lat[0], c->lat[1], c->d_desc, 0, c->B, rg, rb, c->norm[0], c->norm[1], c->unary, c->Q, c->d_M,
+                            c->d_M + ld * ld, (int)ld, c->kp_max, s, CrfLabelOut(), c->kl_pix));
+    const int runs = (c->maxHW + CRF_KL_RUN - 1) / CRF_KL_RUN;
+    hipLaunchKernelGGL(crf_kl_partial_kernel, dim3(runs < 1024 ? runs : 1024, c->B), dim3(CRF_KL_RUN), 0, s, c->d_desc, c->kl_pix, c->kl_part);
+    hipLaunchKernelGGL(crf_kl_final_kernel, dim3(1), dim3(64), 0, s, c->d_desc, c->kl_part, c->kl_out, c->B);
+    CHIP(c, hipGetLastError());
+    CHIP(c, hipMemcpyAsync(h_out_per_image, c->kl_out, sizeof(double) * c->B, hipMemcpyDeviceToHost, s));
+    CHIP(c, hipStreamSynchronize(s));
     return PNP_OK;
 }

@@ -172,8 +172,8 @@ struct CrfBuildScratch {
     int* range_err;
 };
 // h_range_err: set to 1 when the flag was raised (read back with the lattice size: the build's one synchronisation)
-int crf_build_lattice(int D, const CrfLattice& L, const PostDesc* d_imgs, const PostDesc* h_imgs, const uint8_t* d_rgb, float sxy, float srgb,
-                      int B, size_t ent_total, int max_pixels, const CrfBuildScratch& scratch, int* h_range_err, int* h_points,
+int crf_build_lattice(int D, const CrfLattice& L, const PostDesc* d_imgs, const PostDesc* h_imgs, const uint8_t* d_rgb, const float sxy[2],
+                      const float srgb[3], int B, size_t ent_total, int max_pixels, const CrfBuildScratch& scratch, int* h_range_err, int* h_points,
                       hipStream_t s);
 int crf_lattice_norm(const CrfLattice& L, const PostDesc* d_imgs, int B, int max_pixels, size_t ent_total, float* va, float* vb,
                      float* norm_out, hipStream_t s);
@@ -190,5 +190,13 @@ struct CrfLabelOut {
 int crf_update(const CrfLattice& Lg, const CrfLattice& Lb, const PostDesc* d_imgs, int img0, int nimg, const float* vg,
                const float* vb, const float* norm_g, const float* norm_b, const float* unary, float* Q, float w_g,
                float w_b, int pairwise, int max_kp, int groups, hipStream_t s, const CrfLabelOut& labels = CrfLabelOut());
+// The update with label-compatibility matrices (one channel group): Q <- softmax(-U + Mg msg_g + Mb msg_b).  The K x K message
+// weights come TRANSPOSED in device memory, MgT[k * ldm + l] = Mg[l][k], ldm >= max_kp a multiple of 8, zeros wherever l or k is
+// not a label.  kl_pix non-null: no update; the per-pixel terms of the KL divergence at the current Q (pnp_crf_kl) go to
+// kl_pix[pixel of the batch].  crf_compat_tile_pixels: the tile it picks.
+int crf_compat_tile_pixels(int max_kp, bool kl);
+int crf_update_compat(const CrfLattice& Lg, const CrfLattice& Lb, const PostDesc* d_imgs, int img0, int nimg, const float* vg,
+                      const float* vb, const float* norm_g, const float* norm_b, const float* unary, float* Q, const float* MgT,
+                      const float* MbT, int ldm, int max_kp, hipStream_t s, const CrfLabelOut& labels, double* kl_pix);
 
 }  // namespace pnp

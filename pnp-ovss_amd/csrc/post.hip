@@ -241,8 +241,9 @@ static int post_build_lattices(pnp_engine* e, hipStream_t s) {
         // the Gaussian (xy-only) lattice depends on the image sizes alone: keep it across batches
         if (t == 0 && sig == p.gauss_sig) continue;
         const size_t entries = (size_t)p.total_pix * p.lat[t].D1;
-        KCHK(e, crf_build_lattice(p.lat[t].D1 - 1, p.lat[t], p.view[0].d_desc, p.desc[0].data(), p.d_rgb, t == 0 ? CRF_POS_XY : CRF_BI_XY,
-                                  CRF_BI_RGB, p.B, entries, p.maxHW, p.scratch, &p.range_err_host, &p.lat_points[t], s));
+        const float xy = t == 0 ? CRF_POS_XY : CRF_BI_XY;      // one width for both position axes and one for the three colours
+        const float sxy[2] = {xy, xy}, srgb[3] = {CRF_BI_RGB, CRF_BI_RGB, CRF_BI_RGB};
+        KCHK(e, crf_build_lattice(p.lat[t].D1 - 1, p.lat[t], p.view[0].d_desc, p.desc[0].data(), p.d_rgb, sxy, srgb, p.B, entries, p.maxHW, p.scratch, &p.range_err_host, &p.lat_points[t], s));
         KCHK(e, crf_lattice_norm(p.lat[t], p.view[0].d_desc, p.B, p.maxHW, entries, p.va, p.vb, p.norm[t], s));
     }
     if (p.range_err_host) {                    // (read back with the lattice size inside crf_build_lattice: no extra sync)

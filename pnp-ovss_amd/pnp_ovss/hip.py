@@ -126,6 +126,12 @@ def load_library():
         "pnp_crf_last_error": (C.c_char_p, [vp]),
         "pnp_crf_set_batch": (i32, [vp, C.POINTER(PnpCrfBatch), f32, f32, f32, vp]),
         "pnp_crf_infer": (i32, [vp, i32, f32, f32, vp, vp, vp]),
+        "pnp_crf_set_batch_aniso": (i32, [vp, C.POINTER(PnpCrfBatch), C.POINTER(f32), C.POINTER(f32), C.POINTER(f32), vp]),
+        "pnp_crf_set_compat": (i32, [vp, i32, i32, C.POINTER(f32), i32]),
+        "pnp_crf_start": (i32, [vp, vp]),
+        "pnp_crf_step": (i32, [vp, i32, f32, f32, vp]),
+        "pnp_crf_read": (i32, [vp, vp, vp, vp]),
+        "pnp_crf_kl": (i32, [vp, f32, f32, C.POINTER(C.c_double), vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)          # AttributeError here = ABI drift, fail loudly
@@ -148,7 +154,8 @@ EXPORTED = ["pnp_create", "pnp_create_shared", "pnp_destroy", "pnp_last_error", 
             "pnp_op_text_embed", "pnp_op_itm_head", "pnp_op_itm_grad_seed", "pnp_op_patchify", "pnp_op_cls_rows",
             "pnp_op_gemm_args", "pnp_overlay_labels", "pnp_jpeg_encode",
             "pnp_crf_create", "pnp_crf_destroy", "pnp_crf_allocated_bytes", "pnp_crf_last_error", "pnp_crf_set_batch",
-            "pnp_crf_infer"]
+            "pnp_crf_infer", "pnp_crf_set_batch_aniso", "pnp_crf_set_compat", "pnp_crf_start", "pnp_crf_step", "pnp_crf_read",
+            "pnp_crf_kl"]
 
 
 PROJ_NAMES = ("vision_proj.weight", "vision_proj.bias", "text_proj.weight", "text_proj.bias")      # the optional ITC projections

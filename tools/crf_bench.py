@@ -52,6 +52,68 @@ def events_ms(torch, fn, reps):
     return float(np.median(out))
 
 
+def kernel_times_us(torch, fn):
+    """Device time of every crf_update kernel launch inside fn(), by torch's profiler: {kernel family: [us per launch]}.
+    Empty where the profiler reports no device kernels (the caller then records nothing rather than an estimate)."""
+    from torch.profiler import ProfilerActivity, profile
+    torch.cuda.synchronize()
+    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+        fn()
+        torch.cuda.synchronize()
+    out = {"crf_update_compat_kernel": [], "crf_update_kernel": []}
+    for ev in prof.events():
+        if "DeviceType.CUDA" not in str(getattr(ev, "device_type", "")):
+            continue
+        us = getattr(ev, "device_time", None)
+        if us is None:
+            us = getattr(ev, "cuda_time", 0.0)
+        for name in out:                                     # (the longer name first: it contains no other)
+            if name in ev.name:
+                out[name].append(float(us))
+                break
+    return out
+
+
+def compat_matrix(torch, crf, a):
+    """--compat matrix: one mean-field step (both filters + the update) with Potts weights against the same step with full
+    matrices on both terms, and the update kernels' own device times per launch, at the tool's geometry and at K = 150."""
+    H, W = map(int, a.size.split("x"))
+    rng = np.random.default_rng(0)
+    rec = {}
+    for K, B in ((a.labels, a.images), (150, min(a.images, 8))):
+        imgs = [synth_photo(rng, H, W) for _ in range(B)]
+        d_rgb = torch.from_numpy(np.concatenate([im.reshape(-1) for im in imgs])).cuda()
+        logits = torch.from_numpy(rng.normal(0, 2, (B, K, H * W)).astype(np.float32)).cuda()
+        d_unary = (-torch.log_softmax(logits, 1).clamp_min(float(np.log(1e-5)))).contiguous().reshape(-1)
+        del logits
+        mats = [(np.diag(np.full(K, w)) + rng.uniform(-0.3 * w, 0, (K, K)) * (1 - np.eye(K))).astype(np.float32) for w in (7.0, 10.0)]
+        solver = crf.DenseCRF(B, B * H * W, H * W, K)
+        solver.set_batch(d_unary, d_rgb, [(H, W)] * B, [K] * B)
+        one = {}
+        for name, cm in (("potts", (None, None)), ("matrix", tuple(mats))):
+            solver.set_compat(*cm)
+            solver.start(7.0, 10.0)
+            solver.step(2)                                                        # warm
+            one[name + "_step_events_ms"] = events_ms(torch, lambda: solver.step(10), max(a.reps // 3, 3)) / 10
+            kt = kernel_times_us(torch, lambda: solver.step(10))
+            fam = "crf_update_kernel" if name == "potts" else "crf_update_compat_kernel"
+            if len(kt[fam]) == 10:                                                # every launch seen, or nothing recorded
+                one[name + "_update_kernel_us_per_launch"] = float(np.median(kt[fam]))
+                one[name + "_update_kernel_us_min_max"] = [float(min(kt[fam])), float(max(kt[fam]))]
+        solver.close()
+        one.update(images=B)
+        rec[f"K{K}"] = one
+        del d_unary, d_rgb
+        torch.cuda.empty_cache()
+    rec["size"] = [H, W]
+    rec["note"] = ("*_step_events_ms: one mean-field step = both lattice filters + one update launch, device events over 10 "
+                   "steps; the two steps launch the same filter kernels, so their difference is the compatibility kernel's "
+                   "launch minus the Potts kernel's.  *_update_kernel_us_per_launch: median device time of the update kernel's "
+                   "10 launches as torch's profiler reports them (absent where it reported none).  Random unaries and random "
+                   "matrices w I + U[-0.3 w, 0]: the arithmetic does not depend on the values")
+    return rec
+
+
 def main():
     import torch
     from oracle import pipeline_np as OP
@@ -64,7 +126,22 @@ def main():
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--oracle_reps", type=int, default=1)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "crf_standalone.json"))
+    ap.add_argument("--compat", choices=["matrix"], default=None,
+                    help="matrix: measure only the compatibility-matrix update next to the Potts one and merge the result into "
+                         "the record at --out as `compat_matrix` (the other fields stay as the last full run wrote them)")
     a = ap.parse_args()
+    if a.compat == "matrix":
+        rec = {}
+        if a.out and os.path.exists(a.out):
+            with open(a.out) as f:
+                rec = json.loads(f.read())
+        rec["compat_matrix"] = compat_matrix(torch, crf, a)
+        line = json.dumps(rec)
+        print(json.dumps(rec["compat_matrix"]))
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(line + "\n")
+        return
     H, W = map(int, a.size.split("x"))
     B, K, IMG = a.images, a.labels, 336
     rng = np.random.default_rng(0)
