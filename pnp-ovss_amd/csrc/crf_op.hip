@@ -2,10 +2,11 @@
 // the caller brings, with kernel widths the caller chooses, in a solver that owns its workspace and needs no pnp_engine -- what
 // pydensecrf's DenseCRF2D is to the reference (PnP_OVSS_0514_updated_segmentation.py:1063-1073).
 //
-// Reused as they are (kernels.h): crf_build_lattice, crf_lattice_norm, crf_filter, crf_update and their PostDesc layout -- one
-// channel group per row, the whole batch as one chunk, driven exactly as post.hip's crf_iterate drives them.  New here: the
-// solver, and the two layout kernels between the caller's channel-major (K, H*W) planes (pydensecrf's layout) and the
-// pixel-major Kp-float rows the mean-field kernels work on.  The planes <-> rows kernels move floats, and the labels come from the
+// The workspace, its sizing, the lattice build with its Gaussian-lattice cache, the mean-field sequence and the PostDesc layout
+// are crf_solver.h's, shared with the engine's post-processing (post.hip): here one channel group per row and the whole batch
+// as one chunk.  This file's own: the solver's argument checks and messages, the compatibility matrices, the KL divergence and
+// the two layout kernels between the caller's channel-major (K, H*W) planes (pydensecrf's layout) and the pixel-major Kp-float
+// rows the mean-field kernels work on.  The planes <-> rows kernels move floats, and the labels come from the
 // last update's own argmax (CrfLabelOut with an identity table).
 // Beyond the reference's call (include/pnp_hip.h): per-axis widths (pnp_crf_set_batch_aniso), label-compatibility vectors and
 // matrices (pnp_crf_set_compat: crf_update_compat of crf.hip takes the update over from crf_update as soon as a term is not
@@ -18,6 +19,7 @@
 
 #include "../../include/pnp_hip.h"
 #include "common.h"
+#include "crf_solver.h"
 #include "kernels.h"
 
 using namespace pnp;
@@ -206,10 +208,7 @@ struct pnp_crf {
     // -- fixed by pnp_crf_create
     int maxB = 0, maxK = 0, maxKp = 0, max_pix_img = 0;
     int64_t max_total_pix = 0;
-    size_t val_cap = 0, valg_cap = 0;             // floats of the bilateral / Gaussian lattice value buffers
-    float *unary = nullptr, *Q = nullptr, *va = nullptr, *vb = nullptr, *vga = nullptr, *vgb = nullptr, *norm[2] = {nullptr, nullptr};
-    CrfLattice lat[2]{};                          // [0] Gaussian, [1] bilateral
-    CrfBuildScratch scratch{};
+    CrfWorkspace ws;                              // sized for the whole batch as one chunk, one channel group per row
     PostDesc* d_desc = nullptr;
     int32_t* d_lut = nullptr;                     // 0 .. 255: the label of a channel is its index
     size_t* d_label_off = nullptr;                // [B] first pixel of every image in the concatenated label output
@@ -218,11 +217,8 @@ struct pnp_crf {
     // -- the batch of the last pnp_crf_set_batch
     bool ready = false;
     int B = 0, kp_max = 0, maxHW = 0;
-    int64_t total_pix = 0;
     std::vector<PostDesc> desc;
-    std::vector<size_t> h_label_off;
-    std::vector<int> gauss_sig;                   // (H, W) list and ...
-    float gauss_xy[2] = {0.f, 0.f};               // ... (sx, sy) widths the Gaussian lattice was last built for
+    std::vector<size_t> h_label_off;              // [B + 1] as d_label_off; [B]: the pixels of the batch
     // -- label compatibility of the two terms (pnp_crf_set_compat; holds until changed).  d_M: two matrices, TRANSPOSED as
     // crf_update_compat reads them (d_M[k * ldm + l] = M[l][k]), row stride ldm = maxKp rounded up to a multiple of 8, zero
     // padded.  A term left scalar is Potts: it takes its weight from the call, and has a matrix (w * I) on the device only
@@ -241,12 +237,6 @@ struct pnp_crf {
 };
 
 namespace {
-
-constexpr int CRF_MAX_IMAGES = 64;                // IMG_BITS of the packed lattice key (crf.hip)
-constexpr int CRF_MAX_LABELS = 255;               // uint8 labels
-// |coordinate| a bilateral lattice key may reach: 11 bits per coordinate less the d + 1 = 6 of the canonical simplex
-// (lattice_embed_kernel's range flag)
-constexpr int CRF_KEY_LIMIT = (1 << 10) - 6;
 
 int cfail(pnp_crf* c, int code, const char* fmt, ...) {
     va_list ap;
@@ -279,9 +269,8 @@ int calloc_dev(pnp_crf* c, T** out, size_t count, bool zero = false) {
     return PNP_OK;
 }
 
-// what pnp_post_reserve allocates for the CRF, for one channel group and one chunk = the whole batch
 int crf_reserve(pnp_crf* c) {
-    const size_t TP = (size_t)c->max_total_pix, Kp = (size_t)c->maxKp, B = (size_t)c->maxB;
+    const size_t TP = (size_t)c->max_total_pix, B = (size_t)c->maxB;
     CK(c, calloc_dev(c, &c->d_desc, B));
     CK(c, calloc_dev(c, &c->d_label_off, B + 1));
     CK(c, calloc_dev(c, &c->d_lut, 256));
@@ -290,50 +279,8 @@ int crf_reserve(pnp_crf* c) {
         for (int i = 0; i < 256; i++) ident[i] = i;
         CHIP(c, hipMemcpy(c->d_lut, ident, sizeof(ident), hipMemcpyHostToDevice));
     }
-    CK(c, calloc_dev(c, &c->unary, TP * Kp));
-    CK(c, calloc_dev(c, &c->Q, TP * Kp));
-    CK(c, calloc_dev(c, &c->norm[0], TP));
-    CK(c, calloc_dev(c, &c->norm[1], TP));
-    for (int t = 0; t < 2; t++) {
-        const int D1 = t == 0 ? 3 : 6;
-        const size_t cap = TP * D1;
-        CrfLattice& L = c->lat[t];
-        L.D1 = D1;
-        L.which = t;
-        L.cap = cap;
-        CK(c, calloc_dev(c, &L.bary, cap));
-        CK(c, calloc_dev(c, &L.vals, cap));
-        CK(c, calloc_dev(c, &L.ent, cap));
-        CK(c, calloc_dev(c, &L.offset, cap));
-        CK(c, calloc_dev(c, &L.seg_start, cap + 1));
-        CK(c, calloc_dev(c, &L.seg_lo, cap));
-        CK(c, calloc_dev(c, &L.seg_hi, cap));
-        CK(c, calloc_dev(c, &L.ukeys, cap));
-        CK(c, calloc_dev(c, &L.idbase, B + 1));
-        CK(c, calloc_dev(c, &L.n1, cap * D1));
-        CK(c, calloc_dev(c, &L.n2, cap * D1));
-        CK(c, calloc_dev(c, &L.nbr8, cap * (D1 / 2)));
-    }
-    const size_t cap6 = c->lat[1].cap;            // E of CrfBuildScratch (kernels.h)
-    CrfBuildScratch& sc = c->scratch;
-    CK(c, calloc_dev(c, &sc.keys_a, cap6));
-    CK(c, calloc_dev(c, &sc.keys_b, cap6));
-    CK(c, calloc_dev(c, &sc.vals_a, cap6));
-    CK(c, calloc_dev(c, &sc.head, cap6));
-    CK(c, calloc_dev(c, &sc.incl, cap6));
-    CK(c, calloc_dev(c, &sc.n1k, cap6 * 6));
-    CK(c, calloc_dev(c, &sc.n2k, cap6 * 6));
-    CK(c, calloc_dev(c, &sc.range_err, 1, true));
-    sc.temp_bytes = crf_sort_temp_bytes(cap6);
-    CK(c, calloc_dev(c, &sc.temp, sc.temp_bytes));
-    // lattice value buffers: one row of Kp floats per lattice point, at most 6 (bilateral) / 3 (Gaussian) points per pixel;
-    // crf_lattice_norm also uses va / vb as scalar scratch of one float per lattice point
-    c->val_cap = std::max(TP * 6 * Kp, cap6);
-    CK(c, calloc_dev(c, &c->va, c->val_cap));
-    CK(c, calloc_dev(c, &c->vb, c->val_cap));
-    c->valg_cap = TP * 3 * Kp;
-    CK(c, calloc_dev(c, &c->vga, c->valg_cap));
-    CK(c, calloc_dev(c, &c->vgb, c->valg_cap));
+    for (const CrfAlloc& a : crf_reserve_plan(c->ws, B, TP, TP, (size_t)c->maxKp, 1))
+        CK(c, calloc_dev(c, reinterpret_cast<char**>(a.dst), a.bytes, a.zero));
     // compatibility matrices, and the KL divergence's per-pixel terms, per-run partials and per-image results
     c->ldm = (c->maxKp + 7) / 8 * 8;
     CK(c, calloc_dev(c, &c->d_M, 2 * (size_t)c->ldm * c->ldm, true));
@@ -349,8 +296,7 @@ int crf_layout(pnp_crf* c, const pnp_crf_batch* b) {
     c->desc.assign(B, PostDesc{});
     c->h_label_off.assign(B + 1, 0);
     c->kp_max = c->maxHW = 0;
-    size_t off = 0, qoff = 0, v[2] = {0, 0};
-    int64_t pix = 0;
+    CrfOffsets at;
     for (int i = 0; i < B; i++) {
         PostDesc d{};
         d.H = b->H[i]; d.W = b->W[i]; d.K = b->K[i];
@@ -358,31 +304,19 @@ int crf_layout(pnp_crf* c, const pnp_crf_batch* b) {
         if (d.K < 2 || d.K > c->maxK) return cfail(c, PNP_ERR_ARG, "image %d: %d labels, the solver holds 2..%d", i, d.K, c->maxK);
         const int64_t n = (int64_t)d.H * d.W;
         if (n > c->max_pix_img) return cfail(c, PNP_ERR_ARG, "image %d: %d x %d = %lld pixels, reserved %d per image", i, d.H, d.W, (long long)n, c->max_pix_img);
-        d.C = d.K; d.has_bg = 0; d.G = 1; d.Kg = d.K;
-        d.Kp = (d.K + 3) / 4 * 4;
-        // the iteration kernels address an image's rows with 24-bit ids and 32-bit byte offsets (crf.hip)
-        if (n * 6 >= (1 << 24) || n * 6 * d.Kp * 4 >= ((int64_t)1 << 32))
+        d.C = d.K; d.has_bg = 0; d.Kg = d.K;
+        if (!crf_layout_image(d, 1, at))
             return cfail(c, PNP_ERR_ARG, "image %d: %lld pixels x %d labels exceed the per-image addressing of the mean-field kernels", i, (long long)n, d.K);
-        d.pix0 = (int)pix;
-        d.off = off;
-        d.qoff = qoff;
-        for (int t = 0; t < 2; t++) {
-            d.voff[t] = v[t];
-            v[t] += (size_t)n * (t == 0 ? 3 : 6) * d.Kp;
-        }
         c->desc[i] = d;
-        c->h_label_off[i] = (size_t)pix;
-        off += (size_t)d.K * n;
-        qoff += (size_t)d.Kp * n;
-        pix += n;
+        c->h_label_off[i] = (size_t)d.pix0;
         c->kp_max = std::max(c->kp_max, d.Kp);
         c->maxHW = std::max(c->maxHW, (int)n);
     }
-    c->h_label_off[B] = (size_t)pix;
-    if (pix > c->max_total_pix) return cfail(c, PNP_ERR_ARG, "batch has %lld pixels, reserved %lld", (long long)pix, (long long)c->max_total_pix);
-    if (v[1] > c->val_cap || v[0] > c->valg_cap) return cfail(c, PNP_ERR_ARG, "batch needs %zu lattice value floats, reserved %zu", v[1], c->val_cap);
+    c->h_label_off[B] = (size_t)at.pix;
+    if (at.pix > c->max_total_pix) return cfail(c, PNP_ERR_ARG, "batch has %lld pixels, reserved %lld", (long long)at.pix, (long long)c->max_total_pix);
+    if (at.voff[1] > c->ws.val_cap || at.voff[0] > c->ws.valg_cap)
+        return cfail(c, PNP_ERR_ARG, "batch needs %zu lattice value floats, reserved %zu", at.voff[1], c->ws.val_cap);
     c->B = B;
-    c->total_pix = pix;
     return PNP_OK;
 }
 
@@ -434,7 +368,7 @@ int widest_feature(const float* w, const float* extent, int n) {
 int crf_set_batch(pnp_crf* c, const pnp_crf_batch* b, const float pos_xy[2], const float bi_xy[2], const float bi_rgb[3], void* stream) {
     c->ready = false;
     c->started = false;
-    if (!c->va || !c->kl_out) return cfail(c, PNP_ERR_STATE, "the solver's workspace was not allocated (pnp_crf_create failed)");
+    if (!c->ws.va || !c->kl_out) return cfail(c, PNP_ERR_STATE, "the solver's workspace was not allocated (pnp_crf_create failed)");
     if (!b) return cfail(c, PNP_ERR_ARG, "batch is null");
     if (b->B < 1 || b->B > c->maxB) return cfail(c, PNP_ERR_ARG, "batch of %d images, the solver holds 1..%d", b->B, c->maxB);
     if (!b->H || !b->W || !b->K || !b->d_rgb || !b->d_unary) return cfail(c, PNP_ERR_ARG, "batch has null arrays (H, W, K, d_rgb, d_unary)");
@@ -453,53 +387,36 @@ int crf_set_batch(pnp_crf* c, const pnp_crf_batch* b, const float pos_xy[2], con
     // next call without a synchronisation)
     CHIP(c, hipMemcpyAsync(c->d_desc, c->desc.data(), sizeof(PostDesc) * B, hipMemcpyHostToDevice, s));
     CHIP(c, hipMemcpyAsync(c->d_label_off, c->h_label_off.data(), sizeof(size_t) * (B + 1), hipMemcpyHostToDevice, s));
-    CK(c, crf_planes_rows(true, c->d_desc, const_cast<float*>(b->d_unary), c->unary, B, c->maxHW, c->kp_max, s));
-    // both lattices and their normalisers; the Gaussian (xy-only) one depends on the image sizes and its width alone and is
-    // kept across batches.  Each build synchronises once (lattice size + range flag read-back)
-    std::vector<int> sig;
-    for (const PostDesc& d : c->desc) { sig.push_back(d.H); sig.push_back(d.W); }
-    int range_err = 0, points = 0;
-    for (int t = 0; t < 2; t++) {
-        if (t == 0 && sig == c->gauss_sig && pos_xy[0] == c->gauss_xy[0] && pos_xy[1] == c->gauss_xy[1]) continue;
-        if (t == 0) c->gauss_sig.clear();
-        const size_t entries = (size_t)c->total_pix * c->lat[t].D1;
-        CK(c, crf_build_lattice(c->lat[t].D1 - 1, c->lat[t], c->d_desc, c->desc.data(), b->d_rgb, t == 0 ? pos_xy : bi_xy, bi_rgb, B,
-                                entries, c->maxHW, c->scratch, &range_err, &points, s));
-        CK(c, crf_lattice_norm(c->lat[t], c->d_desc, B, c->maxHW, entries, c->va, c->vb, c->norm[t], s));
-        if (range_err) {                          // leave no stale state behind: the next set_batch rebuilds both lattices
-            c->gauss_sig.clear();
-            (void)hipMemsetAsync(c->scratch.range_err, 0, sizeof(int), s);
-            // the flag says that a coordinate left the key, not which feature drove it there: named is the width whose feature
-            // spans the most lattice units over these images
-            float extent[5] = {0.f, 0.f, 255.f, 255.f, 255.f};
-            for (const PostDesc& d : c->desc) {
-                extent[0] = std::max(extent[0], (float)(d.W - 1));
-                extent[1] = std::max(extent[1], (float)(d.H - 1));
-            }
-            if (t == 0) {
-                if (iso)
-                    return cfail(c, PNP_ERR_ARG, "lattice key range exceeded: a Gaussian coordinate leaves the 16-bit key; pos_xy = %g is too small for these images", pos_xy[0]);
-                const int at = widest_feature(pos_xy, extent, 2);
-                return cfail(c, PNP_ERR_ARG, "lattice key range exceeded: a Gaussian coordinate leaves the 16-bit key; pos_xy[%d] = %g is too small for these images", at, pos_xy[at]);
-            }
+    CK(c, crf_planes_rows(true, c->d_desc, const_cast<float*>(b->d_unary), c->ws.unary, B, c->maxHW, c->kp_max, s));
+    int range_term = -1;
+    const int built = crf_build(c->ws, c->d_desc, c->desc.data(), B, c->h_label_off[B], c->maxHW, b->d_rgb, pos_xy, bi_xy, bi_rgb, &range_term, s);
+    if (range_term >= 0) {
+        // the flag says that a coordinate left the key, not which feature drove it there: named is the width whose feature
+        // spans the most lattice units over these images
+        float extent[5] = {0.f, 0.f, 255.f, 255.f, 255.f};
+        for (const PostDesc& d : c->desc) {
+            extent[0] = std::max(extent[0], (float)(d.W - 1));
+            extent[1] = std::max(extent[1], (float)(d.H - 1));
+        }
+        if (range_term == 0) {
             if (iso)
-                return cfail(c, PNP_ERR_ARG,
-                             "lattice key range exceeded: a bilateral coordinate leaves the 11-bit key (|coordinate| must stay below %d); "
-                             "bi_rgb = %g (bi_xy = %g) is too small for these images",
-                             CRF_KEY_LIMIT, bi_rgb[0], bi_xy[0]);
-            const float w5[5] = {bi_xy[0], bi_xy[1], bi_rgb[0], bi_rgb[1], bi_rgb[2]};
-            const int at = widest_feature(w5, extent, 5);
-            return cfail(c, PNP_ERR_ARG,
+                return cfail(c, built, "lattice key range exceeded: a Gaussian coordinate leaves the 16-bit key; pos_xy = %g is too small for these images", pos_xy[0]);
+            const int at = widest_feature(pos_xy, extent, 2);
+            return cfail(c, built, "lattice key range exceeded: a Gaussian coordinate leaves the 16-bit key; pos_xy[%d] = %g is too small for these images", at, pos_xy[at]);
+        }
+        if (iso)
+            return cfail(c, built,
                          "lattice key range exceeded: a bilateral coordinate leaves the 11-bit key (|coordinate| must stay below %d); "
-                         "%s[%d] = %g is too small for these images (bi_xy = (%g, %g), bi_rgb = (%g, %g, %g))",
-                         CRF_KEY_LIMIT, at < 2 ? "bi_xy" : "bi_rgb", at < 2 ? at : at - 2, w5[at], w5[0], w5[1], w5[2], w5[3], w5[4]);
-        }
-        if (t == 0) {
-            c->gauss_sig = sig;
-            c->gauss_xy[0] = pos_xy[0];
-            c->gauss_xy[1] = pos_xy[1];
-        }
+                         "bi_rgb = %g (bi_xy = %g) is too small for these images",
+                         CRF_KEY_LIMIT, bi_rgb[0], bi_xy[0]);
+        const float w5[5] = {bi_xy[0], bi_xy[1], bi_rgb[0], bi_rgb[1], bi_rgb[2]};
+        const int at = widest_feature(w5, extent, 5);
+        return cfail(c, built,
+                     "lattice key range exceeded: a bilateral coordinate leaves the 11-bit key (|coordinate| must stay below %d); "
+                     "%s[%d] = %g is too small for these images (bi_xy = (%g, %g), bi_rgb = (%g, %g, %g))",
+                     CRF_KEY_LIMIT, at < 2 ? "bi_xy" : "bi_rgb", at < 2 ? at : at - 2, w5[at], w5[0], w5[1], w5[2], w5[3], w5[4]);
     }
+    if (built != PNP_OK) return cfail(c, built, "lattice build failed (%d): %s", built, hipGetErrorString(hipGetLastError()));
     c->ready = true;
     return PNP_OK;
 }
@@ -597,33 +514,23 @@ CrfLabelOut crf_labels(pnp_crf* c, uint8_t* d_labels) {
     return lab;
 }
 
+CrfSpan crf_span(const pnp_crf* c) { return CrfSpan{c->d_desc, 0, c->B, c->kp_max, 1}; }
+
 // Q0 = softmax(-U)
 int crf_start(pnp_crf* c, hipStream_t s, const CrfLabelOut& lab) {
-    CK(c, crf_update(c->lat[0], c->lat[1], c->d_desc, 0, c->B, c->vga, c->va, c->norm[0], c->norm[1], c->unary, c->Q, 0.f, 0.f, 0,
-                     c->kp_max, 1, s, lab));
+    CK(c, crf_meanfield(c->ws, crf_span(c), true, 0, 0.f, 0.f, nullptr, nullptr, 0, s, lab));
     c->started = true;
     return PNP_OK;
 }
 
-// n mean-field updates from the current Q, as post.hip's crf_iterate: per iteration both filters and the update -- the Potts
-// kernel while both terms are scalar, the compatibility kernel otherwise.  lab: label output of the last update
+// n mean-field updates from the current Q: the Potts kernel while both terms are scalar, the compatibility kernel otherwise.
+// lab: label output of the last update
 int crf_step(pnp_crf* c, int n, float pos_w, float bi_w, hipStream_t s, const CrfLabelOut& lab) {
     const bool potts = c->kind[0] == PNP_CRF_COMPAT_SCALAR && c->kind[1] == PNP_CRF_COMPAT_SCALAR;
     const size_t ld = (size_t)c->ldm;
     if (!potts && n > 0)
         if (int r = crf_matrices(c, pos_w, bi_w, s)) return r;
-    for (int it = 0; it < n; it++) {
-        const float *rg = nullptr, *rb = nullptr;
-        CK(c, crf_filter(c->lat[0], c->d_desc, 0, c->B, c->Q, c->vga, c->vgb, &rg, c->kp_max, s));
-        CK(c, crf_filter(c->lat[1], c->d_desc, 0, c->B, c->Q, c->va, c->vb, &rb, c->kp_max, s));
-        const CrfLabelOut out = it == n - 1 ? lab : CrfLabelOut();
-        if (potts)
-            CK(c, crf_update(c->lat[0], c->lat[1], c->d_desc, 0, c->B, rg, rb, c->norm[0], c->norm[1], c->unary, c->Q, pos_w, bi_w, 1,
-                             c->kp_max, 1, s, out));
-        else
-            CK(c, crf_update_compat(c->lat[0], c->lat[1], c->d_desc, 0, c->B, rg, rb, c->norm[0], c->norm[1], c->unary, c->Q, c->d_M,
-                                    c->d_M + ld * ld, (int)ld, c->kp_max, s, out, nullptr));
-    }
+    CK(c, crf_meanfield(c->ws, crf_span(c), false, n, pos_w, bi_w, potts ? nullptr : c->d_M, c->d_M + ld * ld, (int)ld, s, lab));
     return PNP_OK;
 }
 
@@ -639,7 +546,7 @@ extern "C" int pnp_crf_infer(pnp_crf* c, int32_t iters, float pos_w, float bi_w,
     const CrfLabelOut lab = crf_labels(c, d_labels);
     if (int r = crf_start(c, s, iters == 0 ? lab : CrfLabelOut())) return r;
     if (int r = crf_step(c, iters, pos_w, bi_w, s, lab)) return r;
-    if (d_q) CK(c, crf_planes_rows(false, c->d_desc, d_q, c->Q, c->B, c->maxHW, c->kp_max, s));
+    if (d_q) CK(c, crf_planes_rows(false, c->d_desc, d_q, c->ws.Q, c->B, c->maxHW, c->kp_max, s));
     return PNP_OK;
 }
 
@@ -665,8 +572,8 @@ extern "C" int pnp_crf_read(pnp_crf* c, float* d_q, uint8_t* d_labels, void* str
     if (!c->started) return cfail(c, PNP_ERR_STATE, "no inference was started on this batch: call pnp_crf_start (or pnp_crf_infer) first");
     hipStream_t s = (hipStream_t)stream;
     CHIP(c, hipSetDevice(c->device));
-    if (d_q) CK(c, crf_planes_rows(false, c->d_desc, d_q, c->Q, c->B, c->maxHW, c->kp_max, s));
-    if (d_labels) CK(c, argmax_remap(c->Q, c->d_desc, c->d_lut, 0, d_labels, c->d_label_off, 1, 0, c->B, c->maxHW, s));
+    if (d_q) CK(c, crf_planes_rows(false, c->d_desc, d_q, c->ws.Q, c->B, c->maxHW, c->kp_max, s));
+    if (d_labels) CK(c, argmax_remap(c->ws.Q, c->d_desc, c->d_lut, 0, d_labels, c->d_label_off, 1, 0, c->B, c->maxHW, s));
     return PNP_OK;
 }
 
@@ -680,9 +587,8 @@ extern "C" int pnp_crf_kl(pnp_crf* c, float pos_w, float bi_w, double* h_out_per
     if (int r = crf_matrices(c, pos_w, bi_w, s)) return r;
     const size_t ld = (size_t)c->ldm;
     const float *rg = nullptr, *rb = nullptr;                // one filter pass per term at the current Q, which stays as it is
-    CK(c, crf_filter(c->lat[0], c->d_desc, 0, c->B, c->Q, c->vga, c->vgb, &rg, c->kp_max, s));
-    CK(c, crf_filter(c->lat[1], c->d_desc, 0, c->B, c->Q, c->va, c->vb, &rb, c->kp_max, s));
-    CK(c, crf_update_compat(c->lat[0], c->lat[1], c->d_desc, 0, c->B, rg, rb, c->norm[0], c->norm[1], c->unary, c->Q, c->d_M,
+    CK(c, crf_meanfield_filter(c->ws, crf_span(c), &rg, &rb, s));
+    CK(c, crf_update_compat(c->ws.lat[0], c->ws.lat[1], c->d_desc, 0, c->B, rg, rb, c->ws.norm[0], c->ws.norm[1], c->ws.unary, c->ws.Q, c->d_M,
                             c->d_M + ld * ld, (int)ld, c->kp_max, s, CrfLabelOut(), c->kl_pix));
     const int runs = (c->maxHW + CRF_KL_RUN - 1) / CRF_KL_RUN;
     hipLaunchKernelGGL(crf_kl_partial_kernel, dim3(runs < 1024 ? runs : 1024, c->B), dim3(CRF_KL_RUN), 0, s, c->d_desc, c->kl_pix, c->kl_part);

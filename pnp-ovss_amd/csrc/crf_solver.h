@@ -1,0 +1,73 @@
+// Internal to csrc/: the host side of the DenseCRF mean-field, shared by its two owners -- the engine's post-processing
+// (pnp_engine::Post, post.hip) and the stand-alone solver (pnp_crf, crf_op.hip).  Host code only: the kernels and their
+// launchers are in crf.hip and sort.hip (kernels.h).  Functions return PNP_* codes and format no text: each owner keeps its own
+// error buffer, messages and allocator.
+#pragma once
+#include <vector>
+
+#include "common.h"
+#include "kernels.h"
+
+namespace pnp {
+
+constexpr int CRF_MAX_IMAGES = 64;                // IMG_BITS of the packed lattice key (crf.hip)
+constexpr int CRF_MAX_LABELS = 255;               // uint8 labels
+// |coordinate| a bilateral lattice key may reach: 11 bits per coordinate less the d + 1 = 6 of the canonical simplex
+// (lattice_embed_kernel's range flag)
+constexpr int CRF_KEY_LIMIT = (1 << 10) - 6;
+
+// row stride of the pixel-major CRF arrays in floats: `groups` channel groups of K back to back, zero-padded to a multiple of 4
+// (PostDesc::Kp; the paired run of K = 21 has rows of 44 instead of 2 x 24)
+constexpr int crf_row_stride(int groups, int K) { return (groups * K + 3) / 4 * 4; }
+
+struct CrfWorkspace {
+    float *unary = nullptr, *Q = nullptr, *va = nullptr, *vb = nullptr, *vga = nullptr, *vgb = nullptr, *norm[2] = {nullptr, nullptr};
+    CrfLattice lat[2]{};                          // [0] Gaussian, [1] bilateral
+    CrfBuildScratch scratch{};
+    size_t val_cap = 0, valg_cap = 0;             // floats of the bilateral (va, vb) / Gaussian (vga, vgb) lattice value buffers
+    std::vector<double> gauss_sig;                // what the Gaussian lattice was last built for: its widths (sx, sy), then H, W of every image
+    int lat_points[2] = {0, 0};                   // lattice points of the last build (Gaussian, bilateral)
+};
+
+// One device allocation of the workspace: the owner allocates `bytes` with its own allocator (its list, its byte count),
+// zero-filled if `zero`, and stores the pointer in *dst
+struct CrfAlloc {
+    void** dst;
+    size_t bytes;
+    bool zero;
+};
+// The workspace's allocations, in order, for batches of at most `images` images and `total_pix` pixels, rows of `groups` channel
+// groups of at most max_kp floats each, and lattice value buffers for the rows of `value_pix` pixels at once (a chunk of the
+// batch; total_pix: all of it).  Sets the capacities of `ws`.
+std::vector<CrfAlloc> crf_reserve_plan(CrfWorkspace& ws, size_t images, size_t total_pix, size_t value_pix, size_t max_kp, size_t groups);
+
+struct CrfOffsets {                               // running offsets of a batch layout
+    int64_t pix = 0;
+    size_t off = 0, qoff = 0, voff[2] = {0, 0};
+};
+// Where d (H, W, K are set) lies in a batch with `groups` channel groups per row -- pix0, off, G, Kp, qoff, voff -- and `at`
+// advanced past it.  False: beyond the per-image addressing of the iteration kernels (24-bit row ids, 32-bit byte offsets: crf.hip)
+bool crf_layout_image(PostDesc& d, int groups, CrfOffsets& at);
+
+// Both lattices of a batch (the features are fixed per batch) and their normalisers.  The Gaussian (xy-only) lattice depends on
+// the image sizes and pos_xy alone and is kept across batches; every lattice built synchronises once (size + range flag
+// read-back).  A raised key-range flag ends the build at that lattice: PNP_ERR_ARG with *range_term = 0 (Gaussian) / 1
+// (bilateral), else -1; the device flag is cleared and no lattice is kept, so the next build makes both.
+int crf_build(CrfWorkspace& ws, const PostDesc* d_desc, const PostDesc* h_desc, int B, size_t total_pix, int maxHW, const uint8_t* d_rgb,
+              const float pos_xy[2], const float bi_xy[2], const float bi_rgb[3], int* range_term, hipStream_t s);
+
+struct CrfSpan {                                  // the images [img0, img0 + nimg) of one layout of a batch
+    const PostDesc* d_desc;
+    int img0, nimg;
+    int kp_max;                                   // widest row of the batch, floats
+    int groups;
+};
+// one filter pass per term at the current Q, which stays as it is: *rg / *rb = the filtered values
+int crf_meanfield_filter(const CrfWorkspace& ws, const CrfSpan& v, const float** rg, const float** rb, hipStream_t s);
+// The mean-field on the images of v.  start: Q0 = softmax(-U) first; then n updates from the current Q, each both filters and the
+// Potts kernel with the weights of the call or, with matrices (MgT, MbT, ldm as crf_update_compat takes them; one group only),
+// the compatibility kernel.  labels: the label output of the last update
+int crf_meanfield(const CrfWorkspace& ws, const CrfSpan& v, bool start, int n, float pos_w, float bi_w, const float* MgT, const float* MbT,
+                  int ldm, hipStream_t s, const CrfLabelOut& labels);
+
+}  // namespace pnp

@@ -1,0 +1,109 @@
+// The DenseCRF host side of crf_solver.h.  Host logic only: every kernel is behind a launcher of kernels.h.
+#include "crf_solver.h"
+
+#include <algorithm>
+
+namespace pnp {
+
+std::vector<CrfAlloc> crf_reserve_plan(CrfWorkspace& ws, size_t B, size_t TP, size_t value_pix, size_t Kp, size_t groups) {
+    std::vector<CrfAlloc> plan;
+    auto want = [&plan](size_t count, bool zero, auto**... dst) {      // `count` elements for each of dst, in order
+        (plan.push_back({reinterpret_cast<void**>(dst), count * sizeof(**dst), zero}), ...);
+    };
+    want(TP * Kp * groups, false, &ws.unary, &ws.Q);
+    want(TP, false, &ws.norm[0], &ws.norm[1]);
+    for (int t = 0; t < 2; t++) {
+        CrfLattice& L = ws.lat[t];
+        L.D1 = t == 0 ? 3 : 6;
+        L.which = t;
+        L.cap = TP * L.D1;
+        want(L.cap, false, &L.bary, &L.vals, &L.ent, &L.offset);
+        want(L.cap + 1, false, &L.seg_start);
+        want(L.cap, false, &L.seg_lo, &L.seg_hi, &L.ukeys);
+        want(B + 1, false, &L.idbase);
+        want(L.cap * L.D1, false, &L.n1, &L.n2);
+        want(L.cap * (L.D1 / 2), false, &L.nbr8);
+    }
+    const size_t cap6 = ws.lat[1].cap;            // E of CrfBuildScratch (kernels.h)
+    CrfBuildScratch& sc = ws.scratch;
+    want(cap6, false, &sc.keys_a, &sc.keys_b, &sc.vals_a, &sc.head, &sc.incl);
+    want(cap6 * 6, false, &sc.n1k, &sc.n2k);
+    want(1, true, &sc.range_err);
+    sc.temp_bytes = crf_sort_temp_bytes(cap6);
+    want(sc.temp_bytes, false, &sc.temp);
+    // lattice value buffers: one row per lattice point, at most 6 (bilateral) / 3 (Gaussian) points per pixel;
+    // crf_lattice_norm also uses va / vb as scalar scratch of one float per lattice point of the whole batch
+    ws.val_cap = std::max(value_pix * 6 * Kp * groups, cap6);
+    want(ws.val_cap, false, &ws.va, &ws.vb);
+    ws.valg_cap = value_pix * 3 * Kp * groups;
+    want(ws.valg_cap, false, &ws.vga, &ws.vgb);
+    return plan;
+}
+
+bool crf_layout_image(PostDesc& d, int groups, CrfOffsets& at) {
+    const int64_t n = (int64_t)d.H * d.W;
+    d.pix0 = (int)at.pix;
+    d.off = at.off;
+    at.pix += n;
+    at.off += (size_t)n * d.K;
+    d.G = groups;
+    d.Kp = crf_row_stride(groups, d.K);
+    d.qoff = at.qoff;
+    at.qoff += (size_t)n * d.Kp;
+    for (int t = 0; t < 2; t++) {
+        d.voff[t] = at.voff[t];
+        at.voff[t] += (size_t)n * (t == 0 ? 3 : 6) * d.Kp;
+    }
+    return n * 6 < (1 << 24) && n * 6 * d.Kp * 4 < ((int64_t)1 << 32);
+}
+
+int crf_build(CrfWorkspace& ws, const PostDesc* d_desc, const PostDesc* h_desc, int B, size_t total_pix, int maxHW, const uint8_t* d_rgb,
+              const float pos_xy[2], const float bi_xy[2], const float bi_rgb[3], int* range_term, hipStream_t s) {
+    std::vector<double> sig = {pos_xy[0], pos_xy[1]};
+    for (int i = 0; i < B; i++) { sig.push_back(h_desc[i].H); sig.push_back(h_desc[i].W); }
+    *range_term = -1;
+    for (int t = 0; t < 2; t++) {
+        if (t == 0 && sig == ws.gauss_sig) continue;
+        if (t == 0) ws.gauss_sig.clear();         // until the new one stands
+        const size_t entries = total_pix * ws.lat[t].D1;
+        int range_err = 0;
+        if (int r = crf_build_lattice(ws.lat[t].D1 - 1, ws.lat[t], d_desc, h_desc, d_rgb, t == 0 ? pos_xy : bi_xy, bi_rgb, B, entries,
+                                      maxHW, ws.scratch, &range_err, &ws.lat_points[t], s))
+            return r;
+        if (int r = crf_lattice_norm(ws.lat[t], d_desc, B, maxHW, entries, ws.va, ws.vb, ws.norm[t], s)) return r;
+        if (range_err) {                          // leave no stale state behind
+            ws.gauss_sig.clear();
+            (void)hipMemsetAsync(ws.scratch.range_err, 0, sizeof(int), s);
+            *range_term = t;
+            return PNP_ERR_ARG;
+        }
+        if (t == 0) ws.gauss_sig = sig;
+    }
+    return PNP_OK;
+}
+
+int crf_meanfield_filter(const CrfWorkspace& ws, const CrfSpan& v, const float** rg, const float** rb, hipStream_t s) {
+    if (int r = crf_filter(ws.lat[0], v.d_desc, v.img0, v.nimg, ws.Q, ws.vga, ws.vgb, rg, v.kp_max, s)) return r;
+    return crf_filter(ws.lat[1], v.d_desc, v.img0, v.nimg, ws.Q, ws.va, ws.vb, rb, v.kp_max, s);
+}
+
+int crf_meanfield(const CrfWorkspace& ws, const CrfSpan& v, bool start, int n, float pos_w, float bi_w, const float* MgT, const float* MbT,
+                  int ldm, hipStream_t s, const CrfLabelOut& labels) {
+    if (start)
+        if (int r = crf_update(ws.lat[0], ws.lat[1], v.d_desc, v.img0, v.nimg, ws.vga, ws.va, ws.norm[0], ws.norm[1], ws.unary, ws.Q, 0.f, 0.f,
+                               0, v.kp_max, v.groups, s, n == 0 ? labels : CrfLabelOut()))
+            return r;
+    for (int it = 0; it < n; it++) {
+        const float *rg = nullptr, *rb = nullptr;
+        if (int r = crf_meanfield_filter(ws, v, &rg, &rb, s)) return r;
+        const CrfLabelOut out = it == n - 1 ? labels : CrfLabelOut();
+        const int r = MgT ? crf_update_compat(ws.lat[0], ws.lat[1], v.d_desc, v.img0, v.nimg, rg, rb, ws.norm[0], ws.norm[1], ws.unary, ws.Q, MgT,
+                                              MbT, ldm, v.kp_max, s, out, nullptr)
+                          : crf_update(ws.lat[0], ws.lat[1], v.d_desc, v.img0, v.nimg, rg, rb, ws.norm[0], ws.norm[1], ws.unary, ws.Q, pos_w, bi_w,
+                                       1, v.kp_max, v.groups, s, out);
+        if (r) return r;
+    }
+    return PNP_OK;
+}
+
+}  // namespace pnp

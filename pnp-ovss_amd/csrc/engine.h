@@ -12,6 +12,7 @@
 
 #include "../../include/pnp_hip.h"
 #include "common.h"
+#include "crf_solver.h"
 #include "kernels.h"
 
 namespace pnp {
@@ -77,13 +78,6 @@ struct WeightStore {
         (void)hipSetDevice(device);
         for (void* p : allocs) (void)hipFree(p);
     }
-};
-
-// One layout of the prepared batch's CRF rows: [0] one channel group per row, [1] the paired run's two (1-drop | N-drop)
-struct PostView {
-    const PostDesc* d_desc;    // device descriptors of this layout
-    int kp_max;                // widest row of the prepared batch, floats
-    int groups;
 };
 
 }  // namespace pnp
@@ -155,31 +149,25 @@ struct pnp_engine {
         int maxB = 0, maxK = 0, maxKp = 0, max_pix_img = 0, chunk = 0;
         int64_t max_total_pix = 0;
         int lut_cap = 0, cls_cap = 0, tok_cap = 0, wts_cap = 0;
-        size_t val_cap = 0, valg_cap = 0;
         int32_t *d_img_cls_off = nullptr, *d_cls_off = nullptr, *d_tok_idx = nullptr, *d_cls_div = nullptr, *d_lut = nullptr;
         size_t* d_label_off = nullptr;
         double* d_wts = nullptr;
         int32_t* d_wt_off = nullptr;
         float *merged = nullptr, *thr = nullptr, *maps = nullptr, *maps2 = nullptr, *maps3 = nullptr, *stats = nullptr;
-        float *unary = nullptr, *Q = nullptr, *va = nullptr, *vb = nullptr, *vga = nullptr, *vgb = nullptr, *norm[2] = {nullptr, nullptr};
-        pnp::CrfLattice lat[2]{};             // [0] Gaussian, [1] bilateral
-        pnp::CrfBuildScratch scratch{};
+        pnp::CrfWorkspace crf;                // the DenseCRF arrays, sized for groups_cap groups per row and chunks of `chunk` images
         // -- the batch of the last pnp_post_prepare
         int B = 0, Cmax = 0, Kmax = 0, maxHW = 0, maxH = 0, maxW = 0, max_radius = 0;
-        int64_t total_pix = 0;
         int lut_stride = 0;
         std::vector<pnp::PostDesc> desc[2];   // host copies of the two layouts; [0] is the batch's geometry for every host loop
-        pnp::PostView view[2]{};              // (d_desc and groups are fixed by reserve, kp_max is the batch's)
+        // the prepared batch in its two layouts: [0] one channel group per row, [1] the paired run's two (1-drop | N-drop)
+        pnp::CrfSpan view[2]{};               // (d_desc and groups are fixed by reserve, kp_max is the batch's)
         // host staging of the per-batch tables: lives in the engine until the next prepare (pageable memory: the runtime copies
         // it into its own staging buffer at enqueue time, so rewriting it on the next call is safe without a synchronisation)
-        std::vector<size_t> h_label_off;
+        std::vector<size_t> h_label_off;      // [B + 1] first pixel of every image; [B]: the pixels of the batch
         std::vector<int32_t> h_wt_off;
         std::vector<double> h_wts;
         const uint8_t* d_rgb = nullptr;
         const float* d_gt = nullptr;
-        std::vector<int> gauss_sig;           // (H, W) list the Gaussian lattice was last built for
-        int range_err_host = 0;               // key-range flag of the lattices built by the last prepare
-        int lat_points[2] = {0, 0};           // lattice points of the prepared batch (Gaussian, bilateral)
         bool maps_in_2 = false;               // where the current maps live after blur
     } post;
 

@@ -1,6 +1,8 @@
 // The post-processing entry points of include/pnp_hip.h (pnp_post_reserve ... pnp_postprocess_pair): token merge, threshold,
 // upsample, blur and DenseCRF of a batch of differently sized images.  Host logic only: the kernels are in
-// pipeline_kernels.hip, crf.hip and sort.hip; the state is pnp_engine::Post (engine.h).
+// pipeline_kernels.hip, crf.hip and sort.hip; the state is pnp_engine::Post (engine.h).  The DenseCRF arrays, lattice build and
+// mean-field sequence are crf_solver.h's, shared with the stand-alone solver (crf_op.hip); the engine's own are the chunking, the
+// paired two-group layout, the stage profile and the reference's fixed parameters.
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -16,19 +18,15 @@ namespace {
 constexpr int CRF_ITERS = 10;
 constexpr float CRF_POS_W = 7.0f, CRF_POS_XY = 3.0f, CRF_BI_W = 10.0f, CRF_BI_XY = 50.0f, CRF_BI_RGB = 5.0f;
 
-// row stride of the pixel-major CRF arrays in floats: `groups` channel groups of K back to back, zero-padded to a multiple of 4
-// (PostDesc::Kp; the paired run of K = 21 has rows of 44 instead of 2 x 24)
-constexpr int crf_row_stride(int groups, int K) { return (groups * K + 3) / 4 * 4; }
-
 }  // namespace
 
 extern "C" int pnp_post_reserve(pnp_engine* e, int32_t max_batch, int64_t max_total_pixels, int32_t max_pixels_per_image,
                                 int32_t max_channels, int32_t crf_chunk) {
     if (!e) return PNP_ERR_ARG;
     if (e->post.reserved) return fail(e, PNP_ERR_STATE, "post-process workspace already reserved");
-    if (max_batch <= 0 || max_batch > 64 || max_total_pixels <= 0 || max_pixels_per_image <= 0 || max_channels <= 0 ||
-        max_channels > 255)
-        return fail(e, PNP_ERR_ARG, "bad post-process bounds (at most 64 images per batch, 255 channels)");
+    if (max_batch <= 0 || max_batch > CRF_MAX_IMAGES || max_total_pixels <= 0 || max_pixels_per_image <= 0 || max_channels <= 0 ||
+        max_channels > CRF_MAX_LABELS)
+        return fail(e, PNP_ERR_ARG, "bad post-process bounds (at most %d images per batch, %d channels)", CRF_MAX_IMAGES, CRF_MAX_LABELS);
     HIPCHK(e, hipSetDevice(e->c.device));
     auto& p = e->post;
     p.maxB = max_batch;
@@ -40,7 +38,7 @@ extern "C" int pnp_post_reserve(pnp_engine* e, int32_t max_batch, int64_t max_to
     for (int g = 0; g < 2; g++) {
         PostDesc* d = nullptr;
         KCHK(e, dalloc(e, &d, B));
-        p.view[g] = PostView{d, 0, g + 1};
+        p.view[g] = CrfSpan{d, 0, 0, 0, g + 1};
     }
     KCHK(e, dalloc(e, &p.d_img_cls_off, B + 1));
     p.cls_cap = (int)(B * K + 1);
@@ -75,50 +73,8 @@ extern "C" int pnp_post_reserve(pnp_engine* e, int32_t max_batch, int64_t max_to
         if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = (size_t)96 << 30;
         p.groups_cap = 2 * single <= free_b / 3 ? 2 : 1;
     }
-    const size_t G2 = (size_t)p.groups_cap;
-    KCHK(e, dalloc(e, &p.unary, TP * Kp * G2));
-    KCHK(e, dalloc(e, &p.Q, TP * Kp * G2));
-    KCHK(e, dalloc(e, &p.norm[0], TP));
-    KCHK(e, dalloc(e, &p.norm[1], TP));
-    for (int t = 0; t < 2; t++) {
-        const int D1 = t == 0 ? 3 : 6;
-        const size_t cap = TP * D1;
-        CrfLattice& L = p.lat[t];
-        L.D1 = D1;
-        L.which = t;
-        L.cap = cap;
-        KCHK(e, dalloc(e, &L.bary, cap));
-        KCHK(e, dalloc(e, &L.vals, cap));
-        KCHK(e, dalloc(e, &L.ent, cap));
-        KCHK(e, dalloc(e, &L.offset, cap));
-        KCHK(e, dalloc(e, &L.seg_start, cap + 1));
-        KCHK(e, dalloc(e, &L.seg_lo, cap));
-        KCHK(e, dalloc(e, &L.seg_hi, cap));
-        KCHK(e, dalloc(e, &L.ukeys, cap));
-        KCHK(e, dalloc(e, &L.idbase, B + 1));
-        KCHK(e, dalloc(e, &L.n1, cap * D1));
-        KCHK(e, dalloc(e, &L.n2, cap * D1));
-        KCHK(e, dalloc(e, &L.nbr8, cap * (D1 / 2)));
-    }
-    const size_t cap6 = p.lat[1].cap;          // E of CrfBuildScratch (kernels.h)
-    CrfBuildScratch& sc = p.scratch;
-    KCHK(e, dalloc(e, &sc.keys_a, cap6));
-    KCHK(e, dalloc(e, &sc.keys_b, cap6));
-    KCHK(e, dalloc(e, &sc.vals_a, cap6));
-    KCHK(e, dalloc(e, &sc.head, cap6));
-    KCHK(e, dalloc(e, &sc.incl, cap6));
-    KCHK(e, dalloc(e, &sc.n1k, cap6 * 6));
-    KCHK(e, dalloc(e, &sc.n2k, cap6 * 6));
-    KCHK(e, dalloc(e, &sc.range_err, 1, true));
-    sc.temp_bytes = crf_sort_temp_bytes(cap6);
-    KCHK(e, dalloc(e, &sc.temp, sc.temp_bytes));
-    // lattice value buffers: bilateral upper bound (6 entries per pixel) x K
-    p.val_cap = std::max(chunk_pix * 6 * Kp * G2, cap6);
-    KCHK(e, dalloc(e, &p.va, p.val_cap));
-    KCHK(e, dalloc(e, &p.vb, p.val_cap));
-    p.valg_cap = chunk_pix * 3 * Kp * G2;
-    KCHK(e, dalloc(e, &p.vga, p.valg_cap));
-    KCHK(e, dalloc(e, &p.vgb, p.valg_cap));
+    for (const CrfAlloc& a : crf_reserve_plan(p.crf, B, TP, chunk_pix, Kp, (size_t)p.groups_cap))
+        KCHK(e, dalloc(e, reinterpret_cast<char**>(a.dst), a.bytes, a.zero));
     p.reserved = true;
     return PNP_OK;
 }
@@ -141,7 +97,7 @@ static void gaussian_taps(int H, int W, std::vector<double>& wts) {
 
 // Step 1, host only: validates the batch against the reserved bounds and lays it out -- both descriptor sets, the label and
 // blur-tap tables, the batch maxima.  Nothing is enqueued, so an error leaves the stream untouched.
-static int post_layout(pnp_engine* e, const pnp_post_batch* b) {
+static int post_layout(pnp_engine* e, const pnp_post_batch* b, bool want_crf) {
     auto& p = e->post;
     const int B = b->B;
     const bool own_taps = b->blur_wts && b->blur_wt_off;
@@ -151,41 +107,28 @@ static int post_layout(pnp_engine* e, const pnp_post_batch* b) {
     p.h_wts.clear();
     p.Cmax = p.Kmax = p.maxHW = p.maxH = p.maxW = p.max_radius = 0;
     p.view[0].kp_max = p.view[1].kp_max = 0;
-    size_t off = 0, qoff[2] = {0, 0};
-    size_t v[2][2] = {{0, 0}, {0, 0}};         // [layout][lattice] value offsets inside the current CRF chunk (upper bound: entries * Kp)
-    size_t chunk_need = 0;                     // bilateral value floats of the first chunk that exceeds what is reserved
-    bool chunk_over = false;
-    int64_t pix = 0;
+    CrfOffsets at[2];                          // [layout]; the value offsets are those inside the current CRF chunk (upper bound: entries * Kp)
+    size_t chunk_need = 0;                     // bilateral value floats of the first chunk that exceeds what is reserved (0: none)
     for (int i = 0; i < B; i++) {
         PostDesc d{};
         d.H = b->H[i]; d.W = b->W[i]; d.C = b->n_classes[i]; d.has_bg = b->has_bg[i] ? 1 : 0; d.K = d.C + d.has_bg;
         if (d.H <= 0 || d.W <= 0 || d.C <= 0 || d.K > p.maxK) return fail(e, PNP_ERR_ARG, "image %d: bad H/W/classes (K=%d max %d)", i, d.K, p.maxK);
         if ((int64_t)d.H * d.W > p.max_pix_img) return fail(e, PNP_ERR_ARG, "image %d: %dx%d exceeds max_pixels_per_image", i, d.H, d.W);
         if (b->img_cls_off[i + 1] - b->img_cls_off[i] != d.C) return fail(e, PNP_ERR_ARG, "image %d: merge plan has %d classes, expected %d", i, b->img_cls_off[i + 1] - b->img_cls_off[i], d.C);
-        d.pix0 = (int)pix;
-        d.off = off;
         d.Kg = d.K;
-        if (i % p.chunk == 0) v[0][0] = v[0][1] = v[1][0] = v[1][1] = 0;
         for (int g = 0; g < 2; g++) {          // one channel group per row | the paired run's two, packed back to back
-            d.G = g + 1;
-            d.Kp = crf_row_stride(d.G, d.K);
-            d.qoff = qoff[g];
-            qoff[g] += (size_t)d.Kp * d.H * d.W;
-            for (int t = 0; t < 2; t++) {
-                d.voff[t] = v[g][t];
-                v[g][t] += (size_t)d.H * d.W * (t == 0 ? 3 : 6) * d.Kp;
-            }
+            if (i % p.chunk == 0) at[g].voff[0] = at[g].voff[1] = 0;
+            // refused with the widest row this engine would run the image with: the paired layout where it is reserved
+            if (!crf_layout_image(d, g + 1, at[g]) && want_crf && g < p.groups_cap)
+                return fail(e, PNP_ERR_ARG, "image %d: %d x %d pixels x %d floats per row exceed the per-image addressing of the mean-field "
+                            "kernels: its DenseCRF cannot be computed", i, d.H, d.W, d.Kp);
             p.desc[g][i] = d;
             p.view[g].kp_max = std::max(p.view[g].kp_max, d.Kp);
         }
         const bool chunk_ends = i + 1 == B || (i + 1) % p.chunk == 0;
-        if (chunk_ends && !chunk_over && (p.groups_cap * v[0][1] > p.val_cap || p.groups_cap * v[0][0] > p.valg_cap)) {   // incl. room for the paired run
-            chunk_over = true;
-            chunk_need = p.groups_cap * v[0][1];
-        }
-        p.h_label_off[i] = (size_t)pix;
-        off += (size_t)d.K * d.H * d.W;
-        pix += (int64_t)d.H * d.W;
+        if (chunk_ends && !chunk_need && (p.groups_cap * at[0].voff[1] > p.crf.val_cap || p.groups_cap * at[0].voff[0] > p.crf.valg_cap))
+            chunk_need = p.groups_cap * at[0].voff[1];                     // incl. room for the paired run
+        p.h_label_off[i] = (size_t)d.pix0;
         p.maxH = std::max(p.maxH, d.H); p.maxW = std::max(p.maxW, d.W); p.maxHW = std::max(p.maxHW, d.H * d.W);
         p.Cmax = std::max(p.Cmax, d.C); p.Kmax = std::max(p.Kmax, d.K);
         p.h_wt_off[i] = (int32_t)p.h_wts.size();
@@ -197,15 +140,14 @@ static int post_layout(pnp_engine* e, const pnp_post_batch* b) {
         p.max_radius = std::max(p.max_radius, (int)p.h_wts.size() - p.h_wt_off[i] - 1);
     }
     p.h_wt_off[B] = (int32_t)p.h_wts.size();
-    p.h_label_off[B] = (size_t)pix;
-    if (pix > p.max_total_pix) return fail(e, PNP_ERR_ARG, "batch has %lld pixels, reserved %lld", (long long)pix, (long long)p.max_total_pix);
+    p.h_label_off[B] = (size_t)at[0].pix;
+    if (at[0].pix > p.max_total_pix) return fail(e, PNP_ERR_ARG, "batch has %lld pixels, reserved %lld", (long long)at[0].pix, (long long)p.max_total_pix);
     if ((int)p.h_wts.size() > p.wts_cap) return fail(e, PNP_ERR_ARG, "blur taps exceed reserved capacity");
     const int ncls = b->img_cls_off[B], ntok = b->cls_off[ncls];
     if (ncls > p.cls_cap || ntok > p.tok_cap) return fail(e, PNP_ERR_ARG, "merge plan exceeds reserved capacity");
     if (b->lut_stride < p.Kmax || B * b->lut_stride > p.lut_cap) return fail(e, PNP_ERR_ARG, "bad lut_stride");
-    if (chunk_over) return fail(e, PNP_ERR_ARG, "CRF chunk needs %zu value floats, reserved %zu", chunk_need, p.val_cap);
+    if (chunk_need) return fail(e, PNP_ERR_ARG, "CRF chunk needs %zu value floats, reserved %zu", chunk_need, p.crf.val_cap);
     p.B = B;
-    p.total_pix = pix;
     p.lut_stride = b->lut_stride;
     p.d_rgb = b->d_rgb;
     p.d_gt = b->d_gt;
@@ -231,28 +173,16 @@ static int post_upload(pnp_engine* e, const pnp_post_batch* b, hipStream_t s) {
     return PNP_OK;
 }
 
-// Step 3: the two lattices of the batch (the features are fixed per batch) and their normalisers.  The bilateral one is built
-// every time, so every call synchronises once, inside crf_build_lattice's read-back.
+// Step 3: the two lattices of the batch and their normalisers, for the reference's widths.  The bilateral one is built every
+// time, so every call synchronises once, inside the build's read-back.
 static int post_build_lattices(pnp_engine* e, hipStream_t s) {
     auto& p = e->post;
-    std::vector<int> sig;
-    for (const PostDesc& d : p.desc[0]) { sig.push_back(d.H); sig.push_back(d.W); }
-    for (int t = 0; t < 2; t++) {
-        // the Gaussian (xy-only) lattice depends on the image sizes alone: keep it across batches
-        if (t == 0 && sig == p.gauss_sig) continue;
-        const size_t entries = (size_t)p.total_pix * p.lat[t].D1;
-        const float xy = t == 0 ? CRF_POS_XY : CRF_BI_XY;      // one width for both position axes and one for the three colours
-        const float sxy[2] = {xy, xy}, srgb[3] = {CRF_BI_RGB, CRF_BI_RGB, CRF_BI_RGB};
-        KCHK(e, crf_build_lattice(p.lat[t].D1 - 1, p.lat[t], p.view[0].d_desc, p.desc[0].data(), p.d_rgb, sxy, srgb, p.B, entries, p.maxHW, p.scratch, &p.range_err_host, &p.lat_points[t], s));
-        KCHK(e, crf_lattice_norm(p.lat[t], p.view[0].d_desc, p.B, p.maxHW, entries, p.va, p.vb, p.norm[t], s));
-    }
-    if (p.range_err_host) {                    // (read back with the lattice size inside crf_build_lattice: no extra sync)
-        p.range_err_host = 0;                  // leave no stale state behind: the next prepare rebuilds both lattices
-        p.gauss_sig.clear();
-        (void)hipMemsetAsync(p.scratch.range_err, 0, 4, s);
-        return fail(e, PNP_ERR_ARG, "lattice key out of packing range (image too large for the 64-bit key)");
-    }
-    p.gauss_sig = sig;
+    const float pos_xy[2] = {CRF_POS_XY, CRF_POS_XY}, bi_xy[2] = {CRF_BI_XY, CRF_BI_XY}, bi_rgb[3] = {CRF_BI_RGB, CRF_BI_RGB, CRF_BI_RGB};
+    int range_term = -1;
+    const int r = crf_build(p.crf, p.view[0].d_desc, p.desc[0].data(), p.B, p.h_label_off[p.B], p.maxHW, p.d_rgb, pos_xy, bi_xy, bi_rgb,
+                            &range_term, s);
+    if (range_term >= 0) return fail(e, r, "lattice key out of packing range (image too large for the 64-bit key)");
+    if (r != PNP_OK) return fail(e, r, "CRF lattice build failed (%d): %s", r, hipGetErrorString(hipGetLastError()));
     p.has_crf = true;
     return PNP_OK;
 }
@@ -267,7 +197,7 @@ extern "C" int pnp_post_prepare(pnp_engine* e, const pnp_post_batch* b, int32_t 
     if (want_crf && !b->d_rgb) return fail(e, PNP_ERR_ARG, "CRF needs d_rgb");
     hipStream_t s = (hipStream_t)stream;
     p.prepared = false;
-    if (int r = post_layout(e, b)) return r;
+    if (int r = post_layout(e, b, want_crf != 0)) return r;
     if (int r = post_upload(e, b, s)) return r;
     p.has_crf = false;
     // one synchronisation per batch: the lattice build's, or without a lattice to build this one
@@ -356,27 +286,20 @@ static void crf_count_bytes(pnp_engine* e, int groups, int iters) {
     }
     const double kavg = pix > 0 ? kpix / pix : 0;
     e->crf_prof.work += (double)iters * 20.0 * 4.0 * groups * kpix;
-    e->crf_prof.lattice += (double)iters * 2.0 * 4.0 * groups * kavg * (2.0 * p.lat_points[0] + 3.0 * p.lat_points[1]);
+    e->crf_prof.lattice += (double)iters * 2.0 * 4.0 * groups * kavg * (2.0 * p.crf.lat_points[0] + 3.0 * p.crf.lat_points[1]);
 }
 
-// mean-field iterations over the unary rows already in p.unary, chunk by chunk, in the single- or two-group layout `v`.
-// labels: when set, the last update also writes the label maps (argmax + LUT fused into it: no separate pass over Q)
-static int crf_iterate(pnp_engine* e, const PostView& v, int32_t iters, float pos_w, float bi_w, hipStream_t s,
+// mean-field iterations over the unary rows already in p.crf.unary, chunk by chunk, in the single- or two-group layout `v`.
+// labels: when set, the last update of every chunk also writes the label maps (argmax + LUT fused into it: no separate pass over Q)
+static int crf_iterate(pnp_engine* e, CrfSpan v, int32_t iters, float pos_w, float bi_w, hipStream_t s,
                        const CrfLabelOut& labels = CrfLabelOut()) {
     auto& p = e->post;
     bool timed = false;
     if (int r = crf_timer_start(e, s, &timed)) return r;
     for (int c0 = 0; c0 < p.B; c0 += p.chunk) {
-        const int n = std::min(p.chunk, p.B - c0);
-        KCHK(e, crf_update(p.lat[0], p.lat[1], v.d_desc, c0, n, p.vga, p.va, p.norm[0], p.norm[1], p.unary, p.Q, pos_w, bi_w, 0,
-                           v.kp_max, v.groups, s));
-        for (int it = 0; it < iters; it++) {
-            const float *rg = nullptr, *rb = nullptr;
-            KCHK(e, crf_filter(p.lat[0], v.d_desc, c0, n, p.Q, p.vga, p.vgb, &rg, v.kp_max, s));
-            KCHK(e, crf_filter(p.lat[1], v.d_desc, c0, n, p.Q, p.va, p.vb, &rb, v.kp_max, s));
-            KCHK(e, crf_update(p.lat[0], p.lat[1], v.d_desc, c0, n, rg, rb, p.norm[0], p.norm[1], p.unary, p.Q, pos_w, bi_w, 1,
-                               v.kp_max, v.groups, s, it == iters - 1 ? labels : CrfLabelOut()));
-        }
+        v.img0 = c0;
+        v.nimg = std::min(p.chunk, p.B - c0);
+        KCHK(e, crf_meanfield(p.crf, v, true, iters, pos_w, bi_w, nullptr, nullptr, 0, s, labels));
     }
     if (timed) {
         crf_timer_stop(e, s);
@@ -394,7 +317,7 @@ extern "C" int pnp_densecrf(pnp_engine* e, int32_t iters, float pos_w, float pos
         return fail(e, PNP_ERR_ARG, "lattices are built for sxy=%g / sxy=%g, srgb=%g (PnP.py:1036-1041)", CRF_POS_XY, CRF_BI_XY, CRF_BI_RGB);
     hipStream_t s = (hipStream_t)stream;
     const float* maps = p.maps_in_2 ? p.maps2 : p.maps;
-    KCHK(e, unary_from_maps(maps, p.view[0].d_desc, p.unary, p.B, p.maxHW, p.maxKp, 0, s));
+    KCHK(e, unary_from_maps(maps, p.view[0].d_desc, p.crf.unary, p.B, p.maxHW, p.maxKp, 0, s));
     return crf_iterate(e, p.view[0], iters, pos_w, bi_w, s);
 }
 
@@ -405,7 +328,7 @@ extern "C" int pnp_remap_hist(pnp_engine* e, int32_t from_crf, uint8_t* d_labels
     const PostDesc* desc = p.view[0].d_desc;
     if (!d_labels) return fail(e, PNP_ERR_ARG, "d_labels is null");
     hipStream_t s = (hipStream_t)stream;
-    const float* src = from_crf ? p.Q : (p.maps_in_2 ? p.maps2 : p.maps);
+    const float* src = from_crf ? p.crf.Q : (p.maps_in_2 ? p.maps2 : p.maps);
     KCHK(e, argmax_remap(src, desc, p.d_lut, p.lut_stride, d_labels, p.d_label_off, from_crf ? 1 : 0, 0, p.B, p.maxHW, s));
     if (d_hist && p.d_gt) KCHK(e, confusion_hist(d_labels, p.d_gt, desc, p.d_label_off, d_hist, n_class, p.B, p.maxHW, s));
     return PNP_OK;
@@ -443,7 +366,7 @@ extern "C" int pnp_postprocess_pair(pnp_engine* e, const float* d_gradcam_1drop,
         // PnP.py: Scale_0_1 in the 1-drop branch only; PnPc.py: both
         if (int r = pnp_threshold_upsample(e, threshold, (scale01_mask >> grp) & 1, stream)) return r;
         if (int r = pnp_blur_minmax(e, stream)) return r;
-        KCHK(e, unary_from_maps(p.maps2, p.view[1].d_desc, p.unary, p.B, p.maxHW, p.maxKp, grp, s));
+        KCHK(e, unary_from_maps(p.maps2, p.view[1].d_desc, p.crf.unary, p.B, p.maxHW, p.maxKp, grp, s));
     }
     const CrfLabelOut lout{{d_labels_1drop, d_labels_ndrop}, p.d_lut, p.lut_stride, p.d_label_off};
     if (int r = crf_iterate(e, p.view[1], CRF_ITERS, CRF_POS_W, CRF_BI_W, s, lout)) return r;
@@ -466,15 +389,15 @@ bool pnp::post_get_buffer(pnp_engine* e, const std::string& n, void** d_ptr, siz
     if (n == "merged") return set(p.merged, (size_t)p.maxB * p.maxK * e->PP * 4);
     if (n == "maps") return set(p.maps_in_2 ? p.maps2 : p.maps, mk);
     if (n == "maps_pre_blur") return set(p.maps, mk);
-    if (n == "unary") return set(p.unary, mq);
-    if (n == "crf_q") return set(p.Q, mq);
-    if (n == "crf_idbase_gauss") return set(p.lat[0].idbase, ((size_t)p.maxB + 1) * 4);
-    if (n == "crf_idbase_bilateral") return set(p.lat[1].idbase, ((size_t)p.maxB + 1) * 4);
-    if (n == "crf_norm_gauss") return set(p.norm[0], (size_t)p.max_total_pix * 4);
-    if (n == "crf_norm_bilateral") return set(p.norm[1], (size_t)p.max_total_pix * 4);
-    if (n == "crf_offset_gauss") return set(p.lat[0].offset, (size_t)p.max_total_pix * 3 * 4);          // per pixel: 3 lattice ids
-    if (n == "crf_offset_bilateral") return set(p.lat[1].offset, (size_t)p.max_total_pix * 6 * 4);  // per pixel: 6 lattice ids
-    if (n == "crf_nbr8_gauss") return set(p.lat[0].nbr8, (size_t)(p.lat[0].D1 / 2) * p.lat[0].cap * sizeof(CrfNbr8));
-    if (n == "crf_nbr8_bilateral") return set(p.lat[1].nbr8, (size_t)(p.lat[1].D1 / 2) * p.lat[1].cap * sizeof(CrfNbr8));
+    if (n == "unary") return set(p.crf.unary, mq);
+    if (n == "crf_q") return set(p.crf.Q, mq);
+    if (n == "crf_idbase_gauss") return set(p.crf.lat[0].idbase, ((size_t)p.maxB + 1) * 4);
+    if (n == "crf_idbase_bilateral") return set(p.crf.lat[1].idbase, ((size_t)p.maxB + 1) * 4);
+    if (n == "crf_norm_gauss") return set(p.crf.norm[0], (size_t)p.max_total_pix * 4);
+    if (n == "crf_norm_bilateral") return set(p.crf.norm[1], (size_t)p.max_total_pix * 4);
+    if (n == "crf_offset_gauss") return set(p.crf.lat[0].offset, (size_t)p.max_total_pix * 3 * 4);          // per pixel: 3 lattice ids
+    if (n == "crf_offset_bilateral") return set(p.crf.lat[1].offset, (size_t)p.max_total_pix * 6 * 4);  // per pixel: 6 lattice ids
+    if (n == "crf_nbr8_gauss") return set(p.crf.lat[0].nbr8, (size_t)(p.crf.lat[0].D1 / 2) * p.crf.lat[0].cap * sizeof(CrfNbr8));
+    if (n == "crf_nbr8_bilateral") return set(p.crf.lat[1].nbr8, (size_t)(p.crf.lat[1].D1 / 2) * p.crf.lat[1].cap * sizeof(CrfNbr8));
     return false;
 }
