@@ -1,5 +1,6 @@
 // Internal to csrc/ (not installed, never included from include/): the engine's state and the few helpers its translation
-// units share -- engine.hip (lifetime, weights, model, introspection, operator shims) and post.hip (post-processing).
+// units share -- engine.hip (lifetime, weights, introspection), model.hip (the model sequence and the drop loop), ops.hip (operator
+// shims and the entry points without engine state) and post.hip (post-processing).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -8,6 +9,7 @@
 #include <map>
 #include <memory>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/pnp_hip.h"
@@ -116,12 +118,6 @@ struct pnp_engine {
     // ---- activations
     int ldq = 0;               // row stride (elements) of the fused q|k|v buffer
     float* x0 = nullptr;       // [M, D] token embeddings of drop iteration 0 (patch embed + pos, cls row): later iterations reuse them
-    // what the reusable state was computed from (embed == 1 call): an embed == 2 call that does not match recomputes instead.
-    // CONTRACT: the record catches stale POINTERS and SHAPES, not stale CONTENTS -- a caller that refills the same image / id
-    // buffers in place between an embed == 1 and an embed == 2 call gets the old embeddings (the one caller, pnp_drop_loop_layer,
-    // always starts a batch with embed == 1; pnp_vit_forward / pnp_text_forward_xattn invalidate the record)
-    struct { const float* images = nullptr; const int64_t* ids = nullptr; const int64_t* mask = nullptr; int B = 0, L = 0, ld = 0;
-             bool vit = false, text = false; } reuse;
     void *patches = nullptr, *vt = nullptr;
     pnp::Act xn, qk, ctx, h1, embT;
     float *x = nullptr, *emb32 = nullptr;
@@ -230,6 +226,45 @@ inline int dalloc_t(pnp_engine* e, void** out, size_t count, bool zero = false) 
 }
 // a raw kernel launch: KCHK(e, launched()) right behind it
 inline int launched() { return hipPeekAtLastError() == hipSuccess ? PNP_OK : PNP_ERR_HIP; }   // (KCHK reads and clears the error)
+
+// state-dict names of the optional ITC projections, [0] / [1] as in pnp_engine::proj_w
+inline const char* const kProj[2] = {"vision_proj", "text_proj"};
+
+inline GemmArgs G_(const void* A, int lda, const void* B, int ldb, int M, int N, int K) {
+    GemmArgs g;
+    g.A = A; g.lda = lda; g.B = B; g.ldb = ldb; g.M = M; g.N = N; g.K = K;
+    return g;
+}
+
+// The launch of a Linear in the engine's mode, y[M, n] = a[M, K] . w[r0 .. r0 + n, K]^T (n = 0: the whole weight); the caller
+// adds the epilogue.  A pair weight (bf16x3) meets either a pair activation, or one fp32 array whose rows the kernel splits
+// (a_f32: the text side, gemm_nt_small_x3_kernel).
+inline GemmArgs linear(const void* a, int lda, const Weight& w, int M, int r0 = 0, int n = 0) {
+    GemmArgs g = G_(a, lda, w.hi(r0), w.cols, M, n ? n : w.rows, w.cols);
+    g.B_lo = w.lo(r0);
+    g.a_f32 = w.pair;
+    return g;
+}
+inline GemmArgs linear(const Act& a, int lda, const Weight& w, int M, int r0 = 0, int n = 0) {
+    GemmArgs g = linear(a.hi, lda, w, M, r0, n);
+    g.A_lo = a.lo;
+    g.a_f32 = w.pair && !a.lo;
+    return g;
+}
+// the same product written feature-major, y^T[n, M] = w . a^T: the operands change places
+inline GemmArgs linear_t(const Act& a, int lda, const Weight& w, int M, int r0 = 0, int n = 0) {
+    GemmArgs g = linear(a, lda, w, M, r0, n);
+    std::swap(g.A, g.B); std::swap(g.A_lo, g.B_lo); std::swap(g.lda, g.ldb); std::swap(g.M, g.N);
+    return g;
+}
+
+// every GEMM of an engine goes through here: the launch is timed into the engine's own ring when profiling is on.  gemm_nt
+// takes the bf16 kernels by itself when an operand is a pair
+inline int egemm(pnp_engine* e, GemmArgs g, hipStream_t s) {
+    g.prof = e->gemm_prof;
+    g.sk = e->sk_ws.part ? &e->sk_ws : nullptr;
+    return gemm_nt(e->bf, g, s);
+}
 
 // post.hip's share of pnp_get_buffer: the post-process arrays by name (false: not one of them, or nothing reserved yet)
 bool post_get_buffer(pnp_engine* e, const std::string& name, void** d_ptr, size_t* bytes);

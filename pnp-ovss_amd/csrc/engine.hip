@@ -1,11 +1,8 @@
-// The engine behind include/pnp_hip.h: owns weights + workspace on one MI355X, sequences the
-// hand-written kernels of this directory on the caller's stream: lifetime, weights, model, introspection and the operator
-// shims (the post-processing entry points are in post.hip; the state both share is engine.h).  Host logic, but for four small
-// layout kernels (transpose_cast_kernel_f32, feat_to_tok_kernel, tok_to_feat_kernel, embed_reuse_kernel); every FLOP of the
-// hot path is in the other .hip files.  No allocation / sync inside hot-path calls.
-#include <cmath>
+// The engine behind include/pnp_hip.h: owns weights + workspace on one MI355X.  This unit is its lifetime, the weight loader,
+// introspection and profiling; the sequences of the hand-written kernels of this directory on the caller's stream are in
+// model.hip (the model) and post.hip (post-processing), the entry points that need no engine in ops.hip, and the state all of
+// them share is engine.h.  Host logic, but for one small layout kernel (transpose_cast_kernel_f32).
 #include <cstring>
-#include <utility>
 
 #include "engine.h"
 
@@ -38,62 +35,6 @@ __global__ void transpose_cast_kernel_f32(const float* __restrict__ in, float* _
     }
 }
 
-// The two extra layouts the analytic backward reads (V token-major for text layers >= stash_layer, K^T feature-major for
-// layers > stash_layer) as 32 x 32 LDS transposes of what the forward's two cross K / V GEMMs have just written, instead of
-// two more GEMMs over the same products (split-bf16 mode: 0.56 ms of GEMM per forward against 0.18 ms of copies; the copies
-// are also bit-identical to the forward's values, which two GEMMs with swapped operand roles are not).
-//   feat_to_tok: src [R features, ld_src] with token column b * n_pad + t  ->  dst [(b * N + t), R]
-__global__ void feat_to_tok_kernel(const float* __restrict__ src, int ld_src, int n_pad, float* __restrict__ dst, int R, int N) {
-    __shared__ float t[32][33];
-    const int b = blockIdx.z, r0 = blockIdx.x * 32, t0 = blockIdx.y * 32;
-    for (int i = threadIdx.y; i < 32; i += 8) {
-        const int r = r0 + i, tok = t0 + threadIdx.x;
-        t[i][threadIdx.x] = (r < R && tok < N) ? src[(size_t)r * ld_src + (size_t)b * n_pad + tok] : 0.f;
-    }
-    __syncthreads();
-    for (int i = threadIdx.y; i < 32; i += 8) {
-        const int tok = t0 + i, r = r0 + threadIdx.x;
-        if (r < R && tok < N) dst[((size_t)b * N + tok) * R + r] = t[threadIdx.x][i];
-    }
-}
-//   tok_to_feat: src [(b * N + t), ld_src] columns c0 .. c0 + R  ->  dst [R features, ld_dst] at token column b * n_pad + t
-__global__ void tok_to_feat_kernel(const float* __restrict__ src, int ld_src, float* __restrict__ dst, int ld_dst, int n_pad, int R, int N) {
-    __shared__ float t[32][33];
-    const int b = blockIdx.z, r0 = blockIdx.x * 32, t0 = blockIdx.y * 32;
-    for (int i = threadIdx.y; i < 32; i += 8) {
-        const int tok = t0 + i, r = r0 + threadIdx.x;
-        t[i][threadIdx.x] = (r < R && tok < N) ? src[((size_t)b * N + tok) * ld_src + r] : 0.f;
-    }
-    __syncthreads();
-    for (int i = threadIdx.y; i < 32; i += 8) {
-        const int r = r0 + i, tok = t0 + threadIdx.x;
-        if (r < R && tok < N) dst[(size_t)r * ld_dst + (size_t)b * n_pad + tok] = t[threadIdx.x][i];
-    }
-}
-
-// Patch embeddings of a later drop iteration: the images are the ones of iteration 0 with more 16 x 16 blocks zeroed
-// (PnP.py:597-603), so a token's embedding is either what iteration 0 computed or, for a dropped patch, bias + pos exactly as the
-// GEMM epilogue forms it from a zero accumulator ((0 + bias[n]) + pos[t][n]); the cls row never changes.  One pass over x instead of
-// patchify + the patch GEMM.
-__global__ void embed_reuse_kernel(const float* __restrict__ x0, const uint8_t* __restrict__ dropped, const float* __restrict__ bias,
-                                   const float* __restrict__ pos, float* __restrict__ x, int rows, int N, int D4) {
-    const size_t total = (size_t)rows * D4;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int m = (int)(i / D4), c = (int)(i - (size_t)m * D4);
-        const int b = m / N, t = m - b * N;
-        f32x4 v;
-        if (t > 0 && dropped[(size_t)b * (N - 1) + (t - 1)]) {
-            const f32x4 bv = reinterpret_cast<const f32x4*>(bias)[c];
-            const f32x4 pv = reinterpret_cast<const f32x4*>(pos)[(size_t)t * D4 + c];
-#pragma unroll
-            for (int e = 0; e < 4; e++) v[e] = __fadd_rn(__fadd_rn(0.0f, bv[e]), pv[e]);
-        } else {
-            v = reinterpret_cast<const f32x4*>(x0)[i];
-        }
-        reinterpret_cast<f32x4*>(x)[i] = v;
-    }
-}
-
 int new_weight(pnp_engine* e, int rows, int cols, bool pair, Weight* w) {
     *w = Weight{nullptr, rows, cols, pair ? 2 : (int)e->esz, pair};
     return dalloc_t(e, &w->p, (size_t)rows * cols);      // a pair belongs to bf16x3, whose compute type is fp32
@@ -121,42 +62,6 @@ int make_weight(pnp_engine* e, const float* src32, int rows, int cols, bool tran
     if (tmp) (void)hipFree(tmp);
     if (r != PNP_OK || st != hipSuccess) return fail(e, PNP_ERR_HIP, "weight conversion failed");
     return PNP_OK;
-}
-
-GemmArgs G_(const void* A, int lda, const void* B, int ldb, int M, int N, int K) {
-    GemmArgs g;
-    g.A = A; g.lda = lda; g.B = B; g.ldb = ldb; g.M = M; g.N = N; g.K = K;
-    return g;
-}
-
-// The launch of a Linear in the engine's mode, y[M, n] = a[M, K] . w[r0 .. r0 + n, K]^T (n = 0: the whole weight); the caller
-// adds the epilogue.  A pair weight (bf16x3) meets either a pair activation, or one fp32 array whose rows the kernel splits
-// (a_f32: the text side, gemm_nt_small_x3_kernel).
-GemmArgs linear(const void* a, int lda, const Weight& w, int M, int r0 = 0, int n = 0) {
-    GemmArgs g = G_(a, lda, w.hi(r0), w.cols, M, n ? n : w.rows, w.cols);
-    g.B_lo = w.lo(r0);
-    g.a_f32 = w.pair;
-    return g;
-}
-GemmArgs linear(const Act& a, int lda, const Weight& w, int M, int r0 = 0, int n = 0) {
-    GemmArgs g = linear(a.hi, lda, w, M, r0, n);
-    g.A_lo = a.lo;
-    g.a_f32 = w.pair && !a.lo;
-    return g;
-}
-// the same product written feature-major, y^T[n, M] = w . a^T: the operands change places
-GemmArgs linear_t(const Act& a, int lda, const Weight& w, int M, int r0 = 0, int n = 0) {
-    GemmArgs g = linear(a, lda, w, M, r0, n);
-    std::swap(g.A, g.B); std::swap(g.A_lo, g.B_lo); std::swap(g.lda, g.ldb); std::swap(g.M, g.N);
-    return g;
-}
-
-// every GEMM of an engine goes through here: the launch is timed into the engine's own ring when profiling is on.  gemm_nt
-// takes the bf16 kernels by itself when an operand is a pair
-int egemm(pnp_engine* e, GemmArgs g, hipStream_t s) {
-    g.prof = e->gemm_prof;
-    g.sk = e->sk_ws.part ? &e->sk_ws : nullptr;
-    return gemm_nt(e->bf, g, s);
 }
 
 }  // namespace
@@ -466,7 +371,6 @@ bool resolve(pnp_engine* e, const std::string& n, Key& s) {
 
 // the optional ITC projections: 1 = `name` is one of the four tensors (staged like a GEMM weight until finalize), 0 = it is
 // not, < 0 = its shape contradicts the model.  The embedding width E is the weight's first dimension.
-const char* const kProj[2] = {"vision_proj", "text_proj"};
 int resolve_proj(pnp_engine* e, const std::string& n, const int64_t* shape, int ndim, Key& s) {
     int which = -1;
     bool bias = false;
@@ -605,460 +509,6 @@ extern "C" int pnp_finalize_weights(pnp_engine* e) {
     return PNP_OK;
 }
 
-// =========================================================================================== model
-
-// embed: 0 = compute the token embeddings (the operator form) | 1 = compute them and keep a copy (drop iteration 0) | 2 = the
-// images are those of the last embed-1 call with the patches of d_dropped zeroed: reuse the copy (embed_reuse_kernel)
-static int vit_forward_impl(pnp_engine* e, const float* d_images, const uint8_t* d_dropped, int32_t B, void* stream, int embed) {
-    if (!e || !d_images) return PNP_ERR_ARG;
-    if (!e->finalized) return fail(e, PNP_ERR_STATE, "weights not finalized");
-    if (B <= 0 || B > e->c.max_batch) return fail(e, PNP_ERR_ARG, "batch %d out of range (max %d)", B, e->c.max_batch);
-    hipStream_t s = (hipStream_t)stream;
-    const int D = e->D, N = e->N, M = B * N, F = D * e->c.vit_mlp_ratio, bf = e->bf;
-    const int ldv = e->c.max_batch * e->Npad;
-    if (embed == 2 && !(e->reuse.vit && e->reuse.images == d_images && e->reuse.B == B)) embed = 0;   // stale: recompute
-    if (embed == 2 && d_dropped) {
-        hipLaunchKernelGGL(embed_reuse_kernel, dim3(2048), dim3(256), 0, s, (const float*)e->x0, d_dropped, (const float*)e->patch_b,
-                           (const float*)e->pos, e->x, M, N, D / 4);
-        KCHK(e, launched());
-    } else {
-        KCHK(e, patchify(bf, d_images, d_dropped, e->patches, B, e->c.img_size, e->P, s));
-        KCHK(e, cls_rows(e->cls, e->pos, e->x, B, N, D, s));
-        {
-            GemmArgs g = linear(e->patches, 768, e->patch_w, B * e->PP);
-            g.bias = e->patch_b; g.resid = e->pos; g.ldr = D; g.out_f32 = e->x; g.ldo = D; g.row_div = e->PP;
-            KCHK(e, egemm(e, g, s));
-        }
-        if (embed == 1) {
-            HIPCHK(e, hipMemcpyAsync(e->x0, e->x, (size_t)M * D * sizeof(float), hipMemcpyDeviceToDevice, s));
-            e->reuse.images = d_images;
-            e->reuse.B = B;
-            e->reuse.vit = true;
-        }
-    }
-    const float scale = 1.0f / sqrtf(64.f);
-    // split-bf16 ("bf16x3"): every Linear of the block is a wide-kernel launch on (hi, lo) bf16 operand pairs -- three bf16 MFMA
-    // passes per product, fp32-class result; LayerNorm, the attention kernel and the GELU epilogue hand the next GEMM its
-    // operand already split (the handles' lo halves, null in the other modes)
-    const int ln = bf | e->x3;                   // LayerNorm writes bf16 for the pair too
-    for (int l = 0; l < e->c.vit_depth; l++) {
-        const VitLayerW& w = e->vit[l];
-        KCHK(e, layernorm(ln, e->x, w.n1w, w.n1b, e->c.vit_ln_eps, M, D, nullptr, e->xn.hi, nullptr, nullptr, s, e->xn.lo));
-        if (bf || e->x3) {   // q | k | v natural in one launch: [M, 3D] at the padded stride; the attention kernel transposes V on its LDS reads
-            GemmArgs g = linear(e->xn, D, w.qkv_w, M);
-            g.bias = w.qkv_b; g.out_t = e->qk.hi; g.out_lo = e->qk.lo; g.ldo_t = e->ldq;
-            KCHK(e, egemm(e, g, s));
-            if (e->x3)       // the split form of the bf16 kernel (vit_attn32_x3_kernel)
-                KCHK(e, vit_attention_x3(e->qk.hi, e->qk.lo, e->ldq, D, e->ctx.hi, e->ctx.lo, B, e->c.vit_heads, N, scale, s));
-            else
-                KCHK(e, vit_attention(bf, e->qk.hi, e->ldq, D, (const char*)e->qk.hi + (size_t)2 * D * e->esz, e->ldq, e->Npad, e->ctx.hi,
-                                      B, e->c.vit_heads, N, scale, s));
-        } else {
-            {   // q | k  natural: [M, 2D]
-                GemmArgs g = linear(e->xn, D, w.qkv_w, M, 0, 2 * D);
-                g.bias = w.qkv_b; g.out_t = e->qk.hi; g.ldo_t = 2 * D;
-                KCHK(e, egemm(e, g, s));
-            }
-            {   // V^T: [D, B*Npad] = Wv . xn^T, token columns padded per image
-                GemmArgs g = linear_t(e->xn, D, w.qkv_w, M, 2 * D, D);
-                g.bias = w.qkv_b + 2 * D; g.bias_on_rows = 1; g.out_t = e->vt; g.ldo_t = ldv; g.col_div = N; g.col_pad = e->Npad;
-                KCHK(e, egemm(e, g, s));
-            }
-            KCHK(e, vit_attention(bf, e->qk.hi, 2 * D, D, e->vt, ldv, e->Npad, e->ctx.hi, B, e->c.vit_heads, N, scale, s));
-        }
-        {
-            GemmArgs g = linear(e->ctx, D, w.proj_w, M);
-            g.bias = w.proj_b; g.resid = e->x; g.ldr = D; g.out_f32 = e->x; g.ldo = D;
-            KCHK(e, egemm(e, g, s));
-        }
-        KCHK(e, layernorm(ln, e->x, w.n2w, w.n2b, e->c.vit_ln_eps, M, D, nullptr, e->xn.hi, nullptr, nullptr, s, e->xn.lo));
-        {
-            GemmArgs g = linear(e->xn, D, w.fc1_w, M);
-            g.bias = w.fc1_b; g.mode = GEMM_EPI_GELU; g.out_t = e->h1.hi; g.out_lo = e->h1.lo; g.ldo_t = F;
-            KCHK(e, egemm(e, g, s));
-        }
-        {
-            GemmArgs g = linear(e->h1, F, w.fc2_w, M);
-            g.bias = w.fc2_b; g.resid = e->x; g.ldr = D; g.out_f32 = e->x; g.ldo = D;
-            KCHK(e, egemm(e, g, s));
-        }
-    }
-    KCHK(e, layernorm(ln, e->x, e->vnorm_w, e->vnorm_b, e->c.vit_ln_eps, M, D, e->emb32, e->embT.hi, nullptr, nullptr, s, e->embT.lo));
-    return pnp_cross_kv(e, B, stream);
-}
-extern "C" int pnp_vit_forward(pnp_engine* e, const float* d_images, const uint8_t* d_dropped, int32_t B, void* stream) {
-    if (e) e->reuse.vit = false;                 // the operator form writes e->x: x0 no longer describes what follows
-    return vit_forward_impl(e, d_images, d_dropped, B, stream, 0);
-}
-
-// encoder_hidden_states -> key / value of every text layer's cross-attention (B/med.py:208-211): the reference
-// projects image_embeds once per layer inside BertSelfAttention.forward; here all 12 layers are projected in four
-// launches (natural + transposed layouts) right after the ViT, from the compute-type copy of image_embeds.
-extern "C" int pnp_cross_kv(pnp_engine* e, int32_t B, void* stream) {
-    if (!e) return PNP_ERR_ARG;
-    if (!e->finalized) return fail(e, PNP_ERR_STATE, "weights not finalized");
-    if (B <= 0 || B > e->c.max_batch) return fail(e, PNP_ERR_ARG, "batch %d out of range (max %d)", B, e->c.max_batch);
-    hipStream_t s = (hipStream_t)stream;
-    const int D = e->D, N = e->N, M = B * N;
-    const int ldv = e->c.max_batch * e->Npad;
-    const int H = e->H, TL = e->TL, SL = e->SL, nVn = TL - SL, nKt = TL - SL - 1;
-    // K token-major and V^T feature-major of all layers: fp32 from the pair GEMM in bf16x3, the compute type otherwise
-    auto out = [&](GemmArgs& g, void* p, int ld) {
-        if (e->x3) { g.out_f32 = (float*)p; g.ldo = ld; }
-        else { g.out_t = p; g.ldo_t = ld; }
-    };
-    {
-        GemmArgs g = linear(e->embT, D, e->ck_w, M);
-        g.bias = e->ck_b; out(g, e->Knat, TL * H);
-        KCHK(e, egemm(e, g, s));
-    }
-    {
-        GemmArgs g = linear_t(e->embT, D, e->cv_w, M);
-        g.bias = e->cv_b; g.bias_on_rows = 1; out(g, e->Vt, ldv); g.col_div = N; g.col_pad = e->Npad;
-        KCHK(e, egemm(e, g, s));
-    }
-    // V token-major of layers >= SL, K^T of layers > SL
-    if (e->x3) {             // from V^T and from K token-major (see feat_to_tok_kernel)
-        hipLaunchKernelGGL(feat_to_tok_kernel, dim3((nVn * H + 31) / 32, (N + 31) / 32, B), dim3(32, 8), 0, s,
-                           (const float*)e->Vt + (size_t)SL * H * ldv, ldv, e->Npad, (float*)e->Vnat, nVn * H, N);
-        KCHK(e, launched());
-        if (nKt > 0) {
-            hipLaunchKernelGGL(tok_to_feat_kernel, dim3((nKt * H + 31) / 32, (N + 31) / 32, B), dim3(32, 8), 0, s,
-                               (const float*)e->Knat + (size_t)(SL + 1) * H, TL * H, (float*)e->Kt, ldv, e->Npad, nKt * H, N);
-            KCHK(e, launched());
-        }
-        return PNP_OK;
-    }
-    {
-        GemmArgs g = linear(e->embT, D, e->cv_w, M, SL * H, nVn * H);
-        g.bias = e->cv_b + (size_t)SL * H; g.out_t = e->Vnat; g.ldo_t = nVn * H;
-        KCHK(e, egemm(e, g, s));
-    }
-    if (nKt > 0) {
-        GemmArgs g = linear_t(e->embT, D, e->ck_w, M, (SL + 1) * H, nKt * H);
-        g.bias = e->ck_b + (size_t)(SL + 1) * H; g.bias_on_rows = 1; g.out_t = e->Kt; g.ldo_t = ldv; g.col_div = N; g.col_pad = e->Npad;
-        KCHK(e, egemm(e, g, s));
-    }
-    return PNP_OK;
-}
-
-// One BERT layer of the text stack on the R = B * L rows in place (layer 0 reads h0, layer i the h_out of layer i - 1): the
-// self-attention sub-layer, the cross-attention sub-layer over the image's K / V, the FFN.
-//   cross = false: the text-only form -- no cross-attention sub-layer (the FFN reads a_out), and nothing is kept for the backward
-//   self_in_place: the self-attention sub-layer's outputs of the previous call are valid (text_forward_impl's prefix reuse)
-static int text_layer(pnp_engine* e, int i, const int64_t* d_mask, int32_t ld, int32_t B, int32_t L, bool cross, bool self_in_place,
-                      hipStream_t s) {
-    const int H = e->H, I = e->I, TL = e->TL, R = B * L, bf = e->bf, N = e->N;
-    const int ldv = e->c.max_batch * e->Npad;
-    const TextLayerW& w = e->txt[i];
-    TextLayerA& a = e->ta[i];
-    const float* h = i ? e->ta[i - 1].h_out : e->h0;
-    const void* hT = i ? e->ta[i - 1].h_outT : e->h0T;
-    const bool keep_p = cross && i >= e->SL;                               // the attention probabilities of the stash layers
-    auto keep = [&](float* p) -> float* { return cross ? p : nullptr; };   // the LayerNorm x-hat / rstd the backward reads
-    if (!self_in_place) {
-        {
-            GemmArgs g = linear(hT, H, w.qkv_w, R);
-            g.bias = w.qkv_b; g.out_t = a.qkv; g.ldo_t = 3 * H;
-            KCHK(e, egemm(e, g, s));
-        }
-        KCHK(e, text_self_attn(bf, a.qkv, d_mask, ld, e->ctx_s, keep_p ? a.Ps : nullptr, e->dS, B, L, H, s));
-        {
-            GemmArgs g = linear(e->ctx_s, H, w.so_w, R);
-            g.bias = w.so_b; g.resid = h; g.ldr = H; g.out_f32 = e->tmp; g.ldo = H;
-            KCHK(e, egemm(e, g, s));
-        }
-        KCHK(e, layernorm(bf, e->tmp, w.sln_w, w.sln_b, e->c.txt_ln_eps, R, H, a.a_out, a.a_outT, keep(a.a_hat), keep(a.a_rstd), s));
-    }
-    const float* f = a.a_out;                    // the rows the FFN reads
-    const void* fT = a.a_outT;
-    if (cross) {
-        {
-            GemmArgs g = linear(a.a_outT, H, w.cq_w, R);
-            g.bias = w.cq_b; g.out_t = a.qc; g.ldo_t = H;
-            KCHK(e, egemm(e, g, s));
-        }
-        KCHK(e, xattn(bf, 0, (const char*)e->Knat + (size_t)i * H * e->esz, TL * H,
-                      (const char*)e->Vt + (size_t)i * H * ldv * e->esz, ldv, e->Npad, a.qc, H, e->ctx_c, H,
-                      keep_p ? a.Pc : nullptr, e->Nst, B, L, N, e->nh, s));
-        {
-            GemmArgs g = linear(e->ctx_c, H, w.co_w, R);
-            g.bias = w.co_b; g.resid = a.a_out; g.ldr = H; g.out_f32 = e->tmp; g.ldo = H;
-            KCHK(e, egemm(e, g, s));
-        }
-        KCHK(e, layernorm(bf, e->tmp, w.cln_w, w.cln_b, e->c.txt_ln_eps, R, H, a.c_out, a.c_outT, a.c_hat, a.c_rstd, s));
-        f = a.c_out;
-        fT = a.c_outT;
-    }
-    {
-        GemmArgs g = linear(fT, H, w.i_w, R);
-        g.bias = w.i_b; g.mode = GEMM_EPI_GELU; g.out_t = e->g; g.ldo_t = I;
-        if (cross) { g.aux = a.u; g.ld_aux = I; }                          // the GELU pre-activation, for the backward
-        KCHK(e, egemm(e, g, s));
-    }
-    {
-        GemmArgs g = linear(e->g, I, w.o_w, R);
-        g.bias = w.o_b; g.resid = f; g.ldr = H; g.out_f32 = e->tmp; g.ldo = H;
-        KCHK(e, egemm(e, g, s));
-    }
-    KCHK(e, layernorm(bf, e->tmp, w.oln_w, w.oln_b, e->c.txt_ln_eps, R, H, a.h_out, a.h_outT, keep(a.o_hat), keep(a.o_rstd), s));
-    return PNP_OK;
-}
-
-// reuse_prefix: the token ids / mask are those of the previous call on this engine (drop iterations 1..): the embeddings and the
-// self-attention sub-layer of text layer 0 do not see the image -- their activations of the previous call are still in place
-static int text_forward_impl(pnp_engine* e, const int64_t* d_ids, const int64_t* d_mask, int32_t ld, int32_t B, int32_t L,
-                             float* d_logits, void* stream, bool reuse_prefix) {
-    if (!e || !d_ids || !d_mask) return PNP_ERR_ARG;
-    if (!e->finalized) return fail(e, PNP_ERR_STATE, "weights not finalized");
-    if (B <= 0 || B > e->c.max_batch || L < 5 || L > e->c.max_text_len || ld < L)
-        return fail(e, PNP_ERR_ARG, "text batch %d x %d (ld %d) out of range (max %d x %d)", B, L, ld, e->c.max_batch, e->c.max_text_len);
-    hipStream_t s = (hipStream_t)stream;
-    const int H = e->H, TL = e->TL, R = B * L;
-    e->acts_text_only = false;
-    if (reuse_prefix && !(e->reuse.text && e->reuse.ids == d_ids && e->reuse.mask == d_mask && e->reuse.B == B && e->reuse.L == L &&
-                          e->reuse.ld == ld))
-        reuse_prefix = false;                    // not the captions whose prefix is in place: compute it
-    if (!reuse_prefix) {
-        KCHK(e, text_embed(d_ids, ld, e->word, e->tpos, e->temb, B, L, H, e->c.enc_token_id, e->c.vocab, s));
-        KCHK(e, layernorm(e->bf, e->temb, e->eln_w, e->eln_b, e->c.txt_ln_eps, R, H, e->h0, e->h0T, nullptr, nullptr, s));
-    }
-    for (int i = 0; i < TL; i++) {
-        int r = text_layer(e, i, d_mask, ld, B, L, true, reuse_prefix && i == 0, s);
-        if (r) return r;
-    }
-    KCHK(e, itm_head(e->ta[TL - 1].h_out, e->itm_w, e->itm_b, d_logits ? d_logits : e->logits_scratch, B, L, H, s));
-    return PNP_OK;
-}
-extern "C" int pnp_text_forward_xattn(pnp_engine* e, const int64_t* d_ids, const int64_t* d_mask, int32_t ld, int32_t B,
-                                      int32_t L, float* d_logits, void* stream) {
-    if (e) e->reuse.text = false;
-    return text_forward_impl(e, d_ids, d_mask, ld, B, L, d_logits, stream, false);
-}
-
-// BertModel.forward(mode="text") (B/med.py:565-568, 473): the text stack without its cross-attention sub-layers and without the
-// [ENC] substitution, for T texts that need no image.  Runs in the multimodal pass's activation buffers (temb, h0, tmp, ctx_s, g and
-// each layer's qkv / a_out / h_out with their compute-type copies; no stash is written), max_batch rows of text at a time, so what
-// those buffers held for a GradCAM backward is gone: the reuse record, the kept layer and the backward are invalidated.  image_embeds
-// and the cross K / V of the last pnp_vit_forward are not touched.
-extern "C" int pnp_text_forward_text(pnp_engine* e, const int64_t* d_ids, const int64_t* d_mask, int32_t ld, int32_t T, int32_t L,
-                                     float* d_hidden, void* stream) {
-    if (!e || !d_ids || !d_mask) return PNP_ERR_ARG;
-    if (T <= 0 || L < 2 || L > e->c.max_text_len || ld < L)
-        return fail(e, PNP_ERR_ARG, "text batch %d x %d (ld %d) out of range (2 <= L <= %d, T > 0)", T, L, ld, e->c.max_text_len);
-    if (!e->finalized) return fail(e, PNP_ERR_STATE, "weights not finalized");
-    hipStream_t s = (hipStream_t)stream;
-    const int H = e->H, TL = e->TL;
-    e->reuse.text = false;
-    e->grad_layer = -1;
-    e->acts_text_only = true;
-    for (int t0 = 0; t0 < T; t0 += e->c.max_batch) {
-        const int B = T - t0 < e->c.max_batch ? T - t0 : e->c.max_batch, R = B * L;
-        const int64_t* ids = d_ids + (size_t)t0 * ld;
-        const int64_t* mask = d_mask + (size_t)t0 * ld;
-        KCHK(e, text_embed(ids, ld, e->word, e->tpos, e->temb, B, L, H, -1, e->c.vocab, s));
-        KCHK(e, layernorm(e->bf, e->temb, e->eln_w, e->eln_b, e->c.txt_ln_eps, R, H, e->h0, e->h0T, nullptr, nullptr, s));
-        for (int i = 0; i < TL; i++) {
-            int r = text_layer(e, i, mask, ld, B, L, false, false, s);
-            if (r) return r;
-        }
-        if (d_hidden)
-            HIPCHK(e, hipMemcpyAsync(d_hidden + (size_t)t0 * L * H, e->ta[TL - 1].h_out, (size_t)R * H * sizeof(float),
-                                     hipMemcpyDeviceToDevice, s));
-    }
-    return PNP_OK;
-}
-
-// F.normalize(Linear(x), dim=-1) with vision_proj (which = 0) or text_proj (which = 1) (B/blip_image_text_matching.py:137-138,
-// 158-159, 260-263): the Linear is one launch of the mode's GEMM (exact fp32 MFMA | split-bf16 with the fp32 rows split by the
-// kernel | bf16 after a cast of the rows into the ViT's LayerNorm scratch) with fp32 output, then l2_normalize_rows in place.
-extern "C" int pnp_project_normalize(pnp_engine* e, int32_t which, const float* d_x, int64_t row_stride, int32_t rows, float* d_out,
-                                     void* stream) {
-    if (!e || !d_x || !d_out) return PNP_ERR_ARG;
-    if (which < 0 || which > 1) return fail(e, PNP_ERR_ARG, "which = %d: 0 (vision_proj) or 1 (text_proj)", which);
-    if (rows <= 0) return fail(e, PNP_ERR_ARG, "rows = %d", rows);
-    const int K = which == 0 ? e->D : e->H;
-    if (row_stride < K || row_stride % 4 || row_stride > (int64_t)1 << 30)
-        return fail(e, PNP_ERR_ARG, "row_stride %lld: a multiple of 4 elements, at least %d", (long long)row_stride, K);
-    // the GEMM kernels address an operand by 32-bit byte offsets from its base
-    if ((int64_t)rows * row_stride * 4 >= (int64_t)1 << 32)
-        return fail(e, PNP_ERR_ARG, "rows %d x row_stride %lld: the input must span less than 4 GiB", rows, (long long)row_stride);
-    if (!e->finalized) return fail(e, PNP_ERR_STATE, "weights not finalized");
-    const Weight& w = e->proj_w[which];
-    if (!w.p || !e->proj_b[which])
-        return fail(e, PNP_ERR_STATE, "missing weight %s.weight (the state dict held no %s.weight / .bias)", kProj[which], kProj[which]);
-    hipStream_t s = (hipStream_t)stream;
-    const int E = e->proj_E[which];
-    if (e->bf) {
-        // bf16 operands: rows are cast into xn (free between ViT forwards), as many at a time as it holds
-        size_t cap = (size_t)e->c.max_batch * e->N * e->D / K;
-        cap = cap < 16384 ? cap : 16384;           // (and few enough for the generic tiles: the wide bf16 kernel has no such epilogue)
-        for (size_t r0 = 0; r0 < (size_t)rows; r0 += cap) {
-            const int n = (int)((size_t)rows - r0 < cap ? (size_t)rows - r0 : cap);
-            KCHK(e, cast_rows_bf16(d_x + r0 * row_stride, (int)row_stride, e->xn.hi, n, K, s));
-            GemmArgs g = linear(e->xn.hi, K, w, n);
-            g.bias = e->proj_b[which]; g.out_f32 = d_out + r0 * E; g.ldo = E;
-            KCHK(e, egemm(e, g, s));
-        }
-    } else {
-        GemmArgs g = linear(d_x, (int)row_stride, w, rows);
-        g.bias = e->proj_b[which]; g.out_f32 = d_out; g.ldo = E;
-        KCHK(e, egemm(e, g, s));
-    }
-    KCHK(e, l2_normalize_rows(d_out, rows, E, 1e-12f, s));
-    return PNP_OK;
-}
-
-// sim = image_feat @ text_feat.t() (B/blip_image_text_matching.py:265).  Stateless.
-extern "C" int pnp_itc_similarity(const float* d_img_feat, const float* d_txt_feat, int32_t B, int32_t T, int32_t E, float* d_sim,
-                                  void* stream) {
-    if (!d_img_feat || !d_txt_feat || !d_sim || B <= 0 || T <= 0 || E <= 0 || E % 4) return PNP_ERR_ARG;
-    return itc_similarity(d_img_feat, d_txt_feat, d_sim, B, T, E, (hipStream_t)stream);
-}
-
-extern "C" int pnp_xattn_grad(pnp_engine* e, int32_t B, int32_t L, void* stream) {
-    return pnp_xattn_grad_layer(e, B, L, e ? e->SL : 0, stream);
-}
-
-extern "C" int pnp_xattn_grad_layer(pnp_engine* e, int32_t B, int32_t L, int32_t layer, void* stream) {
-    if (!e) return PNP_ERR_ARG;
-    if (!e->finalized) return fail(e, PNP_ERR_STATE, "weights not finalized");
-    if (B <= 0 || B > e->c.max_batch || L < 5 || L > e->c.max_text_len) return fail(e, PNP_ERR_ARG, "bad B/L");
-    if (layer < e->SL || layer >= e->TL)
-        return fail(e, PNP_ERR_ARG, "layer %d: cross-attention maps are kept for text layers %d..%d (stash_layer)", layer, e->SL, e->TL - 1);
-    if (e->acts_text_only)
-        return fail(e, PNP_ERR_STATE, "the text activations in place are those of pnp_text_forward_text: run pnp_text_forward_xattn first");
-    hipStream_t s = (hipStream_t)stream;
-    const int H = e->H, I = e->I, TL = e->TL, R = B * L, bf = e->bf, N = e->N, SL = e->SL;
-    const int ldv = e->c.max_batch * e->Npad, nVn = TL - SL;
-    e->grad_layer = layer;
-    KCHK(e, itm_grad_seed(e->itm_w, e->dh, B, L, H, s));
-    for (int i = TL - 1; i >= layer; i--) {
-        const TextLayerW& w = e->txt[i];
-        TextLayerA& a = e->ta[i];
-        KCHK(e, layernorm_bwd(bf, e->dh, w.oln_w, a.o_hat, a.o_rstd, R, H, e->d_pre, e->d_preT, s));
-        {   // dg = (d_pre . Wo2) * gelu'(u)
-            GemmArgs g = linear(e->d_preT, H, w.o_wT, R);
-            g.mode = GEMM_EPI_GELU_GRAD; g.aux = a.u; g.ld_aux = I; g.out_t = e->dg; g.ldo_t = I;
-            KCHK(e, egemm(e, g, s));
-        }
-        {   // dc = d_pre + dg . Wi
-            GemmArgs g = linear(e->dg, I, w.i_wT, R);
-            g.resid = e->d_pre; g.ldr = H; g.out_f32 = e->dc; g.ldo = H;
-            KCHK(e, egemm(e, g, s));
-        }
-        KCHK(e, layernorm_bwd(bf, e->dc, w.cln_w, a.c_hat, a.c_rstd, R, H, e->d_cpre, e->d_cpreT, s));
-        {
-            GemmArgs g = linear(e->d_cpreT, H, w.co_wT, R);
-            g.out_t = e->dctxc; g.ldo_t = H;
-            KCHK(e, egemm(e, g, s));
-        }
-        const char* vnat = (const char*)e->Vnat + (size_t)(i - SL) * H * e->esz;
-        if (i == layer) {
-            KCHK(e, xattn(bf, 2, vnat, nVn * H, nullptr, 0, e->Npad, e->dctxc, H, nullptr, 0, e->dPc, e->Nst, B, L, N, e->nh, s));
-            break;
-        }
-        KCHK(e, xattn(bf, 1, vnat, nVn * H, (const char*)e->Kt + (size_t)(i - SL - 1) * H * ldv * e->esz, ldv, e->Npad,
-                      e->dctxc, H, e->dqc, H, a.Pc, e->Nst, B, L, N, e->nh, s));
-        {
-            GemmArgs g = linear(e->dqc, H, w.cq_wT, R);
-            g.resid = e->d_cpre; g.ldr = H; g.out_f32 = e->da; g.ldo = H;
-            KCHK(e, egemm(e, g, s));
-        }
-        KCHK(e, layernorm_bwd(bf, e->da, w.sln_w, a.a_hat, a.a_rstd, R, H, e->d_apre, e->d_apreT, s));
-        {
-            GemmArgs g = linear(e->d_apreT, H, w.so_wT, R);
-            g.out_f32 = e->dctx_s; g.ldo = H;
-            KCHK(e, egemm(e, g, s));
-        }
-        KCHK(e, text_self_attn_bwd(bf, a.qkv, e->dctx_s, a.Ps, e->dS, e->dqkv, B, L, H, s));
-        {
-            GemmArgs g = linear(e->dqkv, 3 * H, w.qkv_wT, R);
-            g.resid = e->d_apre; g.ldr = H; g.out_f32 = e->dh; g.ldo = H;
-            KCHK(e, egemm(e, g, s));
-        }
-    }
-    return PNP_OK;
-}
-
-extern "C" int pnp_gradcam_gather(pnp_engine* e, const int64_t* d_mask, int32_t ld, int32_t B, int32_t L, int32_t head,
-                                  float* d_out, void* stream) {
-    if (!e || !d_mask || !d_out) return PNP_ERR_ARG;
-    if (head < 0 || head >= e->nh) return fail(e, PNP_ERR_ARG, "head %d out of range", head);
-    if (B <= 0 || B > e->c.max_batch || L < 5 || L > e->c.max_text_len || ld < L) return fail(e, PNP_ERR_ARG, "bad B/L/ld");
-    if (e->grad_layer < 0) return fail(e, PNP_ERR_STATE, "call pnp_xattn_grad first");
-    // P of the layer the last backward stopped at, and its dL/dP
-    KCHK(e, gradcam_gather(e->ta[e->grad_layer].Pc, e->dPc, d_mask, ld, d_out, B, e->nh, head, L, e->Nst, e->PP, (hipStream_t)stream));
-    return PNP_OK;
-}
-
-static int compute_gradcam_impl(pnp_engine* e, const float* d_images, const uint8_t* d_dropped, const int64_t* d_ids,
-                                const int64_t* d_mask, int32_t ld, int32_t B, int32_t L, int32_t layer, int32_t head,
-                                float* d_out, float* d_logits, void* stream, int embed) {
-    int r = vit_forward_impl(e, d_images, d_dropped, B, stream, embed);
-    if (r) return r;
-    // drop iterations 1..: same captions as iteration 0 (embed == 2 only comes from the drop loop; a stash layer of 0 keeps the
-    // probabilities of layer 0's self-attention, which are in place as well)
-    r = text_forward_impl(e, d_ids, d_mask, ld, B, L, d_logits, stream, embed == 2);
-    if (r) return r;
-    if (embed == 1) {                            // the prefix now in place belongs to these captions
-        e->reuse.ids = d_ids; e->reuse.mask = d_mask; e->reuse.L = L; e->reuse.ld = ld;
-        e->reuse.text = true;
-    } else if (embed == 0) {
-        e->reuse.text = false;
-    }
-    r = pnp_xattn_grad_layer(e, B, L, layer, stream);
-    if (r) return r;
-    return pnp_gradcam_gather(e, d_mask, ld, B, L, head, d_out, stream);
-}
-extern "C" int pnp_compute_gradcam_layer(pnp_engine* e, const float* d_images, const uint8_t* d_dropped, const int64_t* d_ids,
-                                         const int64_t* d_mask, int32_t ld, int32_t B, int32_t L, int32_t layer, int32_t head,
-                                         float* d_out, float* d_logits, void* stream) {
-    return compute_gradcam_impl(e, d_images, d_dropped, d_ids, d_mask, ld, B, L, layer, head, d_out, d_logits, stream, 0);
-}
-
-extern "C" int pnp_compute_gradcam(pnp_engine* e, const float* d_images, const uint8_t* d_dropped, const int64_t* d_ids,
-                                   const int64_t* d_mask, int32_t ld, int32_t B, int32_t L, int32_t head, float* d_out,
-                                   float* d_logits, void* stream) {
-    return pnp_compute_gradcam_layer(e, d_images, d_dropped, d_ids, d_mask, ld, B, L, e ? e->SL : 0, head, d_out, d_logits, stream);
-}
-
-extern "C" int pnp_drop_step(pnp_engine* e, const float* d_gradcam, float* d_g0, float* d_agg, uint8_t* d_dropped,
-                             int32_t* d_picks, int32_t iter, int32_t B, int32_t T, int32_t npick, int32_t max_picks,
-                             void* stream) {
-    if (!e || !d_gradcam || !d_agg || !d_dropped || (npick > 0 && !d_picks)) return PNP_ERR_ARG;
-    if (T < 4) return fail(e, PNP_ERR_ARG, "T=%d too short", T);
-    KCHK(e, drop_step(d_gradcam, d_g0, d_agg, d_dropped, d_picks, iter, B, T, e->PP, npick, max_picks, (hipStream_t)stream));
-    return PNP_OK;
-}
-
-extern "C" int pnp_drop_loop(pnp_engine* e, const float* d_images, const int64_t* d_ids, const int64_t* d_mask, int32_t ld,
-                             int32_t B, int32_t L, int32_t head, int32_t drop_iter, int32_t npick, float* d_g0,
-                             float* d_agg, int32_t* d_picks, float* d_logits, void* stream) {
-    return pnp_drop_loop_layer(e, d_images, d_ids, d_mask, ld, B, L, e ? e->SL : 0, head, drop_iter, npick, d_g0, d_agg, d_picks,
-                               d_logits, stream);
-}
-
-extern "C" int pnp_drop_loop_layer(pnp_engine* e, const float* d_images, const int64_t* d_ids, const int64_t* d_mask, int32_t ld,
-                                   int32_t B, int32_t L, int32_t layer, int32_t head, int32_t drop_iter, int32_t npick, float* d_g0,
-                                   float* d_agg, int32_t* d_picks, float* d_logits, void* stream) {
-    if (!e || !d_images || !d_ids || !d_mask || !d_g0) return PNP_ERR_ARG;
-    if (drop_iter < 1) return fail(e, PNP_ERR_ARG, "drop_iter must be >= 1");
-    if (drop_iter == 1)   // PnP.py:565-575: single call, no aggregate
-        return pnp_compute_gradcam_layer(e, d_images, nullptr, d_ids, d_mask, ld, B, L, layer, head, d_g0, d_logits, stream);
-    if (!d_agg || !d_picks) return PNP_ERR_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(e, hipMemsetAsync(e->dropped, 0, (size_t)B * e->PP, s));
-    for (int it = 0; it < drop_iter; it++) {
-        // the token embeddings of iteration 0 serve the later iterations (same images, more patches zeroed)
-        int r = compute_gradcam_impl(e, d_images, e->dropped, d_ids, d_mask, ld, B, L, layer, head, e->G, d_logits, stream, it == 0 ? 1 : 2);
-        if (r) return r;
-        r = pnp_drop_step(e, e->G, d_g0, d_agg, e->dropped, d_picks, it, B, L - 1, npick, drop_iter * npick, stream);
-        if (r) return r;
-    }
-    return PNP_OK;
-}
-
 // =========================================================================================== introspection
 
 extern "C" int pnp_get_buffer(pnp_engine* e, const char* name, void** d_ptr, size_t* bytes) {
@@ -1145,239 +595,4 @@ extern "C" int pnp_profile_read(pnp_engine* e, int64_t* launches, double* flops,
     *flops = pf.flops;
     *ms = total;
     return PNP_OK;
-}
-
-extern "C" int pnp_op_gemm(int32_t bf, const void* d_A, int32_t lda, const void* d_B, int32_t ldb, int32_t M, int32_t N,
-                           int32_t K, const float* d_bias, const float* d_resid, int32_t ldr, float* d_out_f32, int32_t ldo,
-                           int32_t gelu, void* stream) {
-    GemmArgs g = G_(d_A, lda, d_B, ldb, M, N, K);
-    g.bias = d_bias; g.resid = d_resid; g.ldr = ldr; g.out_f32 = d_out_f32; g.ldo = ldo;
-    g.mode = gelu ? GEMM_EPI_GELU : GEMM_EPI_LINEAR;
-    return gemm_nt(bf, g, (hipStream_t)stream);
-}
-
-extern "C" int pnp_op_gemm_ex(int32_t bf, const void* d_A, int32_t lda, const void* d_B, int32_t ldb, int32_t M, int32_t N,
-                              int32_t K, const float* d_bias, const float* d_resid, int32_t ldr, float* d_out_f32, int32_t ldo,
-                              void* d_out_t, int32_t ldo_t, int32_t mode, void* stream) {
-    GemmArgs g = G_(d_A, lda, d_B, ldb, M, N, K);
-    g.bias = d_bias; g.resid = d_resid; g.ldr = ldr; g.out_f32 = d_out_f32; g.ldo = ldo; g.out_t = d_out_t; g.ldo_t = ldo_t;
-    g.mode = mode ? GEMM_EPI_GELU : GEMM_EPI_LINEAR;
-    return gemm_nt(bf, g, (hipStream_t)stream);
-}
-
-extern "C" int pnp_op_split(const float* d_in, void* d_hi, void* d_lo, int64_t n, void* stream) {
-    if (!d_in || !d_hi || !d_lo || n <= 0) return PNP_ERR_ARG;
-    return split_f32(d_in, d_hi, d_lo, (size_t)n, (hipStream_t)stream);
-}
-
-extern "C" int pnp_op_gemm_x3(const void* d_A_hi, const void* d_A_lo, int32_t lda, const void* d_B_hi, const void* d_B_lo,
-                              int32_t ldb, int32_t M, int32_t N, int32_t K, const float* d_bias, int32_t bias_on_rows,
-                              const float* d_resid, int32_t ldr, float* d_out_f32, int32_t ldo, void* d_out_hi, void* d_out_lo,
-                              int32_t ldo_t, int32_t gelu, int32_t col_div, int32_t col_pad, void* stream) {
-    if (!d_A_hi || !d_A_lo || !d_B_hi || !d_B_lo) return PNP_ERR_ARG;
-    GemmArgs g = G_(d_A_hi, lda, d_B_hi, ldb, M, N, K);
-    g.A_lo = d_A_lo; g.B_lo = d_B_lo;
-    g.bias = d_bias; g.bias_on_rows = bias_on_rows; g.resid = d_resid; g.ldr = ldr; g.out_f32 = d_out_f32; g.ldo = ldo;
-    g.out_t = d_out_hi; g.out_lo = d_out_lo; g.ldo_t = ldo_t; g.col_div = col_div; g.col_pad = col_pad;
-    g.mode = gelu ? GEMM_EPI_GELU : GEMM_EPI_LINEAR;
-    g.sk = streamk_mode() ? streamk_ws_default() : nullptr;     // op level: the per-device workspace (shared by all callers: the launcher serialises)
-    return gemm_nt(1, g, (hipStream_t)stream);
-}
-
-extern "C" int pnp_set_tuning(const char* key, int32_t value) {
-    if (!key) return PNP_ERR_ARG;
-    if (!strcmp(key, "streamk")) {
-        if (value < 0 || value > 2) return PNP_ERR_ARG;
-        set_streamk_mode(value);
-        return PNP_OK;
-    }
-    if (!strcmp(key, "text_rows")) {
-        if (value < 0 || value > 4) return PNP_ERR_ARG;
-        set_text_rows(value);
-        return PNP_OK;
-    }
-    if (!strcmp(key, "gemm_stamps")) {
-        if (value < 0 || value > 1) return PNP_ERR_ARG;
-        return gemm_set_stamps(value);
-    }
-    return PNP_ERR_ARG;
-}
-
-extern "C" int pnp_streamk_status(pnp_engine* e, int64_t* launches, uint32_t* gave_up) {
-    if (!launches || !gave_up) return PNP_ERR_ARG;
-    StreamKWs* ws = e ? &e->sk_ws : streamk_ws_default();
-    *launches = ws ? ws->launches : 0;
-    *gave_up = 0;
-    if (!ws || !ws->part) return PNP_OK;
-    if (e) HIPCHK(e, hipSetDevice(e->c.device));
-    if (hipDeviceSynchronize() != hipSuccess) return PNP_ERR_HIP;
-    return streamk_ws_timeouts(ws, gave_up);
-}
-
-extern "C" int pnp_op_gemm_x3a(const float* d_A, int32_t lda, const void* d_B_hi, const void* d_B_lo, int32_t ldb, int32_t M,
-                               int32_t N, int32_t K, const float* d_bias, const float* d_resid, int32_t ldr, float* d_out_f32,
-                               int32_t ldo, int32_t mode, float* d_aux, int32_t ld_aux, void* stream) {
-    if (!d_A || !d_B_hi || !d_B_lo || !d_out_f32 || mode < 0 || mode > 2) return PNP_ERR_ARG;
-    GemmArgs g = G_(d_A, lda, d_B_hi, ldb, M, N, K);
-    g.B_lo = d_B_lo; g.a_f32 = 1;
-    g.bias = d_bias; g.resid = d_resid; g.ldr = ldr; g.out_f32 = d_out_f32; g.ldo = ldo;
-    g.mode = mode; g.aux = d_aux; g.ld_aux = ld_aux;
-    return gemm_nt(0, g, (hipStream_t)stream);
-}
-
-extern "C" int pnp_op_gemm_tokcols(int32_t bf, const void* d_A, int32_t lda, const void* d_B, int32_t ldb, int32_t M, int32_t N,
-                                   int32_t K, const float* d_bias_rows, void* d_out_t, int32_t ldo_t, int32_t col_div,
-                                   int32_t col_pad, void* stream) {
-    if (!d_out_t || col_div < 0 || (col_div > 0 && col_pad < col_div)) return PNP_ERR_ARG;
-    GemmArgs g = G_(d_A, lda, d_B, ldb, M, N, K);
-    g.bias = d_bias_rows; g.bias_on_rows = 1; g.out_t = d_out_t; g.ldo_t = ldo_t; g.col_div = col_div; g.col_pad = col_pad;
-    return gemm_nt(bf, g, (hipStream_t)stream);
-}
-
-extern "C" int pnp_op_gemm_args(int32_t bf, const void* d_A, int32_t lda, const void* d_B, int32_t ldb, int32_t M, int32_t N,
-                                int32_t K, const float* d_bias, int32_t bias_on_rows, const float* d_resid, int32_t ldr,
-                                float* d_out_f32, int32_t ldo, void* d_out_t, int32_t ldo_t, int32_t mode, float* d_aux,
-                                int32_t ld_aux, int32_t row_div, int32_t col_div, int32_t col_pad, void* stream) {
-    if (!d_A || !d_B || (!d_out_f32 && !d_out_t) || M <= 0 || N <= 0 || K <= 0 || lda < K || ldb < K) return PNP_ERR_ARG;
-    if (mode < 0 || mode > 2 || (mode == GEMM_EPI_GELU_GRAD && !d_aux)) return PNP_ERR_ARG;
-    if (row_div < 0 || col_div < 0 || (col_div > 0 && col_pad < col_div)) return PNP_ERR_ARG;
-    GemmArgs g = G_(d_A, lda, d_B, ldb, M, N, K);
-    g.bias = d_bias; g.bias_on_rows = bias_on_rows ? 1 : 0; g.resid = d_resid; g.ldr = ldr;
-    g.out_f32 = d_out_f32; g.ldo = ldo; g.out_t = d_out_t; g.ldo_t = ldo_t;
-    g.mode = mode; g.aux = d_aux; g.ld_aux = ld_aux; g.row_div = row_div; g.col_div = col_div; g.col_pad = col_pad;
-    return gemm_nt(bf ? 1 : 0, g, (hipStream_t)stream);
-}
-
-extern "C" int pnp_op_vit_attention(int32_t bf, const void* d_qk, int32_t ld_qk, int32_t D, const void* d_vt, int32_t ld_vt,
-                                    int32_t n_pad, void* d_ctx, int32_t B, int32_t heads, int32_t N, float scale, void* stream) {
-    if (!d_qk || !d_vt || !d_ctx || B <= 0 || heads <= 0 || N <= 0) return PNP_ERR_ARG;
-    return vit_attention(bf, d_qk, ld_qk, D, d_vt, ld_vt, n_pad, d_ctx, B, heads, N, scale, (hipStream_t)stream);
-}
-
-extern "C" int pnp_op_vit_attention_x3(const void* d_qkv_hi, const void* d_qkv_lo, int32_t ld_qkv, int32_t D, void* d_ctx_hi,
-                                       void* d_ctx_lo, int32_t B, int32_t heads, int32_t N, float scale, void* stream) {
-    if (B <= 0 || heads <= 0 || N <= 0 || ld_qkv < 3 * D) return PNP_ERR_ARG;
-    return vit_attention_x3(d_qkv_hi, d_qkv_lo, ld_qkv, D, d_ctx_hi, d_ctx_lo, B, heads, N, scale, (hipStream_t)stream);
-}
-
-extern "C" int pnp_op_layernorm(const float* d_x, const float* d_w, const float* d_b, float eps, int32_t rows, int32_t D,
-                                float* d_y, void* stream) {
-    return layernorm(0, d_x, d_w, d_b, eps, rows, D, d_y, nullptr, nullptr, nullptr, (hipStream_t)stream);
-}
-
-extern "C" int pnp_op_xattn(int32_t bf16, int32_t mode, const void* d_nat, int32_t ld_nat, const void* d_tr, int32_t ld_tr,
-                            int32_t n_pad, const void* d_x, int32_t ldx, void* d_out, int32_t ldo, float* d_probs,
-                            int32_t n_stride, int32_t B, int32_t L, int32_t N, int32_t heads, void* stream) {
-    if (!d_nat || !d_x || !d_probs || mode < 0 || mode > 2 || (mode != 2 && (!d_tr || !d_out))) return PNP_ERR_ARG;
-    if (B <= 0 || L <= 0 || N <= 0 || heads <= 0) return PNP_ERR_ARG;
-    return xattn(bf16, mode, d_nat, ld_nat, d_tr, ld_tr, n_pad, d_x, ldx, d_out, ldo, d_probs, n_stride, B, L, N, heads,
-                 (hipStream_t)stream);
-}
-
-extern "C" int pnp_op_text_self_attn(int32_t bf16, const void* d_qkv, const int64_t* d_mask, int32_t ld_mask, void* d_ctx,
-                                     float* d_probs, float* d_scratch, int32_t B, int32_t L, int32_t H, void* stream) {
-    if (!d_qkv || !d_mask || !d_ctx || B <= 0 || L <= 0 || H <= 0 || ld_mask < L) return PNP_ERR_ARG;
-    return text_self_attn(bf16, d_qkv, d_mask, ld_mask, d_ctx, d_probs, d_scratch, B, L, H, (hipStream_t)stream);
-}
-
-extern "C" int pnp_op_text_self_attn_bwd(int32_t bf16, const void* d_qkv, const float* d_dctx, const float* d_probs,
-                                         float* d_ds_scratch, void* d_dqkv, int32_t B, int32_t L, int32_t H, void* stream) {
-    if (!d_qkv || !d_dctx || !d_probs || !d_ds_scratch || !d_dqkv || B <= 0 || L <= 0 || H <= 0) return PNP_ERR_ARG;
-    return text_self_attn_bwd(bf16, d_qkv, d_dctx, d_probs, d_ds_scratch, d_dqkv, B, L, H, (hipStream_t)stream);
-}
-
-extern "C" int pnp_op_layernorm_ex(int32_t bf16, const float* d_x, const float* d_w, const float* d_b, float eps, int32_t rows,
-                                   int32_t D, float* d_y, void* d_yt, void* d_yt_lo, float* d_xhat, float* d_rstd, void* stream) {
-    if (!d_x || !d_w || !d_b || rows <= 0 || D <= 0 || (d_yt_lo && !d_yt)) return PNP_ERR_ARG;
-    return layernorm(bf16, d_x, d_w, d_b, eps, rows, D, d_y, d_yt, d_xhat, d_rstd, (hipStream_t)stream, d_yt_lo);
-}
-
-extern "C" int pnp_op_layernorm_bwd(int32_t bf16, const float* d_dy, const float* d_w, const float* d_xhat, const float* d_rstd,
-                                    int32_t rows, int32_t D, float* d_dx, void* d_dxt, void* stream) {
-    if (!d_dy || !d_w || !d_xhat || !d_rstd || rows <= 0 || D <= 0) return PNP_ERR_ARG;
-    return layernorm_bwd(bf16, d_dy, d_w, d_xhat, d_rstd, rows, D, d_dx, d_dxt, (hipStream_t)stream);
-}
-
-extern "C" int pnp_op_text_embed(const int64_t* d_ids, int32_t ld_ids, const float* d_word, const float* d_pos, float* d_out,
-                                 int32_t B, int32_t L, int32_t H, int32_t enc_id, int32_t vocab, void* stream) {
-    if (!d_ids || !d_word || !d_pos || !d_out || B <= 0 || L <= 0 || H <= 0 || H % 4 || vocab <= 0 || ld_ids < L || enc_id >= vocab)
-        return PNP_ERR_ARG;
-    return text_embed(d_ids, ld_ids, d_word, d_pos, d_out, B, L, H, enc_id, vocab, (hipStream_t)stream);
-}
-
-extern "C" int pnp_op_itm_head(const float* d_hlast, const float* d_w, const float* d_bias, float* d_logits, int32_t B, int32_t L,
-                               int32_t H, void* stream) {
-    if (!d_hlast || !d_w || !d_bias || !d_logits || B <= 0 || L <= 0 || H <= 0) return PNP_ERR_ARG;
-    return itm_head(d_hlast, d_w, d_bias, d_logits, B, L, H, (hipStream_t)stream);
-}
-
-extern "C" int pnp_op_itm_grad_seed(const float* d_w, float* d_dh, int32_t B, int32_t L, int32_t H, void* stream) {
-    if (!d_w || !d_dh || B <= 0 || L <= 0 || H <= 0) return PNP_ERR_ARG;
-    return itm_grad_seed(d_w, d_dh, B, L, H, (hipStream_t)stream);
-}
-
-extern "C" int pnp_op_patchify(int32_t bf16, const float* d_img, const uint8_t* d_dropped, void* d_out, int32_t B, int32_t S,
-                               int32_t P, void* stream) {
-    if (!d_img || !d_out || B <= 0 || P <= 0 || S != P * 16) return PNP_ERR_ARG;
-    return patchify(bf16, d_img, d_dropped, d_out, B, S, P, (hipStream_t)stream);
-}
-
-extern "C" int pnp_op_cls_rows(const float* d_cls, const float* d_pos, float* d_x, int32_t B, int32_t N, int32_t D, void* stream) {
-    if (!d_cls || !d_pos || !d_x || B <= 0 || N <= 0 || D <= 0) return PNP_ERR_ARG;
-    return cls_rows(d_cls, d_pos, d_x, B, N, D, (hipStream_t)stream);
-}
-
-extern "C" int pnp_dbg_gemm_stamps(uint64_t* host_out, int32_t max_blocks) {
-    return gemm_read_stamps((unsigned long long*)host_out, max_blocks);
-}
-
-extern "C" int pnp_preprocess_images(const uint8_t* d_rgb, const pnp_pre_image* d_desc, int32_t B, int32_t S, int32_t max_H,
-                                     const int32_t* d_coef, uint8_t* d_tmp, const float* mean3, const float* std3,
-                                     float* d_out, void* stream) {
-    if (!d_rgb || !d_desc || !d_coef || !d_tmp || !mean3 || !std3 || !d_out) return PNP_ERR_ARG;
-    static_assert(sizeof(pnp_pre_image) == 40, "pnp_pre_image layout is part of the ABI");
-    return preprocess_images(d_rgb, d_desc, B, S, max_H, d_coef, d_tmp, mean3, std3, d_out, (hipStream_t)stream);
-}
-
-extern "C" int pnp_jpeg_decode(const uint8_t* d_data, const pnp_jpeg_image* d_images, const pnp_jpeg_tables* d_tables,
-                               const pnp_jpeg_segment* d_segments, int32_t n_images, int32_t n_segments, uint8_t* d_clean,
-                               int32_t* d_seg_bits, int16_t* d_coef, int64_t coef_elems, uint8_t* d_planes, uint8_t* d_rgb,
-                               int32_t max_blocks_per_image, int32_t max_pixels_per_image, int32_t* d_err, void* stream) {
-    if (!d_data || !d_images || !d_tables || !d_segments || !d_clean || !d_seg_bits || !d_coef || !d_planes || !d_rgb || !d_err ||
-        coef_elems <= 0)
-        return PNP_ERR_ARG;
-    static_assert(sizeof(pnp_jpeg_image) == sizeof(JpegImage) && sizeof(pnp_jpeg_tables) == sizeof(JpegTables) &&
-                      sizeof(pnp_jpeg_segment) == sizeof(JpegSegment), "JPEG descriptor layouts are part of the ABI");
-    return jpeg_decode(d_data, reinterpret_cast<const JpegImage*>(d_images), reinterpret_cast<const JpegTables*>(d_tables),
-                       reinterpret_cast<const JpegSegment*>(d_segments), n_images, n_segments, d_clean, d_seg_bits, d_coef,
-                       (size_t)coef_elems, d_planes, d_rgb, max_blocks_per_image, max_pixels_per_image, d_err, (hipStream_t)stream);
-}
-
-// operator forms of the lattice build's sort / scan (tests); the scratch is allocated per call
-extern "C" int pnp_op_sort_pairs(uint64_t* d_keys_in, uint64_t* d_keys_out, uint32_t* d_vals_in, uint32_t* d_vals_out, int64_t n,
-                                 int32_t begin_bit, int32_t end_bit, const size_t* h_seg_off, int32_t n_seg, void* stream) {
-    if (n < 0 || (n && (!d_keys_in || !d_keys_out || !d_vals_in || !d_vals_out))) return PNP_ERR_ARG;
-    if (!n) return PNP_OK;
-    const size_t tb = sort_temp_bytes((size_t)n);
-    void* temp = nullptr;
-    if (hipMalloc(&temp, tb) != hipSuccess) return PNP_ERR_NOMEM;
-    int r = radix_sort_pairs(d_keys_in, d_keys_out, d_vals_in, d_vals_out, (size_t)n, begin_bit, end_bit, h_seg_off, n_seg, temp, tb, (hipStream_t)stream);
-    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess && r == PNP_OK) r = PNP_ERR_HIP;
-    (void)hipFree(temp);
-    return r;
-}
-extern "C" int pnp_op_scan_i32(const int32_t* d_in, int32_t* d_out, int64_t n, int32_t inclusive, void* stream) {
-    if (n < 0 || (n && (!d_in || !d_out))) return PNP_ERR_ARG;
-    if (!n) return PNP_OK;
-    const size_t tb = sort_temp_bytes((size_t)n);
-    void* temp = nullptr;
-    if (hipMalloc(&temp, tb) != hipSuccess) return PNP_ERR_NOMEM;
-    int r = device_scan_i32(d_in, d_out, (size_t)n, inclusive != 0, temp, tb, (hipStream_t)stream);
-    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess && r == PNP_OK) r = PNP_ERR_HIP;
-    (void)hipFree(temp);
-    return r;
-}
-
-extern "C" int pnp_op_cast(int32_t to_bf16, const float* d_in, void* d_out, int64_t n, void* stream) {
-    return cast_f32(to_bf16, d_in, d_out, (size_t)n, (hipStream_t)stream);
 }

@@ -647,7 +647,7 @@ def _wide_bf16_case(kind, M, N, K, tok=None):
 # ragged last row tile (15 470 = 60 x 256 + 110) and K = 1024 / 4096 with the epilogue each launch uses in the engine.
 BENCH_M = 35 * 442
 BENCH_LAUNCHES = [
-    # (form, epilogue, M, N, K, token-column geometry)          engine.hip launch it mirrors
+    # (form, epilogue, M, N, K, token-column geometry)          model.hip launch it mirrors
     ("x3", "plain_split", BENCH_M, 3072, 1024, None),          # qkv            -> (hi, lo) pair          EPI 7
     ("x3", "gelu_split", BENCH_M, 4096, 1024, None),           # fc1 + GELU     -> (hi, lo) pair          EPI 6
     ("x3", "resid_f32", BENCH_M, 1024, 4096, None),            # fc2 + residual -> fp32 in place          EPI 2
@@ -1508,7 +1508,7 @@ def test_bf16_vs_f32_divergence_is_bounded():
 @pytest.mark.parametrize("mode", ["f32", "bf16", "bf16x3"])
 def test_drop_loop_embedding_reuse_is_bit_identical(mode):
     """pnp_drop_loop keeps the token embeddings of iteration 0 and, in the later iterations, replaces only the rows of dropped
-    patches by bias + pos (engine.hip: embed_reuse_kernel) instead of re-running patchify + the patch GEMM on the re-zeroed images
+    patches by bias + pos (model.hip: embed_reuse_kernel) instead of re-running patchify + the patch GEMM on the re-zeroed images
     (PnP.py:597-603).  Against a hand-written loop of the operator-level calls, which compute the embeddings from the images
     every time: gradcam_0, the aggregate, the picks and the logits are bit-identical."""
     g = _golden("droploop_small.npz")
