@@ -284,6 +284,50 @@ int pnp_crf_read(pnp_crf* c, float* d_q, uint8_t* d_labels, void* stream);
  * launch grid.  Synchronises.  This is densecrf's klDivergence as this project reads it (up to the constant densecrf leaves
  * out as well); like the rest of the CRF it is pinned by nothing the reference holds (oracle/README.md). */
 int pnp_crf_kl(pnp_crf* c, float pos_w, float bi_w, double* h_out_per_image, void* stream);
+/* ---- any number of pairwise terms over features the caller brings (pydensecrf's addPairwiseEnergy) ----
+ * T = 1 .. max_terms terms; term t has d_t = 1 .. max_dims float32 features per pixel, ALREADY DIVIDED by their kernel widths
+ * and used as given, and a compatibility of its own (scalar weight, vector or matrix: message weights as pnp_crf_set_compat
+ * documents them).  Per term: the permutohedral embedding of pnp_crf_set_batch on f[i] = F_t[i][pixel]; msg_t = norm_t *
+ * lattice_t(norm_t * Q) with norm_t = 1 / sqrt(lattice_t(1) + 1e-20) (sequential splat in pixel order, d_t + 1 axis blurs,
+ * slice with alpha = 1 / (1 + 2^-d_t)); acc_t[l] = sum_k M_t[l][k] msg_t[k] (one fp32 accumulator, k ascending; a scalar:
+ * w_t * msg_t[l]).  Update: logit = ((-U + acc_0) + acc_1) + ... + acc_{T-1} in term order, Q = softmax(logit).  With T = 2,
+ * F_0 = (x / sx, y / sy), F_1 = (x / sx, y / sy, r / sr, g / sg, b / sb) this is pnp_crf_infer's arithmetic bit for bit.
+ * DIAG_KERNEL and NORMALIZE_SYMMETRIC only.
+ *
+ * pnp_crf_create_terms: pnp_crf_create for max_terms <= 8 terms of max_dims <= 6 feature axes.  D = 1 .. 6 and worst-case
+ * sizing are the contract: every term gets a lattice for max_dims + 1 points per pixel (what a noisy feature can reach: 5.2 -
+ * 5.5 at D = 6), and one pair of value buffers of that many rows per pixel serves all terms in turn;
+ * pnp_crf_allocated_bytes reports the total, and a failed allocation leaves a handle whose pnp_crf_last_error says how many
+ * bytes were wanted.  The solver serves pnp_crf_set_batch* / pnp_crf_infer as one of pnp_crf_create does.
+ *
+ * pnp_crf_set_batch_terms: batch->d_rgb is not read.  terms[t].d_features (device) holds the (dims, H_b * W_b) blocks of the
+ * images back to back, as d_unary holds the (K_b, H_b * W_b) blocks; it is read during this call only.  Builds every lattice
+ * and normaliser; synchronises once per lattice.  The lattice key holds min(16, 64 / dims) bits per coordinate (no image
+ * bits): |coordinate| < 505 at dims = 6, < 2042 at dims = 5, < 32000 below.  A coordinate beyond it, or a feature that is not
+ * finite, is PNP_ERR_ARG: the message names the term and the limit, and a wider kernel width is the remedy.  After a failed
+ * call the solver holds no batch.
+ *
+ * pnp_crf_set_term_compat: pnp_crf_set_compat for term < max_terms of the feature path (pnp_crf_set_compat itself keeps to
+ * the Gaussian / bilateral terms 0 and 1 of the two-term path; the two sets of compatibilities are separate).
+ * pnp_crf_infer_terms / pnp_crf_step_terms: pnp_crf_infer / pnp_crf_step with weights[T] (host), the weight of every term left
+ * scalar.  pnp_crf_start and pnp_crf_read serve both kinds of batch; start + step_terms(a) + step_terms(b) leaves the Q of
+ * infer_terms(a + b) bit for bit.  The two-term calls on a terms batch and the terms calls on a two-term batch return
+ * PNP_ERR_STATE; pnp_crf_kl on a terms batch returns PNP_ERR_ARG (not available).  Null pointers and counts out of range are
+ * refused before any HIP call. */
+enum { PNP_CRF_MAX_TERMS = 8, PNP_CRF_MAX_DIMS = 6 };
+typedef struct pnp_crf_term {
+    int32_t dims;                /* feature axes of the term, 1..max_dims */
+    const float* d_features;     /* device: concatenated (dims, H_b * W_b) blocks */
+} pnp_crf_term;
+int pnp_crf_create_terms(int32_t device, int32_t max_batch, int64_t max_total_pixels, int32_t max_pixels_per_image, int32_t max_labels,
+                         int32_t max_terms, int32_t max_dims, pnp_crf** out);
+int pnp_crf_set_batch_terms(pnp_crf* c, const pnp_crf_batch* batch, int32_t n_terms, const pnp_crf_term* terms, void* stream);
+int pnp_crf_set_term_compat(pnp_crf* c, int32_t term, int32_t kind, const float* host_values, int32_t K);
+int pnp_crf_infer_terms(pnp_crf* c, int32_t iters, const float* weights, float* d_q, uint8_t* d_labels, void* stream);
+int pnp_crf_step_terms(pnp_crf* c, int32_t n, const float* weights, void* stream);
+/* Lattice points of one term over the whole batch, as the last successful set_batch built it: term < T of a terms batch; 0
+ * (Gaussian) or 1 (bilateral) of a two-term batch.  -1 for a null solver, no batch, or no such term. */
+int64_t pnp_crf_lattice_points(const pnp_crf* c, int32_t term);
 
 /* ---- input side ("next" row: the tensors the reference's datasets hand to the model) -------
  * Dataset.py:434-443: transforms.Resize((S, S), BICUBIC) on the PIL image -> ToTensor -> Normalize(mean, std).

@@ -45,18 +45,23 @@ template <> struct KeyPack<5> { static constexpr int BITS = 11; };
 // search compares whole keys).  5 x 11 + 6 bits <= 61: at most 64 images per prepared batch.
 constexpr int IMG_SHIFT = 55;
 constexpr int IMG_BITS = 6;
+// Keys of the feature path (lattice_embed_features_kernel, D = 1 .. 6 caller-supplied axes): WITHOUT image bits -- mark_heads
+// takes the image boundaries from the descriptors and the neighbour search stays inside idbase[b] .. idbase[b + 1], so all 64
+// bits are coordinates: 16, 16, 16, 16, 12, 10 per coordinate (D = 6: |coordinate| < 2^9 - 7 = 505; the 9 bits that 55 / 6
+// leave reach 249, too few for xy / 50, rgb / 5 and one more channel on a 375 x 500 image)
+template <int D> struct FeatKey { static constexpr int BITS = 64 / D < 16 ? 64 / D : 16; };
+// |elevated coordinate| the feature path accepts whatever the key holds: rem0 and the keys pass through int16 as in densecrf
+constexpr float CRF_FEAT_ELEV_LIMIT = 32000.f;
 
-template <int D>
+template <int D, int BITS = KeyPack<D>::BITS>
 __device__ __forceinline__ uint64_t pack_key(const int* c) {
-    constexpr int BITS = KeyPack<D>::BITS;
     uint64_t k = 0;
 #pragma unroll
     for (int i = 0; i < D; i++) k = (k << BITS) | (uint64_t)((c[i] + (1 << (BITS - 1))) & ((1 << BITS) - 1));
     return k;
 }
-template <int D>
+template <int D, int BITS = KeyPack<D>::BITS>
 __device__ __forceinline__ void unpack_key(uint64_t k, int* c) {
-    constexpr int BITS = KeyPack<D>::BITS;
 #pragma unroll
     for (int i = D - 1; i >= 0; i--) {
         c[i] = (int)(k & ((1 << BITS) - 1)) - (1 << (BITS - 1));      // image bits above D*BITS are ignored
@@ -172,6 +177,114 @@ __global__ void lattice_embed_kernel(const PostDesc* __restrict__ imgs, const ui
     }
 }
 
+// The same embedding on D = 1 .. 6 features the caller brings (pnp_crf_set_batch_terms): image b's block of `feat` is D planes of
+// H * W floats at float offset pix0 * D, already divided by their widths, so a wave reads 256 consecutive bytes of every plane.
+// From `elevated` on these are lattice_embed_kernel's statements (tests: xy and xy+rgb features give its lattices bit for bit)
+// with the feature path's key (FeatKey: no image bits) and one more reason to raise the range flag: a non-finite feature, or
+// an elevated coordinate beyond CRF_FEAT_ELEV_LIMIT, where rem0 and the keys would wrap in their int16 casts and could land
+// back inside the key's range.  (The statements are repeated, not shared through a function: with the body factored out
+// lattice_embed_kernel compiled to other instructions, and the two-term path keeps the ones it had.)
+template <int D>
+__global__ void lattice_embed_features_kernel(const PostDesc* __restrict__ imgs, const float* __restrict__ feat, float* __restrict__ bary,
+                                              uint64_t* __restrict__ keys, uint32_t* __restrict__ vals, int* __restrict__ range_err) {
+    constexpr int BITS = FeatKey<D>::BITS;
+    const int b = blockIdx.y;
+    const PostDesc im = imgs[b];
+    const int n = im.H * im.W;
+    const float* const fb = feat + (size_t)im.pix0 * D;
+    float scale_factor[D];
+    {
+        const float inv_std_dev = (float)(sqrt(2.0 / 3.0) * (D + 1));
+#pragma unroll
+        for (int i = 0; i < D; i++) scale_factor[i] = (float)(1.0 / sqrt((double)((i + 2) * (i + 1))) * inv_std_dev);
+    }
+    for (int pix = blockIdx.x * blockDim.x + threadIdx.x; pix < n; pix += gridDim.x * blockDim.x) {
+        float f[D];
+#pragma unroll
+        for (int i = 0; i < D; i++) f[i] = ld_stream(fb + (size_t)i * n + pix);
+        const size_t e0 = (size_t)(im.pix0 + pix) * (D + 1);
+        float elevated[D + 1], rem0[D + 1], barycentric[D + 2];
+        int rank[D + 1];
+        float sm = 0.f;
+#pragma unroll
+        for (int j = D; j > 0; j--) {
+            const float cf = __fmul_rn(f[j - 1], scale_factor[j - 1]);
+            elevated[j] = __fsub_rn(sm, __fmul_rn((float)j, cf));
+            sm = __fadd_rn(sm, cf);
+        }
+        elevated[0] = sm;
+        const float down_factor = 1.0f / (D + 1);
+        const float up_factor = (float)(D + 1);
+        int sum = 0;
+#pragma unroll
+        for (int i = 0; i <= D; i++) {
+            const float v = __fmul_rn(down_factor, elevated[i]);
+            const float up = __fmul_rn(ceilf(v), up_factor);
+            const float down = __fmul_rn(floorf(v), up_factor);
+            int rd2;
+            if (__fsub_rn(up, elevated[i]) < __fsub_rn(elevated[i], down)) rd2 = (int)(short)up;
+            else rd2 = (int)(short)down;
+            rem0[i] = (float)rd2;
+            sum = (int)__fadd_rn((float)sum, __fmul_rn((float)rd2, down_factor));
+        }
+#pragma unroll
+        for (int i = 0; i <= D; i++) rank[i] = 0;
+#pragma unroll
+        for (int i = 0; i < D; i++) {
+            const double di = (double)__fsub_rn(elevated[i], rem0[i]);
+#pragma unroll
+            for (int j = i + 1; j <= D; j++) {
+                if (di < (double)__fsub_rn(elevated[j], rem0[j])) rank[i]++;
+                else rank[j]++;
+            }
+        }
+#pragma unroll
+        for (int i = 0; i <= D; i++) {
+            rank[i] += sum;
+            if (rank[i] < 0) {
+                rank[i] += D + 1;
+                rem0[i] = __fadd_rn(rem0[i], (float)(D + 1));
+            } else if (rank[i] > D) {
+                rank[i] -= D + 1;
+                rem0[i] = __fsub_rn(rem0[i], (float)(D + 1));
+            }
+        }
+#pragma unroll
+        for (int i = 0; i <= D + 1; i++) barycentric[i] = 0.f;
+#pragma unroll
+        for (int i = 0; i <= D; i++) {
+            const float v = __fmul_rn(__fsub_rn(elevated[i], rem0[i]), down_factor);
+            // barycentric[D - rank[i]] += v ; barycentric[D - rank[i] + 1] -= v   (static indexing)
+#pragma unroll
+            for (int s = 0; s <= D + 1; s++) {
+                if (s == D - rank[i]) barycentric[s] = __fadd_rn(barycentric[s], v);
+                if (s == D - rank[i] + 1) barycentric[s] = __fsub_rn(barycentric[s], v);
+            }
+        }
+        barycentric[0] = __fadd_rn(barycentric[0], __fadd_rn(1.0f, barycentric[D + 1]));
+
+        bool wild = false;                                  // beyond what the int16 casts below hold, or not finite
+        #pragma unroll
+        for (int i = 0; i <= D; i++) wild |= !(fabsf(elevated[i]) < CRF_FEAT_ELEV_LIMIT);          // (a NaN compares false)
+#pragma unroll
+        for (int rem = 0; rem <= D; rem++) {
+            int key[D];
+            bool bad = wild;
+#pragma unroll
+            for (int i = 0; i < D; i++) {
+                // canonical[rem][rank[i]] = rem if rank[i] <= D - rem else rem - (D+1)
+                const int canon = (rank[i] <= D - rem) ? rem : rem - (D + 1);
+                key[i] = (int)(short)(rem0[i] + (float)canon);
+                bad |= (key[i] <= -(1 << (BITS - 1)) + D + 1) || (key[i] >= (1 << (BITS - 1)) - D - 1);
+            }
+            if (bad) atomicExch(range_err, 1);
+            keys[e0 + rem] = pack_key<D, BITS>(key);
+            vals[e0 + rem] = (uint32_t)(e0 + rem);
+            bary[e0 + rem] = barycentric[rem];
+        }
+    }
+}
+
 // head[i] = 1 where sorted entry i starts a new lattice point (first entry of the image or new key)
 __global__ void mark_heads_kernel(const uint64_t* __restrict__ keys, const PostDesc* __restrict__ imgs, int D1,
                                   int* __restrict__ head) {
@@ -228,11 +341,12 @@ __device__ __forceinline__ int lower_bound_from(const uint64_t* __restrict__ uke
     }
     return l;
 }
-template <int D>
+// IMG: the keys carry the image index above their coordinates (the xy / xy+rgb path; the feature path's do not)
+template <int D, int BITS = KeyPack<D>::BITS, bool IMG = true>
 __global__ void neighbors_kernel(const uint64_t* __restrict__ ukeys, const int* __restrict__ idbase, size_t cap,
                                  int* __restrict__ n1, int* __restrict__ n2) {
-    constexpr int BITS = KeyPack<D>::BITS;
     const int b = blockIdx.y;
+    const uint64_t image = IMG ? (uint64_t)b << IMG_SHIFT : 0;
     const int lo = idbase[b], hi = idbase[b + 1];
     const int nruns = (hi - lo + kNbrRun - 1) / kNbrRun;
     for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < nruns * (D + 1); t += gridDim.x * blockDim.x) {
@@ -242,7 +356,7 @@ __global__ void neighbors_kernel(const uint64_t* __restrict__ ukeys, const int* 
         bool first1 = true, first2 = true;
         for (int id = id0; id < id1; id++) {
             int c[D], a[D], d2[D];
-            unpack_key<D>(ukeys[id], c);
+            unpack_key<D, BITS>(ukeys[id], c);
 #pragma unroll
             for (int k = 0; k < D; k++) {
                 a[k] = c[k] - 1;
@@ -262,7 +376,7 @@ __global__ void neighbors_kernel(const uint64_t* __restrict__ ukeys, const int* 
                 in2 &= (d2[k] >= -(1 << (BITS - 1)) && d2[k] < (1 << (BITS - 1)));
             }
             if (in1) {
-                const uint64_t k1 = pack_key<D>(a) | ((uint64_t)b << IMG_SHIFT);
+                const uint64_t k1 = pack_key<D, BITS>(a) | image;
                 int l;
                 if (first1) {                                   // binary search inside this image's sorted unique keys [lo, hi)
                     int ll = lo, h = hi;
@@ -280,7 +394,7 @@ __global__ void neighbors_kernel(const uint64_t* __restrict__ ukeys, const int* 
                 if (l < hi && ukeys[l] == k1) r1 = l;
             }
             if (in2) {
-                const uint64_t k2 = pack_key<D>(d2) | ((uint64_t)b << IMG_SHIFT);
+                const uint64_t k2 = pack_key<D, BITS>(d2) | image;
                 int l;
                 if (first2) {
                     int ll = lo, h = hi;
@@ -1175,6 +1289,219 @@ __global__ __launch_bounds__(256) void crf_update_compat_kernel(const CrfLattice
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// One pairwise term of a T-term update over caller-supplied features (pnp_crf_set_batch_terms; the two-term runs above never come
+// here): slice the term's blurred lattice (D1 = d + 1 = 2 .. 7 vertices per pixel), weigh the message, add it into the
+// pixel-major logit row, and after the last term take the softmax:
+//   msg[k]   = (sum_v (bary_v * val_v[k]) * alpha) * norm        v ascending: crf_update_kernel's sequence per term
+//   acc[l]   = w * msg[l] | wvec[l] * msg[l] | sum_k M[l][k] * msg[k]      (one fp32 accumulator, k ascending, no FMA)
+//   row[l]   = (first ? -U[l] : row[l]) + acc[l]
+//   last:  Q = softmax(row), labels, zero pad -- crf_update_compat_kernel's arithmetic element by element
+// so T = 2 with xy and xy+rgb features leaves the bits of crf_update_kernel (scalars) / crf_update_compat_kernel (matrices).
+// Built like crf_update_compat_kernel: TW x TH pixel tiles, XCD-affine image schedule, slice records (2 D1 + 1 words per pixel)
+// staged in LDS by one thread per pixel, 16-byte row gathers with lanes over (pixel, chunk) items.  `base` and `out` may be the
+// same array (the logit rows, updated in place: an item reads its chunk before it writes it, and a tile's rows are only its
+// own).  What a launch keeps in LDS besides the records: nothing (scalar / vector weights, not last: rows go from registers
+// straight to memory), the logit tile (last: the softmax needs whole rows), or tile + message rows (MATRIX: phase 2 with
+// lane = pixel and the transposed matrix through scalar loads, as there).  imgs: the TERM's descriptors (voff[0] = its value rows).
+// Per-thread arrays are indexed by unrolled loops over the template's D1 only.
+template <int D1, bool MATRIX>
+__global__ __launch_bounds__(256) void crf_term_update_kernel(const CrfLattice L, const PostDesc* __restrict__ imgs, const float* __restrict__ val,
+                                                              const float* __restrict__ norm, const float* base, int first, float* out, int last,
+                                                              float w, const float* __restrict__ wvec, const float* __restrict__ MT, int ldm,
+                                                              float alpha, int img0, int nimg, int TP, const CrfLabelOut lout) {
+    extern __shared__ __attribute__((aligned(16))) float tile[];        // [TP][Kp + 1] x (0 | 1 | 2), then the slice records
+    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, bpx = gridDim.x >> 3;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const bool tiled = MATRIX || last;
+    const int TW = crf_tile_w(TP), TH = TP / TW;                        // TP = 32 .. 256, a power of two
+    const int tw_shift = __ffs(TW) - 1;
+    // phase 2 and the softmax: WPS waves cover the pixels of a tile, NG = 4 / WPS waves share a pixel set
+    const int WPS = TP > 64 ? TP >> 6 : 1, NG = 4 / WPS;
+    const int px2 = (wave % WPS) * 64 + lane, lg = wave / WPS;
+    const bool act = px2 < TP;
+    const int pxc = act ? px2 : TP - 1;
+    int b, part, parts;
+    for (int wi = 0; xcd_work(wi, xcd, img0, nimg, b, part, parts); wi++) {
+        const PostDesc im = imgs[b];
+        const int K = im.K, Kp = im.Kp, K4 = Kp >> 2, ldt = Kp + 1;
+        const int lo = L.idbase[b];
+        const int tiles_x = (im.W + TW - 1) / TW, tiles_y = (im.H + TH - 1) / TH, ntiles = tiles_x * tiles_y;
+        const int tfirst = (int)((long)ntiles * part / parts), tend = (int)((long)ntiles * (part + 1) / parts);
+        const char* const Bb = reinterpret_cast<const char*>(base + im.qoff);
+        const char* const Vb = reinterpret_cast<const char*>(val + im.voff[0]);
+        f32x4* const O4 = reinterpret_cast<f32x4*>(out + im.qoff);
+        const uint32_t rowb = (uint32_t)K4 * 16u;
+        float* const msg = tile + TP * ldt;                                            // (MATRIX only)
+        int* const rec_o = reinterpret_cast<int*>(tile + ((tiled ? 1 : 0) + (MATRIX ? 1 : 0)) * TP * ldt);   // [TP][D1] lattice ids
+        float* const rec_w = reinterpret_cast<float*>(rec_o + TP * D1);                // [TP][D1] barycentric weights
+        float* const rec_n = rec_w + TP * D1;                                          // [TP] normaliser; then row maximum / sum
+        const int q256 = 256 / K4, r256 = 256 - q256 * K4;
+        const int pl0 = tid / K4, c0 = tid - pl0 * K4;
+        for (int tl = tfirst + slot; tl < tend; tl += bpx) {
+            const int ty = tl / tiles_x, tx = tl - ty * tiles_x;
+            const int x0 = tx * TW, y0 = ty * TH;
+            // slots of an edge tile that fall outside the image redo its last column / row and store nothing
+            auto pixel_of = [&](int pl) {
+                const int x = x0 + (pl & (TW - 1)), y = y0 + (pl >> tw_shift);
+                return (y < im.H ? y : im.H - 1) * im.W + (x < im.W ? x : im.W - 1);
+            };
+            auto inside = [&](int pl) { return x0 + (pl & (TW - 1)) < im.W && y0 + (pl >> tw_shift) < im.H; };
+            for (int pl = tid; pl < TP; pl += 256) {                     // slice records, one pixel per thread
+                const size_t g = (size_t)im.pix0 + pixel_of(pl);
+#pragma unroll
+                for (int v = 0; v < D1; v++) {
+                    rec_o[pl * D1 + v] = L.offset[g * D1 + v] - lo;
+                    rec_w[pl * D1 + v] = L.bary[g * D1 + v];
+                }
+                rec_n[pl] = norm[g];
+            }
+            __syncthreads();
+            {   // phase 1: the message chunk of every (pixel, chunk) item; without a matrix also its weight and the row's sum
+                int pl = pl0, c = c0;
+                for (int item = tid; item < TP * K4; item += 256) {
+                    const int px = pixel_of(pl);
+                    const uint32_t cofs = (uint32_t)c * 16u;
+                    f32x4 t = *reinterpret_cast<const f32x4*>(Bb + (__umul24((uint32_t)px, rowb) + cofs));
+                    if (first) t = f32x4{-t[0], -t[1], -t[2], -t[3]};
+                    f32x4 vv[D1];
+#pragma unroll
+                    for (int v = 0; v < D1; v++)
+                        vv[v] = *reinterpret_cast<const f32x4*>(Vb + (__umul24((uint32_t)rec_o[pl * D1 + v], rowb) + cofs));
+                    f32x4 o = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                    for (int v = 0; v < D1; v++) {
+                        const float wv = rec_w[pl * D1 + v];
+#pragma unroll
+                        for (int i = 0; i < 4; i++) o[i] = __fadd_rn(o[i], __fmul_rn(__fmul_rn(wv, vv[v][i]), alpha));
+                    }
+                    const float nr = rec_n[pl];
+                    f32x4 m;
+#pragma unroll
+                    for (int i = 0; i < 4; i++) m[i] = __fmul_rn(o[i], nr);
+                    if (!MATRIX) {
+                        f32x4 wl = {w, w, w, w};
+                        if (wvec) wl = *reinterpret_cast<const f32x4*>(wvec + 4 * c);
+#pragma unroll
+                        for (int i = 0; i < 4; i++) t[i] = __fadd_rn(t[i], __fmul_rn(wl[i], m[i]));
+                    }
+                    if (tiled) {
+#pragma unroll
+                        for (int i = 0; i < 4; i++) {
+                            tile[pl * ldt + 4 * c + i] = t[i];
+                            if (MATRIX) msg[pl * ldt + 4 * c + i] = m[i];
+                        }
+                    } else if (inside(pl)) {
+                        O4[(size_t)px * K4 + c] = t;
+                    }
+                    pl += q256;
+                    c += r256;
+                    if (c >= K4) {
+                        c -= K4;
+                        pl++;
+                    }
+                }
+            }
+            __syncthreads();
+            if (!tiled) continue;
+            if (MATRIX) {   // phase 2: lane = pixel, CRF_CL labels per pass over k; M rows through scalar loads (wave-uniform)
+                const float* const x = msg + pxc * ldt;
+                for (int l0 = lg * CRF_CL; l0 < K; l0 += NG * CRF_CL) {
+                    float a[CRF_CL];
+#pragma unroll
+                    for (int i = 0; i < CRF_CL; i++) a[i] = 0.f;
+                    const float* tm = MT + l0;                           // (labels past K: the zero pad of the transposed matrix)
+#pragma unroll 4
+                    for (int k = 0; k < K; k++) {
+                        const float mk = x[k];
+#pragma unroll
+                        for (int i = 0; i < CRF_CL; i++) a[i] = __fadd_rn(a[i], __fmul_rn(tm[i], mk));
+                        tm += ldm;
+                    }
+#pragma unroll
+                    for (int i = 0; i < CRF_CL; i++) {
+                        if (act && l0 + i < K) {
+                            float* const t = tile + px2 * ldt + l0 + i;
+                            *t = __fadd_rn(*t, a[i]);
+                        }
+                    }
+                }
+                __syncthreads();
+            }
+            if (last) {
+                // softmax, label, pad: crf_update_compat_kernel's steps -- maximum (a NaN wins) and sum (k ascending) by one
+                // thread per row, exponentials and divisions by the lanes of phase 2
+                if (tid < TP) {
+                    const float* row = tile + tid * ldt;
+                    float mx = row[0];
+                    for (int k = 1; k < K; k++) {
+                        const float v = row[k];
+                        if (v > mx || v != v) mx = v;
+                    }
+                    rec_n[tid] = mx;
+                }
+                __syncthreads();
+                if (act) {
+                    float* row = tile + px2 * ldt;
+                    const float mx = rec_n[px2];
+                    for (int k = lg; k < K; k += NG) row[k] = pnp_expf(__fsub_rn(row[k], mx));
+                }
+                __syncthreads();
+                if (tid < TP) {
+                    const float* row = tile + tid * ldt;
+                    float sm = 0.f;
+                    for (int k = 0; k < K; k++) sm = __fadd_rn(sm, row[k]);
+                    rec_n[tid] = sm;
+                }
+                __syncthreads();
+                if (act) {
+                    float* row = tile + px2 * ldt;
+                    const float sm = rec_n[px2];
+                    for (int k = lg; k < K; k += NG) row[k] = __fdiv_rn(row[k], sm);
+                }
+                __syncthreads();
+                if (tid < TP) {
+                    const int px = tid;
+                    float* row = tile + px * ldt;
+                    if (lout.lab[0]) {                                   // first maximum, NaN counts as maximum (np.argmax)
+                        int best = 0;
+                        float bv = row[0];
+                        for (int k = 1; k < K; k++) {
+                            const float v = row[k];
+                            if (bv == bv && (v > bv || v != v)) {
+                                best = k;
+                                bv = v;
+                            }
+                        }
+                        if (inside(px)) lout.lab[0][lout.label_off[b] + pixel_of(px)] = (uint8_t)lout.lut[b * lout.lut_stride + best];
+                    }
+                    for (int k = K; k < Kp; k++) row[k] = 0.f;           // pad floats stay zero
+                }
+                __syncthreads();
+            }
+            {
+                int pl = pl0, c = c0;
+                for (int item = tid; item < TP * K4; item += 256) {
+                    if (inside(pl)) {
+                        const float* r = tile + pl * ldt + 4 * c;
+                        const f32x4 v = {r[0], r[1], r[2], r[3]};
+                        if (last) st_stream(O4 + (size_t)pixel_of(pl) * K4 + c, v);
+                        else O4[(size_t)pixel_of(pl) * K4 + c] = v;
+                    }
+                    pl += q256;
+                    c += r256;
+                    if (c >= K4) {
+                        c -= K4;
+                        pl++;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
+
 // ---- spatial renumbering.  The key sort numbers lattice points in (colour-major) key order; the
 // iteration kernels are gather-bound, so the points of each image are renumbered by the position of their
 // FIRST contributor pixel along a Z-order curve over the image: contributors, simplex vertices of neighbouring
@@ -1297,25 +1624,44 @@ static inline int ok() { return hipGetLastError() == hipSuccess ? PNP_OK : PNP_E
 
 size_t crf_sort_temp_bytes(size_t max_entries) { return sort_temp_bytes(max_entries) + 256; }
 
-// Build one lattice (D = 2: Gaussian x/sx, y/sy ; D = 5: bilateral x/sx, y/sy, r/sr, g/sg, b/sb) for images [0,B): sxy = (sx, sy),
-// srgb = (sr, sg, sb), one width per feature axis.  The scratch arrays and the roles each of them takes in turn: CrfBuildScratch
-// (kernels.h).
-int crf_build_lattice(int D, const CrfLattice& L, const PostDesc* d_imgs, const PostDesc* h_imgs, const uint8_t* d_rgb, const float sxy[2],
-                      const float srgb[3], int B, size_t ent_total, int max_pixels, const CrfBuildScratch& sc, int* h_range_err, int* h_points,
-                      hipStream_t s) {
+// Build one lattice for images [0,B).  d_feat null: D = 2 (Gaussian x/sx, y/sy) or D = 5 (bilateral x/sx, y/sy, r/sr, g/sg, b/sb)
+// from pixel positions and d_rgb, sxy = (sx, sy), srgb = (sr, sg, sb), one width per feature axis.  d_feat: D = 1 .. 6 feature
+// planes of the caller's (lattice_embed_features_kernel; keys without image bits).  The scratch arrays and the roles each of
+// them takes in turn: CrfBuildScratch (kernels.h).
+static int build_lattice(int D, const CrfLattice& L, const PostDesc* d_imgs, const PostDesc* h_imgs, const uint8_t* d_rgb, const float sxy[2],
+                         const float srgb[3], const float* d_feat, int B, size_t ent_total, int max_pixels, const CrfBuildScratch& sc,
+                         int* h_range_err, int* h_points, hipStream_t s) {
     const int nb = (max_pixels + 255) / 256 < 512 ? (max_pixels + 255) / 256 : 512;
-    if (D == 2)
+    int coord_bits = 0;
+#define PNP_EMBED_FEATURES(D_)                                                                                                       \
+    case D_:                                                                                                                         \
+        hipLaunchKernelGGL((lattice_embed_features_kernel<D_>), dim3(nb, B), dim3(256), 0, s, d_imgs, d_feat, L.bary, sc.keys_a, sc.vals_a, \
+                           sc.range_err);                                                                                            \
+        coord_bits = D_ * FeatKey<D_>::BITS;                                                                                         \
+        break
+    if (d_feat) {
+        switch (D) {
+            PNP_EMBED_FEATURES(1);
+            PNP_EMBED_FEATURES(2);
+            PNP_EMBED_FEATURES(3);
+            PNP_EMBED_FEATURES(4);
+            PNP_EMBED_FEATURES(5);
+            PNP_EMBED_FEATURES(6);
+            default: return PNP_ERR_ARG;
+        }
+    } else if (D == 2)
         hipLaunchKernelGGL((lattice_embed_kernel<2>), dim3(nb, B), dim3(256), 0, s, d_imgs, d_rgb, sxy[0], sxy[1], srgb[0], srgb[1], srgb[2], L.bary, sc.keys_a, sc.vals_a, sc.range_err);
     else if (D == 5)
         hipLaunchKernelGGL((lattice_embed_kernel<5>), dim3(nb, B), dim3(256), 0, s, d_imgs, d_rgb, sxy[0], sxy[1], srgb[0], srgb[1], srgb[2], L.bary, sc.keys_a, sc.vals_a, sc.range_err);
     else
         return PNP_ERR_ARG;
+#undef PNP_EMBED_FEATURES
     if (B > (1 << IMG_BITS)) return PNP_ERR_ARG;
     // bits actually populated: coordinates (D * BITS, low) + image index (IMG_SHIFT..)
     // stable sort by (image, coordinates).  The entries of image b are the run [pix0 * (D+1), (pix0 + H W) * (D+1)) on entry, so
     // the sort is segmented by image over the coordinate bits [0, D * BITS) alone (sort.hip; the image bits at IMG_SHIFT stay in
     // the keys for the kernels below; the inputs sc.keys_a / sc.vals_a are scratch from here on)
-    const int coord_bits = D == 2 ? 2 * KeyPack<2>::BITS : 5 * KeyPack<5>::BITS;
+    if (!d_feat) coord_bits = D == 2 ? 2 * KeyPack<2>::BITS : 5 * KeyPack<5>::BITS;
     size_t seg_off[(1 << IMG_BITS) + 1];
     for (int b = 0; b < B; b++) {
         seg_off[b] = (size_t)h_imgs[b].pix0 * (D + 1);
@@ -1332,10 +1678,25 @@ int crf_build_lattice(int D, const CrfLattice& L, const PostDesc* d_imgs, const 
     if (const int r = device_scan_i32(sc.head, sc.incl, ent_total, true, sc.temp, sc.temp_bytes, s); r != PNP_OK) return r;
     hipLaunchKernelGGL(scatter_ids_kernel, dim3(nbe, B), dim3(256), 0, s, sc.keys_b, L.vals, sc.head, sc.incl, d_imgs, D + 1, B,
                        ent_total, L.offset, L.seg_start, L.ukeys, L.idbase);
-    if (D == 2)
+#define PNP_NBR_FEATURES(D_)                                                                                                         \
+    case D_:                                                                                                                         \
+        hipLaunchKernelGGL((neighbors_kernel<D_, FeatKey<D_>::BITS, false>), dim3(nbe, B), dim3(256), 0, s, L.ukeys, L.idbase, L.cap, sc.n1k, \
+                           sc.n2k);                                                                                                  \
+        break
+    if (d_feat) {
+        switch (D) {
+            PNP_NBR_FEATURES(1);
+            PNP_NBR_FEATURES(2);
+            PNP_NBR_FEATURES(3);
+            PNP_NBR_FEATURES(4);
+            PNP_NBR_FEATURES(5);
+            PNP_NBR_FEATURES(6);
+        }
+    } else if (D == 2)
         hipLaunchKernelGGL((neighbors_kernel<2>), dim3(nbe, B), dim3(256), 0, s, L.ukeys, L.idbase, L.cap, sc.n1k, sc.n2k);
     else
         hipLaunchKernelGGL((neighbors_kernel<5>), dim3(nbe, B), dim3(256), 0, s, L.ukeys, L.idbase, L.cap, sc.n1k, sc.n2k);
+#undef PNP_NBR_FEATURES
     // spatial renumbering (needs the lattice size on the host: one small read-back per build)
     int M = 0;
     int h_idbase[(1 << IMG_BITS) + 1];                    // first lattice id of every image (the second sort's segments)
@@ -1373,6 +1734,24 @@ int crf_build_lattice(int D, const CrfLattice& L, const PostDesc* d_imgs, const 
     hipLaunchKernelGGL(set_segments_kernel, dim3(1024), dim3(256), 0, s, sc.incl, M, L.seg_lo, L.seg_hi);
     if (hipMemcpyAsync(L.vals, vals2, ent_total * sizeof(uint32_t), hipMemcpyDeviceToDevice, s) != hipSuccess) return PNP_ERR_HIP;
     return ok();
+}
+
+int crf_build_lattice(int D, const CrfLattice& L, const PostDesc* d_imgs, const PostDesc* h_imgs, const uint8_t* d_rgb, const float sxy[2],
+                      const float srgb[3], int B, size_t ent_total, int max_pixels, const CrfBuildScratch& sc, int* h_range_err, int* h_points,
+                      hipStream_t s) {
+    return build_lattice(D, L, d_imgs, h_imgs, d_rgb, sxy, srgb, nullptr, B, ent_total, max_pixels, sc, h_range_err, h_points, s);
+}
+
+int crf_build_lattice_features(int D, const CrfLattice& L, const PostDesc* d_imgs, const PostDesc* h_imgs, const float* d_feat, int B,
+                               size_t ent_total, int max_pixels, const CrfBuildScratch& sc, int* h_range_err, int* h_points, hipStream_t s) {
+    if (!d_feat) return PNP_ERR_ARG;
+    return build_lattice(D, L, d_imgs, h_imgs, nullptr, nullptr, nullptr, d_feat, B, ent_total, max_pixels, sc, h_range_err, h_points, s);
+}
+
+int crf_feature_key_limit(int D) {
+    const int bits = 64 / D < 16 ? 64 / D : 16;
+    const int by_key = (1 << (bits - 1)) - D - 1;
+    return by_key < (int)CRF_FEAT_ELEV_LIMIT ? by_key : (int)CRF_FEAT_ELEV_LIMIT;
 }
 
 static float crf_alpha(int D) { return 1.0f / (1 + powf(2, (float)-D)); }
@@ -1536,6 +1915,57 @@ int crf_update_compat(const CrfLattice& Lg, const CrfLattice& Lb, const PostDesc
         hipLaunchKernelGGL(crf_update_compat_kernel<false>, dim3(nb), dim3(256), smem, s, Lg, Lb, d_imgs, vg, vb, norm_g, norm_b, unary, Q,
                            MgT, MbT, ldm, crf_alpha(2), crf_alpha(5), img0, nimg, tp, labels, kl_pix);
     return ok();
+}
+
+// LDS rows per pixel and pixels per tile of crf_term_update_kernel (see there): crf_compat_tile_pixels' rule on its own rows
+static int crf_term_tile_pixels(int max_kp, int D1, int rows, size_t* smem) {
+    const size_t per_pixel = ((size_t)rows * (max_kp + 1) + 2 * D1 + 1) * sizeof(float);
+    int tp = 256;
+    while (tp > 64 && tp * per_pixel > 64 * 1024) tp >>= 1;
+    if (tp * per_pixel > 158 * 1024) tp = 32;
+    *smem = tp * per_pixel;
+    return tp;
+}
+
+template <int D1, bool MATRIX>
+static int launch_term_update(const CrfLattice& L, const PostDesc* d_imgs, int img0, int nimg, const float* val, const float* norm,
+                              const float* base, bool first, float* out, bool last, float w, const float* wvec, const float* MT, int ldm,
+                              int max_kp, hipStream_t s, const CrfLabelOut& labels) {
+    size_t smem = 0;
+    const int tp = crf_term_tile_pixels(max_kp, D1, (MATRIX ? 1 : 0) + (MATRIX || last ? 1 : 0), &smem);
+    if (smem > 160 * 1024) return PNP_ERR_ARG;
+    if (smem > 64 * 1024) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(crf_term_update_kernel<D1, MATRIX>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)smem) != hipSuccess)
+            return PNP_ERR_HIP;
+    }
+    const int nb = resident_grid(crf_term_update_kernel<D1, MATRIX>, 256, smem);
+    hipLaunchKernelGGL((crf_term_update_kernel<D1, MATRIX>), dim3(nb), dim3(256), smem, s, L, d_imgs, val, norm, base, first ? 1 : 0, out,
+                       last ? 1 : 0, w, wvec, MT, ldm, crf_alpha(D1 - 1), img0, nimg, tp, labels);
+    return ok();
+}
+
+// One term of a T-term update (crf_term_update_kernel).  d_imgs: the term's descriptors; val: its filtered values (crf_filter);
+// base: the unary rows (first) or the logit rows; out: the logit rows, or Q (last).  MT non-null: the K x K message weights
+// transposed as crf_update_compat takes them; else wvec non-null: one weight per label (ldm floats, zero beyond K); else w
+int crf_term_update(const CrfLattice& L, const PostDesc* d_imgs, int img0, int nimg, const float* val, const float* norm, const float* base,
+                    bool first, float* out, bool last, float w, const float* wvec, const float* MT, int ldm, int max_kp, hipStream_t s,
+                    const CrfLabelOut& labels) {
+    if (max_kp < 4 || max_kp > 256 || ((MT || wvec) && (ldm < max_kp || ldm % CRF_CL != 0))) return PNP_ERR_ARG;
+#define PNP_TERM(D1_)                                                                                                                \
+    case D1_:                                                                                                                        \
+        return MT ? launch_term_update<D1_, true>(L, d_imgs, img0, nimg, val, norm, base, first, out, last, w, wvec, MT, ldm, max_kp, s, labels) \
+                  : launch_term_update<D1_, false>(L, d_imgs, img0, nimg, val, norm, base, first, out, last, w, wvec, MT, ldm, max_kp, s, labels)
+    switch (L.D1) {
+        PNP_TERM(2);
+        PNP_TERM(3);
+        PNP_TERM(4);
+        PNP_TERM(5);
+        PNP_TERM(6);
+        PNP_TERM(7);
+    }
+#undef PNP_TERM
+    return PNP_ERR_ARG;
 }
 
 }  // namespace pnp

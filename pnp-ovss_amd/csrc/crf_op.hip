@@ -233,6 +233,17 @@ struct pnp_crf {
     // -- stepwise inference: Q holds the marginals of the last start / step / infer on this batch
     bool started = false;
     double *kl_pix = nullptr, *kl_part = nullptr, *kl_out = nullptr;
+    // -- feature terms (pnp_crf_create_terms; max_terms = 0: a two-term solver).  terms_batch: the batch of the last set_batch is
+    // one of pnp_crf_set_batch_terms, with T terms of tdims[t] feature axes; d_tdesc: [max_terms][maxB] the terms' descriptors
+    // (PostDesc::voff = the term's value rows).  Compatibility per term (pnp_crf_set_term_compat; holds until changed): d_TM
+    // [max_terms] transposed matrices of stride ldm, d_Tvec [max_terms][ldm] vectors
+    int max_terms = 0, max_dims = 0;
+    bool terms_batch = false;
+    int T = 0, tdims[PNP_CRF_MAX_TERMS] = {0};
+    PostDesc* d_tdesc = nullptr;
+    std::vector<PostDesc> tdesc;
+    int tkind[PNP_CRF_MAX_TERMS] = {0}, tcompat_K[PNP_CRF_MAX_TERMS] = {0};
+    float *d_TM = nullptr, *d_Tvec = nullptr;
     char err[512] = {0};
 };
 
@@ -261,7 +272,8 @@ template <typename T>
 int calloc_dev(pnp_crf* c, T** out, size_t count, bool zero = false) {
     void* p = nullptr;
     const size_t bytes = std::max<size_t>((count * sizeof(T) + 255) / 256 * 256, 256);
-    if (hipMalloc(&p, bytes) != hipSuccess) return cfail(c, PNP_ERR_NOMEM, "hipMalloc(%zu) failed", bytes);
+    if (hipMalloc(&p, bytes) != hipSuccess)
+        return cfail(c, PNP_ERR_NOMEM, "out of device memory: an allocation of %zu bytes failed with %zu bytes already held", bytes, c->alloc_bytes);
     c->allocs.push_back(p);
     c->alloc_bytes += bytes;
     if (zero && hipMemset(p, 0, bytes) != hipSuccess) return cfail(c, PNP_ERR_HIP, "hipMemset failed");
@@ -271,22 +283,32 @@ int calloc_dev(pnp_crf* c, T** out, size_t count, bool zero = false) {
 
 int crf_reserve(pnp_crf* c) {
     const size_t TP = (size_t)c->max_total_pix, B = (size_t)c->maxB;
-    CK(c, calloc_dev(c, &c->d_desc, B));
-    CK(c, calloc_dev(c, &c->d_label_off, B + 1));
-    CK(c, calloc_dev(c, &c->d_lut, 256));
+#define CALLOC(call)                 /* (calloc_dev's message says how many bytes were wanted: kept) */ \
+    do {                                                                                               \
+        if (int _r = (call)) return _r;                                                                \
+    } while (0)
+    CALLOC(calloc_dev(c, &c->d_desc, B));
+    CALLOC(calloc_dev(c, &c->d_label_off, B + 1));
+    CALLOC(calloc_dev(c, &c->d_lut, 256));
     {
         int32_t ident[256];
         for (int i = 0; i < 256; i++) ident[i] = i;
         CHIP(c, hipMemcpy(c->d_lut, ident, sizeof(ident), hipMemcpyHostToDevice));
     }
-    for (const CrfAlloc& a : crf_reserve_plan(c->ws, B, TP, TP, (size_t)c->maxKp, 1))
-        CK(c, calloc_dev(c, reinterpret_cast<char**>(a.dst), a.bytes, a.zero));
+    for (const CrfAlloc& a : crf_reserve_plan(c->ws, B, TP, TP, (size_t)c->maxKp, 1, (size_t)c->max_terms, (size_t)c->max_dims))
+        CALLOC(calloc_dev(c, reinterpret_cast<char**>(a.dst), a.bytes, a.zero));
     // compatibility matrices, and the KL divergence's per-pixel terms, per-run partials and per-image results
     c->ldm = (c->maxKp + 7) / 8 * 8;
-    CK(c, calloc_dev(c, &c->d_M, 2 * (size_t)c->ldm * c->ldm, true));
-    CK(c, calloc_dev(c, &c->kl_pix, TP));
-    CK(c, calloc_dev(c, &c->kl_part, TP / CRF_KL_RUN + B + 1));
-    CK(c, calloc_dev(c, &c->kl_out, B));
+    CALLOC(calloc_dev(c, &c->d_M, 2 * (size_t)c->ldm * c->ldm, true));
+    CALLOC(calloc_dev(c, &c->kl_pix, TP));
+    CALLOC(calloc_dev(c, &c->kl_part, TP / CRF_KL_RUN + B + 1));
+    CALLOC(calloc_dev(c, &c->kl_out, B));
+    if (c->max_terms) {
+        CALLOC(calloc_dev(c, &c->d_tdesc, (size_t)c->max_terms * B));
+        CALLOC(calloc_dev(c, &c->d_TM, (size_t)c->max_terms * c->ldm * c->ldm, true));
+        CALLOC(calloc_dev(c, &c->d_Tvec, (size_t)c->max_terms * c->ldm, true));
+    }
+#undef CALLOC
     return PNP_OK;
 }
 
@@ -322,8 +344,10 @@ int crf_layout(pnp_crf* c, const pnp_crf_batch* b) {
 
 }  // namespace
 
-extern "C" int pnp_crf_create(int32_t device, int32_t max_batch, int64_t max_total_pixels, int32_t max_pixels_per_image,
-                              int32_t max_labels, pnp_crf** out) {
+namespace {
+
+int crf_create(int32_t device, int32_t max_batch, int64_t max_total_pixels, int32_t max_pixels_per_image, int32_t max_labels,
+               int32_t max_terms, int32_t max_dims, pnp_crf** out) {
     if (!out) return PNP_ERR_ARG;
     *out = nullptr;
     if (device < 0 || max_batch < 1 || max_batch > CRF_MAX_IMAGES || max_total_pixels < 1 || max_pixels_per_image < 1 ||
@@ -331,6 +355,8 @@ extern "C" int pnp_crf_create(int32_t device, int32_t max_batch, int64_t max_tot
         return PNP_ERR_ARG;
     if (hipSetDevice(device) != hipSuccess) return PNP_ERR_HIP;
     pnp_crf* c = new pnp_crf();
+    c->max_terms = max_terms;
+    c->max_dims = max_dims;
     c->device = device;
     c->maxB = max_batch;
     c->max_total_pix = max_total_pixels;
@@ -339,6 +365,20 @@ extern "C" int pnp_crf_create(int32_t device, int32_t max_batch, int64_t max_tot
     c->maxKp = (max_labels + 3) / 4 * 4;
     *out = c;                                     // handed out on failure too: pnp_crf_last_error says why, pnp_crf_destroy frees
     return crf_reserve(c);
+}
+
+}  // namespace
+
+extern "C" int pnp_crf_create(int32_t device, int32_t max_batch, int64_t max_total_pixels, int32_t max_pixels_per_image,
+                              int32_t max_labels, pnp_crf** out) {
+    return crf_create(device, max_batch, max_total_pixels, max_pixels_per_image, max_labels, 0, 0, out);
+}
+
+extern "C" int pnp_crf_create_terms(int32_t device, int32_t max_batch, int64_t max_total_pixels, int32_t max_pixels_per_image,
+                                    int32_t max_labels, int32_t max_terms, int32_t max_dims, pnp_crf** out) {
+    if (out) *out = nullptr;
+    if (max_terms < 1 || max_terms > PNP_CRF_MAX_TERMS || max_dims < 1 || max_dims > PNP_CRF_MAX_DIMS) return PNP_ERR_ARG;
+    return crf_create(device, max_batch, max_total_pixels, max_pixels_per_image, max_labels, max_terms, max_dims, out);
 }
 
 extern "C" void pnp_crf_destroy(pnp_crf* c) {
@@ -418,10 +458,119 @@ int crf_set_batch(pnp_crf* c, const pnp_crf_batch* b, const float pos_xy[2], con
     }
     if (built != PNP_OK) return cfail(c, built, "lattice build failed (%d): %s", built, hipGetErrorString(hipGetLastError()));
     c->ready = true;
+    c->terms_batch = false;
     return PNP_OK;
 }
 
+// The value rows of term t (dims[t] + 1 per pixel at most) image by image, into tdesc[t * B + i]; false: beyond the per-image
+// addressing of the iteration kernels (24-bit row ids, 32-bit byte offsets: crf.hip)
+bool crf_layout_terms(pnp_crf* c, int T, const int* dims, size_t* need) {
+    const int B = c->B;
+    c->tdesc.assign((size_t)T * B, PostDesc{});
+    *need = 0;
+    for (int t = 0; t < T; t++) {
+        size_t voff = 0;
+        for (int i = 0; i < B; i++) {
+            PostDesc d = c->desc[i];
+            const int64_t rows = (int64_t)d.H * d.W * (dims[t] + 1);
+            d.voff[0] = d.voff[1] = voff;
+            voff += (size_t)rows * d.Kp;
+            c->tdesc[(size_t)t * B + i] = d;
+            if (rows >= (1 << 24) || rows * d.Kp * 4 >= ((int64_t)1 << 32)) return false;
+        }
+        *need = std::max(*need, voff);
+    }
+    return true;
+}
+
 }  // namespace
+
+extern "C" int pnp_crf_set_batch_terms(pnp_crf* c, const pnp_crf_batch* b, int32_t n_terms, const pnp_crf_term* terms, void* stream) {
+    if (!c) return PNP_ERR_ARG;
+    c->ready = false;
+    c->started = false;
+    if (!b) return cfail(c, PNP_ERR_ARG, "batch is null");
+    if (!terms) return cfail(c, PNP_ERR_ARG, "the term array is null");
+    if (n_terms < 1 || n_terms > PNP_CRF_MAX_TERMS) return cfail(c, PNP_ERR_ARG, "%d terms: 1..%d", n_terms, PNP_CRF_MAX_TERMS);
+    int dims[PNP_CRF_MAX_TERMS];
+    const float* feat[PNP_CRF_MAX_TERMS];
+    for (int t = 0; t < n_terms; t++) {
+        if (terms[t].dims < 1 || terms[t].dims > PNP_CRF_MAX_DIMS)
+            return cfail(c, PNP_ERR_ARG, "term %d has %d feature axes: 1..%d", t, terms[t].dims, PNP_CRF_MAX_DIMS);
+        if (!terms[t].d_features) return cfail(c, PNP_ERR_ARG, "term %d: d_features is null", t);
+        dims[t] = terms[t].dims;
+        feat[t] = terms[t].d_features;
+    }
+    if (!c->max_terms) return cfail(c, PNP_ERR_STATE, "this solver holds no feature terms: create it with pnp_crf_create_terms");
+    if (!c->ws.va || !c->d_Tvec) return cfail(c, PNP_ERR_STATE, "the solver's workspace was not allocated (pnp_crf_create_terms failed)");
+    if (n_terms > c->max_terms) return cfail(c, PNP_ERR_ARG, "%d terms, the solver holds 1..%d", n_terms, c->max_terms);
+    for (int t = 0; t < n_terms; t++)
+        if (dims[t] > c->max_dims) return cfail(c, PNP_ERR_ARG, "term %d has %d feature axes, the solver holds 1..%d", t, dims[t], c->max_dims);
+    if (b->B < 1 || b->B > c->maxB) return cfail(c, PNP_ERR_ARG, "batch of %d images, the solver holds 1..%d", b->B, c->maxB);
+    if (!b->H || !b->W || !b->K || !b->d_unary) return cfail(c, PNP_ERR_ARG, "batch has null arrays (H, W, K, d_unary)");
+    if (int r = crf_layout(c, b)) return r;
+    size_t need = 0;
+    if (!crf_layout_terms(c, n_terms, dims, &need))
+        return cfail(c, PNP_ERR_ARG, "an image's lattice value rows exceed the per-image addressing of the mean-field kernels");
+    if (need > c->ws.val_cap) return cfail(c, PNP_ERR_ARG, "batch needs %zu lattice value floats, reserved %zu", need, c->ws.val_cap);
+    hipStream_t s = (hipStream_t)stream;
+    CHIP(c, hipSetDevice(c->device));
+    const int B = c->B;
+    CHIP(c, hipMemcpyAsync(c->d_desc, c->desc.data(), sizeof(PostDesc) * B, hipMemcpyHostToDevice, s));
+    for (int t = 0; t < n_terms; t++)
+        CHIP(c, hipMemcpyAsync(c->d_tdesc + (size_t)t * c->maxB, c->tdesc.data() + (size_t)t * B, sizeof(PostDesc) * B, hipMemcpyHostToDevice, s));
+    CHIP(c, hipMemcpyAsync(c->d_label_off, c->h_label_off.data(), sizeof(size_t) * (B + 1), hipMemcpyHostToDevice, s));
+    CK(c, crf_planes_rows(true, c->d_desc, const_cast<float*>(b->d_unary), c->ws.unary, B, c->maxHW, c->kp_max, s));
+    int range_term = -1;
+    const int built = crf_build_terms(c->ws, c->d_desc, c->desc.data(), B, c->h_label_off[B], c->maxHW, n_terms, dims, feat, &range_term, s);
+    if (range_term >= 0)
+        return cfail(c, built,
+                     "lattice key range exceeded: term %d (%d feature axes) has a lattice coordinate beyond the key (|coordinate| must stay "
+                     "below %d for %d axes) or a feature that is not finite; a wider kernel width (smaller features) is the remedy",
+                     range_term, dims[range_term], crf_feature_key_limit(dims[range_term]), dims[range_term]);
+    if (built != PNP_OK) return cfail(c, built, "lattice build failed (%d): %s", built, hipGetErrorString(hipGetLastError()));
+    c->T = n_terms;
+    for (int t = 0; t < n_terms; t++) c->tdims[t] = dims[t];
+    c->ready = true;
+    c->terms_batch = true;
+    return PNP_OK;
+}
+
+extern "C" int64_t pnp_crf_lattice_points(const pnp_crf* c, int32_t term) {
+    if (!c || !c->ready || term < 0 || term >= (c->terms_batch ? c->T : 2)) return -1;
+    return c->terms_batch ? c->ws.tlat_points[term] : c->ws.lat_points[term];
+}
+
+extern "C" int pnp_crf_set_term_compat(pnp_crf* c, int32_t term, int32_t kind, const float* host_values, int32_t K) {
+    if (!c) return PNP_ERR_ARG;
+    if (term < 0 || term >= PNP_CRF_MAX_TERMS || term >= c->max_terms)
+        return cfail(c, PNP_ERR_ARG, "term = %d: the solver holds terms 0..%d (pnp_crf_create_terms)", term, c->max_terms - 1);
+    if (kind == PNP_CRF_COMPAT_SCALAR) {          // the weight of the call; the values are not read
+        c->tkind[term] = kind;
+        c->tcompat_K[term] = 0;
+        return PNP_OK;
+    }
+    if (kind != PNP_CRF_COMPAT_DIAGONAL && kind != PNP_CRF_COMPAT_MATRIX)
+        return cfail(c, PNP_ERR_ARG, "kind = %d: scalar (0), diagonal (1) or matrix (2)", kind);
+    if (!host_values) return cfail(c, PNP_ERR_ARG, "compatibility values are null");
+    if (K < 2 || K > c->maxK) return cfail(c, PNP_ERR_ARG, "compatibility for %d labels, the solver holds 2..%d", K, c->maxK);
+    if (!c->d_TM || !c->d_Tvec) return cfail(c, PNP_ERR_STATE, "the solver's workspace was not allocated (pnp_crf_create_terms failed)");
+    const size_t ld = (size_t)c->ldm;
+    const bool diag = kind == PNP_CRF_COMPAT_DIAGONAL;
+    c->h_M.assign(diag ? ld : ld * ld, 0.f);
+    for (int l = 0; l < K; l++) {
+        if (diag) c->h_M[l] = host_values[l];
+        else
+            for (int k = 0; k < K; k++) c->h_M[k * ld + l] = host_values[(size_t)l * K + k];      // (transposed)
+    }
+    CHIP(c, hipSetDevice(c->device));
+    // (synchronous, as pnp_crf_set_compat: the weights may not change under a step still in flight)
+    CHIP(c, hipDeviceSynchronize());
+    CHIP(c, hipMemcpy(diag ? c->d_Tvec + term * ld : c->d_TM + term * ld * ld, c->h_M.data(), sizeof(float) * c->h_M.size(), hipMemcpyHostToDevice));
+    c->tkind[term] = kind;
+    c->tcompat_K[term] = K;
+    return PNP_OK;
+}
 
 extern "C" int pnp_crf_set_batch(pnp_crf* c, const pnp_crf_batch* b, float pos_xy, float bi_xy, float bi_rgb, void* stream) {
     if (!c) return PNP_ERR_ARG;
@@ -475,6 +624,13 @@ namespace {
 int crf_need_batch(pnp_crf* c) {
     if (!c->ready) return cfail(c, PNP_ERR_STATE, "no batch is set: call pnp_crf_set_batch first (a failed call leaves none)");
     return PNP_OK;
+}
+
+// The two kinds of batch have their own inference calls (pnp_crf_start and pnp_crf_read serve both)
+int crf_need_kind(pnp_crf* c, bool terms, const char* call) {
+    if (c->terms_batch == terms) return PNP_OK;
+    if (terms) return cfail(c, PNP_ERR_STATE, "%s needs a batch of pnp_crf_set_batch_terms; the batch set is a two-term one (pnp_crf_infer / _step)", call);
+    return cfail(c, PNP_ERR_STATE, "%s needs a two-term batch (pnp_crf_set_batch); the batch set has feature terms (pnp_crf_infer_terms / _step_terms)", call);
 }
 
 // Both terms as matrices on the device: a term left scalar as w * I.  Vector / matrix kinds fix the label count of the batch
@@ -534,12 +690,59 @@ int crf_step(pnp_crf* c, int n, float pos_w, float bi_w, hipStream_t s, const Cr
     return PNP_OK;
 }
 
+// n updates of the T feature terms from the current Q; weights[t]: the weight of a term left scalar
+int crf_step_terms(pnp_crf* c, int n, const float* weights, hipStream_t s, const CrfLabelOut& lab) {
+    const size_t ld = (size_t)c->ldm;
+    const PostDesc* desc[PNP_CRF_MAX_TERMS];
+    const float *wvec[PNP_CRF_MAX_TERMS], *MT[PNP_CRF_MAX_TERMS];
+    for (int t = 0; t < c->T; t++) {
+        if (c->tkind[t] != PNP_CRF_COMPAT_SCALAR)
+            for (int i = 0; i < c->B; i++)
+                if (c->desc[i].K != c->tcompat_K[t])
+                    return cfail(c, PNP_ERR_ARG, "term %d's compatibility is for %d labels, image %d of the batch has %d: a vector or matrix "
+                                 "compatibility needs that many labels in every image", t, c->tcompat_K[t], i, c->desc[i].K);
+        desc[t] = c->d_tdesc + (size_t)t * c->maxB;
+        wvec[t] = c->tkind[t] == PNP_CRF_COMPAT_DIAGONAL ? c->d_Tvec + t * ld : nullptr;
+        MT[t] = c->tkind[t] == PNP_CRF_COMPAT_MATRIX ? c->d_TM + t * ld * ld : nullptr;
+    }
+    const CrfTermsRun run{c->T, desc, weights, wvec, MT, (int)ld};
+    CK(c, crf_meanfield(c->ws, crf_span(c), false, n, 0.f, 0.f, nullptr, nullptr, 0, s, lab, &run));
+    return PNP_OK;
+}
+
 }  // namespace
+
+extern "C" int pnp_crf_infer_terms(pnp_crf* c, int32_t iters, const float* weights, float* d_q, uint8_t* d_labels, void* stream) {
+    if (!c) return PNP_ERR_ARG;
+    if (iters < 0) return cfail(c, PNP_ERR_ARG, "iters = %d", iters);
+    if (!weights) return cfail(c, PNP_ERR_ARG, "weights is null (one float per term)");
+    if (int r = crf_need_batch(c)) return r;
+    if (int r = crf_need_kind(c, true, "pnp_crf_infer_terms")) return r;
+    hipStream_t s = (hipStream_t)stream;
+    CHIP(c, hipSetDevice(c->device));
+    const CrfLabelOut lab = crf_labels(c, d_labels);
+    if (int r = crf_start(c, s, iters == 0 ? lab : CrfLabelOut())) return r;
+    if (int r = crf_step_terms(c, iters, weights, s, lab)) return r;
+    if (d_q) CK(c, crf_planes_rows(false, c->d_desc, d_q, c->ws.Q, c->B, c->maxHW, c->kp_max, s));
+    return PNP_OK;
+}
+
+extern "C" int pnp_crf_step_terms(pnp_crf* c, int32_t n, const float* weights, void* stream) {
+    if (!c) return PNP_ERR_ARG;
+    if (n < 0) return cfail(c, PNP_ERR_ARG, "n = %d", n);
+    if (!weights) return cfail(c, PNP_ERR_ARG, "weights is null (one float per term)");
+    if (int r = crf_need_batch(c)) return r;
+    if (int r = crf_need_kind(c, true, "pnp_crf_step_terms")) return r;
+    if (!c->started) return cfail(c, PNP_ERR_STATE, "no inference was started on this batch: call pnp_crf_start (or pnp_crf_infer_terms) first");
+    CHIP(c, hipSetDevice(c->device));
+    return crf_step_terms(c, n, weights, (hipStream_t)stream, CrfLabelOut());
+}
 
 extern "C" int pnp_crf_infer(pnp_crf* c, int32_t iters, float pos_w, float bi_w, float* d_q, uint8_t* d_labels, void* stream) {
     if (!c) return PNP_ERR_ARG;
     if (iters < 0) return cfail(c, PNP_ERR_ARG, "iters = %d", iters);
     if (int r = crf_need_batch(c)) return r;
+    if (int r = crf_need_kind(c, false, "pnp_crf_infer")) return r;
     hipStream_t s = (hipStream_t)stream;
     CHIP(c, hipSetDevice(c->device));
     // pnp_crf_start + pnp_crf_step(iters) with the labels fused into the last update, then the marginals out
@@ -561,6 +764,7 @@ extern "C" int pnp_crf_step(pnp_crf* c, int32_t n, float pos_w, float bi_w, void
     if (!c) return PNP_ERR_ARG;
     if (n < 0) return cfail(c, PNP_ERR_ARG, "n = %d", n);
     if (int r = crf_need_batch(c)) return r;
+    if (int r = crf_need_kind(c, false, "pnp_crf_step")) return r;
     if (!c->started) return cfail(c, PNP_ERR_STATE, "no inference was started on this batch: call pnp_crf_start (or pnp_crf_infer) first");
     CHIP(c, hipSetDevice(c->device));
     return crf_step(c, n, pos_w, bi_w, (hipStream_t)stream, CrfLabelOut());
@@ -581,6 +785,7 @@ extern "C" int pnp_crf_kl(pnp_crf* c, float pos_w, float bi_w, double* h_out_per
     if (!c) return PNP_ERR_ARG;
     if (!h_out_per_image) return cfail(c, PNP_ERR_ARG, "h_out_per_image is null");
     if (int r = crf_need_batch(c)) return r;
+    if (c->terms_batch) return cfail(c, PNP_ERR_ARG, "the KL divergence is not available for a batch of feature terms (pnp_crf_set_batch_terms)");
     if (!c->started) return cfail(c, PNP_ERR_STATE, "no inference was started on this batch: call pnp_crf_start (or pnp_crf_infer) first");
     hipStream_t s = (hipStream_t)stream;
     CHIP(c, hipSetDevice(c->device));

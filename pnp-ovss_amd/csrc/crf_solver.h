@@ -27,6 +27,14 @@ struct CrfWorkspace {
     size_t val_cap = 0, valg_cap = 0;             // floats of the bilateral (va, vb) / Gaussian (vga, vgb) lattice value buffers
     std::vector<double> gauss_sig;                // what the Gaussian lattice was last built for: its widths (sx, sy), then H, W of every image
     int lat_points[2] = {0, 0};                   // lattice points of the last build (Gaussian, bilateral)
+    // Feature terms (crf_reserve_plan with max_terms > 0): one lattice of up to max_dims axes and one normaliser per term, each
+    // sized for the worst case of max_dims + 1 lattice points per pixel.  The terms take turns in va / vb -- a term's filtered
+    // values are consumed by its own update launch -- and add into the pixel-major rows of `logit`
+    int max_terms = 0, max_dims = 0;
+    std::vector<CrfLattice> tlat;
+    std::vector<float*> tnorm;
+    std::vector<int> tlat_points;
+    float* logit = nullptr;
 };
 
 // One device allocation of the workspace: the owner allocates `bytes` with its own allocator (its list, its byte count),
@@ -38,8 +46,10 @@ struct CrfAlloc {
 };
 // The workspace's allocations, in order, for batches of at most `images` images and `total_pix` pixels, rows of `groups` channel
 // groups of at most max_kp floats each, and lattice value buffers for the rows of `value_pix` pixels at once (a chunk of the
-// batch; total_pix: all of it).  Sets the capacities of `ws`.
-std::vector<CrfAlloc> crf_reserve_plan(CrfWorkspace& ws, size_t images, size_t total_pix, size_t value_pix, size_t max_kp, size_t groups);
+// batch; total_pix: all of it).  max_terms > 0: also up to that many feature-term lattices of 1 .. max_dims axes (build scratch
+// for max_dims + 1 entries per pixel, value buffers for max_dims + 1 rows per pixel).  Sets the capacities of `ws`.
+std::vector<CrfAlloc> crf_reserve_plan(CrfWorkspace& ws, size_t images, size_t total_pix, size_t value_pix, size_t max_kp, size_t groups,
+                                       size_t max_terms = 0, size_t max_dims = 0);
 
 struct CrfOffsets {                               // running offsets of a batch layout
     int64_t pix = 0;
@@ -56,6 +66,24 @@ bool crf_layout_image(PostDesc& d, int groups, CrfOffsets& at);
 int crf_build(CrfWorkspace& ws, const PostDesc* d_desc, const PostDesc* h_desc, int B, size_t total_pix, int maxHW, const uint8_t* d_rgb,
               const float pos_xy[2], const float bi_xy[2], const float bi_rgb[3], int* range_term, hipStream_t s);
 
+// The lattices and normalisers of T feature terms (ws.tlat / ws.tnorm [0, T)): term t has dims[t] = 1 .. ws.max_dims feature planes
+// per image in d_feat[t] (crf_build_lattice_features).  One synchronisation per lattice.  A raised range flag (a coordinate
+// beyond the key, a non-finite feature) ends the build: PNP_ERR_ARG with *range_term = that term, else -1; the flag is cleared.
+int crf_build_terms(CrfWorkspace& ws, const PostDesc* d_desc, const PostDesc* h_desc, int B, size_t total_pix, int maxHW, int T,
+                    const int* dims, const float* const* d_feat, int* range_term, hipStream_t s);
+
+// What a T-term update takes besides the workspace: per term its descriptors (device; PostDesc::voff[0] = the term's value
+// rows), and its compatibility -- MT[t] (K x K message weights, transposed as crf_update_compat takes them) or else wvec[t] (one
+// weight per label, ldm floats) or else the scalar w[t]
+struct CrfTermsRun {
+    int T;
+    const PostDesc* const* d_desc;
+    const float* w;
+    const float* const* wvec;
+    const float* const* MT;
+    int ldm;
+};
+
 struct CrfSpan {                                  // the images [img0, img0 + nimg) of one layout of a batch
     const PostDesc* d_desc;
     int img0, nimg;
@@ -66,8 +94,10 @@ struct CrfSpan {                                  // the images [img0, img0 + ni
 int crf_meanfield_filter(const CrfWorkspace& ws, const CrfSpan& v, const float** rg, const float** rb, hipStream_t s);
 // The mean-field on the images of v.  start: Q0 = softmax(-U) first; then n updates from the current Q, each both filters and the
 // Potts kernel with the weights of the call or, with matrices (MgT, MbT, ldm as crf_update_compat takes them; one group only),
-// the compatibility kernel.  labels: the label output of the last update
+// the compatibility kernel.  labels: the label output of the last update.  terms non-null: each update is instead the T feature
+// terms in order -- filter, then crf_term_update into the logit rows, the last one ending in the softmax -- and the two-term
+// arguments are not read
 int crf_meanfield(const CrfWorkspace& ws, const CrfSpan& v, bool start, int n, float pos_w, float bi_w, const float* MgT, const float* MbT,
-                  int ldm, hipStream_t s, const CrfLabelOut& labels);
+                  int ldm, hipStream_t s, const CrfLabelOut& labels, const CrfTermsRun* terms = nullptr);
 
 }  // namespace pnp

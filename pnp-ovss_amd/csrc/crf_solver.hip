@@ -5,7 +5,8 @@
 
 namespace pnp {
 
-std::vector<CrfAlloc> crf_reserve_plan(CrfWorkspace& ws, size_t B, size_t TP, size_t value_pix, size_t Kp, size_t groups) {
+std::vector<CrfAlloc> crf_reserve_plan(CrfWorkspace& ws, size_t B, size_t TP, size_t value_pix, size_t Kp, size_t groups, size_t max_terms,
+                                       size_t max_dims) {
     std::vector<CrfAlloc> plan;
     auto want = [&plan](size_t count, bool zero, auto**... dst) {      // `count` elements for each of dst, in order
         (plan.push_back({reinterpret_cast<void**>(dst), count * sizeof(**dst), zero}), ...);
@@ -24,16 +25,38 @@ std::vector<CrfAlloc> crf_reserve_plan(CrfWorkspace& ws, size_t B, size_t TP, si
         want(L.cap * L.D1, false, &L.n1, &L.n2);
         want(L.cap * (L.D1 / 2), false, &L.nbr8);
     }
-    const size_t cap6 = ws.lat[1].cap;            // E of CrfBuildScratch (kernels.h)
+    // feature terms: every lattice for the worst case of max_dims + 1 points per pixel
+    const size_t tD1 = max_terms ? max_dims + 1 : 0;
+    ws.max_terms = (int)max_terms;
+    ws.max_dims = (int)max_dims;
+    ws.tlat.assign(max_terms, CrfLattice{});
+    ws.tnorm.assign(max_terms, nullptr);
+    ws.tlat_points.assign(max_terms, 0);
+    for (size_t t = 0; t < max_terms; t++) {
+        CrfLattice& L = ws.tlat[t];
+        L.D1 = (int)tD1;                          // (crf_build_terms sets the term's own d + 1)
+        L.which = 1;
+        L.cap = TP * tD1;
+        want(L.cap, false, &L.bary, &L.vals, &L.ent, &L.offset);
+        want(L.cap + 1, false, &L.seg_start);
+        want(L.cap, false, &L.seg_lo, &L.seg_hi, &L.ukeys);
+        want(B + 1, false, &L.idbase);
+        want(L.cap * tD1, false, &L.n1, &L.n2);
+        want(L.cap * (tD1 / 2), false, &L.nbr8);
+        want(TP, false, &ws.tnorm[t]);
+    }
+    if (max_terms) want(TP * Kp * groups, false, &ws.logit);
+    const size_t rows = std::max<size_t>(6, tD1);  // lattice points per pixel at most, over every lattice of the workspace
+    const size_t cap6 = TP * rows;                // E of CrfBuildScratch (kernels.h)
     CrfBuildScratch& sc = ws.scratch;
     want(cap6, false, &sc.keys_a, &sc.keys_b, &sc.vals_a, &sc.head, &sc.incl);
-    want(cap6 * 6, false, &sc.n1k, &sc.n2k);
+    want(cap6 * rows, false, &sc.n1k, &sc.n2k);
     want(1, true, &sc.range_err);
     sc.temp_bytes = crf_sort_temp_bytes(cap6);
     want(sc.temp_bytes, false, &sc.temp);
     // lattice value buffers: one row per lattice point, at most 6 (bilateral) / 3 (Gaussian) points per pixel;
     // crf_lattice_norm also uses va / vb as scalar scratch of one float per lattice point of the whole batch
-    ws.val_cap = std::max(value_pix * 6 * Kp * groups, cap6);
+    ws.val_cap = std::max(value_pix * rows * Kp * groups, cap6);
     want(ws.val_cap, false, &ws.va, &ws.vb);
     ws.valg_cap = value_pix * 3 * Kp * groups;
     want(ws.valg_cap, false, &ws.vga, &ws.vgb);
@@ -82,18 +105,52 @@ int crf_build(CrfWorkspace& ws, const PostDesc* d_desc, const PostDesc* h_desc, 
     return PNP_OK;
 }
 
+int crf_build_terms(CrfWorkspace& ws, const PostDesc* d_desc, const PostDesc* h_desc, int B, size_t total_pix, int maxHW, int T,
+                    const int* dims, const float* const* d_feat, int* range_term, hipStream_t s) {
+    *range_term = -1;
+    if (T < 1 || T > ws.max_terms) return PNP_ERR_ARG;
+    for (int t = 0; t < T; t++) {
+        if (dims[t] < 1 || dims[t] > ws.max_dims) return PNP_ERR_ARG;
+        CrfLattice& L = ws.tlat[t];
+        L.D1 = dims[t] + 1;
+        const size_t entries = total_pix * L.D1;
+        int range_err = 0;
+        if (int r = crf_build_lattice_features(dims[t], L, d_desc, h_desc, d_feat[t], B, entries, maxHW, ws.scratch, &range_err, &ws.tlat_points[t], s))
+            return r;
+        if (int r = crf_lattice_norm(L, d_desc, B, maxHW, entries, ws.va, ws.vb, ws.tnorm[t], s)) return r;
+        if (range_err) {
+            (void)hipMemsetAsync(ws.scratch.range_err, 0, sizeof(int), s);
+            *range_term = t;
+            return PNP_ERR_ARG;
+        }
+    }
+    return PNP_OK;
+}
+
 int crf_meanfield_filter(const CrfWorkspace& ws, const CrfSpan& v, const float** rg, const float** rb, hipStream_t s) {
     if (int r = crf_filter(ws.lat[0], v.d_desc, v.img0, v.nimg, ws.Q, ws.vga, ws.vgb, rg, v.kp_max, s)) return r;
     return crf_filter(ws.lat[1], v.d_desc, v.img0, v.nimg, ws.Q, ws.va, ws.vb, rb, v.kp_max, s);
 }
 
 int crf_meanfield(const CrfWorkspace& ws, const CrfSpan& v, bool start, int n, float pos_w, float bi_w, const float* MgT, const float* MbT,
-                  int ldm, hipStream_t s, const CrfLabelOut& labels) {
+                  int ldm, hipStream_t s, const CrfLabelOut& labels, const CrfTermsRun* terms) {
     if (start)
         if (int r = crf_update(ws.lat[0], ws.lat[1], v.d_desc, v.img0, v.nimg, ws.vga, ws.va, ws.norm[0], ws.norm[1], ws.unary, ws.Q, 0.f, 0.f,
                                0, v.kp_max, v.groups, s, n == 0 ? labels : CrfLabelOut()))
             return r;
     for (int it = 0; it < n; it++) {
+        if (terms) {
+            for (int t = 0; t < terms->T; t++) {
+                const bool first = t == 0, last = t == terms->T - 1;
+                const float* val = nullptr;
+                if (int r = crf_filter(ws.tlat[t], terms->d_desc[t], v.img0, v.nimg, ws.Q, ws.va, ws.vb, &val, v.kp_max, s)) return r;
+                if (int r = crf_term_update(ws.tlat[t], terms->d_desc[t], v.img0, v.nimg, val, ws.tnorm[t], first ? ws.unary : ws.logit, first,
+                                            last ? ws.Q : ws.logit, last, terms->w[t], terms->wvec[t], terms->MT[t], terms->ldm, v.kp_max, s,
+                                            last && it == n - 1 ? labels : CrfLabelOut()))
+                    return r;
+            }
+            continue;
+        }
         const float *rg = nullptr, *rb = nullptr;
         if (int r = crf_meanfield_filter(ws, v, &rg, &rb, s)) return r;
         const CrfLabelOut out = it == n - 1 ? labels : CrfLabelOut();

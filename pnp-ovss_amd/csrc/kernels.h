@@ -11,7 +11,7 @@ namespace pnp {
 // Per-image descriptor of the post-process batch (images may have different original sizes and
 // class counts).  `off` = offset (in floats) of this image's K*H*W block inside the flat map /
 // unary / Q / tmp buffers; `pix0` = global index of its first pixel; `voff[t]` = offset of its
-// lattice value block (t = 0 Gaussian, 1 bilateral).
+// lattice value block (t = 0 Gaussian, 1 bilateral; the descriptors of a feature term carry that term's offset in both).
 struct PostDesc {
     int H, W, K, C, has_bg, pix0;
     int Kp;            // row stride of the CRF arrays in floats: G groups of Kg back to back, zero-padded to a multiple of 4
@@ -42,7 +42,7 @@ struct alignas(16) CrfNbr8 {
 // One permutohedral lattice type for a whole image batch (device pointers).
 struct CrfLattice {
     int D1;            // d + 1
-    int which;         // 0 Gaussian, 1 bilateral
+    int which;         // 0 Gaussian, 1 bilateral: the PostDesc::voff its value rows use (a feature term: 1, both voff equal)
     size_t cap;        // capacity (entries) = stride of the neighbour tables
     float* bary;       // [entries] barycentric weight per (pixel, vertex)
     uint32_t* vals;    // [entries] sorted (pixel, vertex) indices = contributor lists
@@ -153,7 +153,8 @@ int radix_sort_pairs(uint64_t* keys_in, uint64_t* keys_out, uint32_t* vals_in, u
 int device_scan_i32(const int* in, int* out, size_t n, bool inclusive, void* temp, size_t temp_bytes, hipStream_t s);
 size_t crf_sort_temp_bytes(size_t max_entries);
 // Device scratch of crf_build_lattice, sized once for the largest build: E = (pixels of a batch) x 6 entries of the bilateral
-// lattice (the Gaussian one has 3 per pixel), M <= E lattice points.  The build reuses the arrays as it goes:
+// lattice (the Gaussian one has 3 per pixel; a workspace with feature terms: x max(6, max_dims + 1), and n1k / n2k that many rows
+// of stride E), M <= E lattice points.  The build reuses the arrays as it goes:
 //   keys_a  [E] u64   packed (pixel, vertex) keys, the first sort's input; then the second sort's input keys [M];
 //                     then, as int [M], the contributor-list lengths
 //   keys_b  [E] u64   the first sort's output; then the second sort's output keys [M]; then, as u32 [E], the moved contributor list
@@ -175,6 +176,13 @@ struct CrfBuildScratch {
 int crf_build_lattice(int D, const CrfLattice& L, const PostDesc* d_imgs, const PostDesc* h_imgs, const uint8_t* d_rgb, const float sxy[2],
                       const float srgb[3], int B, size_t ent_total, int max_pixels, const CrfBuildScratch& scratch, int* h_range_err, int* h_points,
                       hipStream_t s);
+// The same build on D = 1 .. 6 feature planes the caller brings (pnp_crf_set_batch_terms): d_feat holds image b's (D, H*W) block
+// at float offset pix0 * D, the features already divided by their widths.  The flag is raised for a coordinate beyond
+// crf_feature_key_limit(D) -- what the key's min(16, 64 / D) bits per coordinate hold, 505 at D = 6 -- and for a non-finite
+// feature.  Scratch for E = (pixels of the batch) x (D + 1) entries, L.cap >= E.
+int crf_build_lattice_features(int D, const CrfLattice& L, const PostDesc* d_imgs, const PostDesc* h_imgs, const float* d_feat, int B,
+                               size_t ent_total, int max_pixels, const CrfBuildScratch& scratch, int* h_range_err, int* h_points, hipStream_t s);
+int crf_feature_key_limit(int D);
 int crf_lattice_norm(const CrfLattice& L, const PostDesc* d_imgs, int B, int max_pixels, size_t ent_total, float* va, float* vb,
                      float* norm_out, hipStream_t s);
 int crf_filter(const CrfLattice& L, const PostDesc* d_imgs, int img0, int nimg, const float* Q,
@@ -198,5 +206,13 @@ int crf_compat_tile_pixels(int max_kp, bool kl);
 int crf_update_compat(const CrfLattice& Lg, const CrfLattice& Lb, const PostDesc* d_imgs, int img0, int nimg, const float* vg,
                       const float* vb, const float* norm_g, const float* norm_b, const float* unary, float* Q, const float* MgT,
                       const float* MbT, int ldm, int max_kp, hipStream_t s, const CrfLabelOut& labels, double* kl_pix);
+// One pairwise term of a T-term update over caller-supplied features: row = (first ? -U : row) + compat(msg_t), and after the
+// last term Q = softmax(row) with the label output.  L: the term's lattice (D1 = 2 .. 7); d_imgs: the term's descriptors
+// (voff[0] = its value rows); val: what crf_filter left; base: unary rows (first) or logit rows; out: logit rows, or Q (last);
+// base == out is allowed.  MT: K x K message weights transposed as crf_update_compat takes them, else wvec: one weight per
+// label (ldm floats, zero beyond K), else the scalar w.
+int crf_term_update(const CrfLattice& L, const PostDesc* d_imgs, int img0, int nimg, const float* val, const float* norm, const float* base,
+                    bool first, float* out, bool last, float w, const float* wvec, const float* MT, int ldm, int max_kp, hipStream_t s,
+                    const CrfLabelOut& labels);
 
 }  // namespace pnp

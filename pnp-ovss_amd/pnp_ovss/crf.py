@@ -20,8 +20,22 @@ Potts weight w being M = w I); and stepwise inference with the KL divergence:
     labels, q = solver.read()
 
 `shims/general/pydensecrf` offers these under pydensecrf's names (a package of its own: `shims/pydensecrf` keeps refusing them).
+
+Any number of pairwise terms over features of your own (pydensecrf's addPairwiseEnergy): grey-scale or multi-channel images, a
+depth channel in the bilateral kernel, two bilateral scales, 1-D signals:
+
+    solver = crf.FeatureCRF(max_batch=1, max_total_pixels=H * W, max_pixels_per_image=H * W, max_labels=K, max_terms=3)
+    terms = [crf.Term(crf.position_features([(H, W)], 3), 3.0),
+             crf.Term(crf.image_features([rgb], 50, 5), 5.0),
+             crf.Term(crf.image_features([np.dstack([rgb, depth])], 80, (13, 13, 13, 0.1)), M)]      # (K, K) message weights
+    labels, q = solver.run([U], terms, iters=10)
+
+Features arrive divided by their kernel widths and are used as given; a term has 1 .. 6 of them (max_dims) and the solver is
+sized for the worst case of d + 1 lattice points per pixel -- that is the contract.  [position_features, image_features of an
+RGB image] with scalar weights is DenseCRF.run bit for bit.  The KL divergence is not available for feature terms.
 """
 import ctypes as C
+import numbers
 
 import numpy as np
 import torch
@@ -105,6 +119,24 @@ def compat_values(compat, name):
     raise ValueError(f"{name} is None, (K,) or (K, K) with 2 <= K <= {MAX_LABELS}, not shape {a.shape}")
 
 
+def message_weights(compat, nlabels, where):
+    """pydensecrf's compat -> (Potts weight, None) for a number, (None, (K, K) float32 message weights) for a vector
+    (diag(-v)) or a matrix (-0.5 * (m + m^T)).  The one place where the pydensecrf shims (shims/general, shims/nd) turn a
+    label-cost compat into this module's message weights: densecrf's PottsCompatibility / DiagonalCompatibility /
+    MatrixCompatibility as this project reads them, pinned by nothing the reference holds (shims/general/pydensecrf/densecrf.py)."""
+    if isinstance(compat, numbers.Real) and not isinstance(compat, bool):
+        return float(compat), None
+    a = np.asarray(compat)
+    if a.dtype.kind not in "fiu":
+        raise ValueError(f"{where}: compat is a number or a numeric array, not {a.dtype}")
+    a = a.astype(np.float32)
+    if a.shape == (nlabels,):
+        return None, np.ascontiguousarray(np.diag(-a))
+    if a.shape == (nlabels, nlabels):
+        return None, np.ascontiguousarray((-0.5 * (a + a.T)).astype(np.float32))
+    raise ValueError(f"{where}: compat is a number, ({nlabels},) or ({nlabels}, {nlabels}), not shape {a.shape}")
+
+
 def check_compat_labels(compat_k, labels, name):
     """A vector or matrix compatibility for compat_k labels needs that many labels in every image of the batch."""
     if compat_k and any(int(k) != compat_k for k in labels):
@@ -118,26 +150,39 @@ def _raise(lib, h, r, what):
     raise (ValueError if r == -22 else RuntimeError)(f"{what} failed ({r}): {msg}")
 
 
-class DenseCRF:
-    """One pnp_crf solver: owns the device workspace for batches up to the given bounds."""
+def _check_bounds(max_batch, max_total_pixels, max_pixels_per_image, max_labels):
+    if not (1 <= int(max_batch) <= MAX_BATCH and 2 <= int(max_labels) <= MAX_LABELS and
+            1 <= int(max_pixels_per_image) <= int(max_total_pixels)):
+        raise ValueError(f"bad bounds: at most {MAX_BATCH} images per batch, 2..{MAX_LABELS} labels, "
+                         f"max_pixels_per_image <= max_total_pixels")
+    return int(max_batch), int(max_total_pixels), int(max_pixels_per_image), int(max_labels)
 
-    def __init__(self, max_batch, max_total_pixels, max_pixels_per_image, max_labels, device=None):
+
+def _cat_device(parts, dtype, device):
+    """Arrays or tensors, flattened and concatenated, as one device tensor of `dtype` (a numpy dtype)."""
+    if all(isinstance(p, torch.Tensor) and p.is_cuda for p in parts):
+        flat = [p.to(device).contiguous().reshape(-1) for p in parts]
+        return torch.cat(flat) if len(flat) > 1 else flat[0]
+    host = [np.ascontiguousarray(p.cpu().numpy() if isinstance(p, torch.Tensor) else p, dtype=dtype).reshape(-1) for p in parts]
+    return torch.from_numpy(np.concatenate(host)).to(device)
+
+
+class _Solver:
+    """What DenseCRF and FeatureCRF share: the pnp_crf handle, its bounds, and the outputs of the batch that is set."""
+
+    def _create(self, what, device, bounds, create, *more):
         if not torch.cuda.is_available():
-            raise RuntimeError("pnp_ovss.crf.DenseCRF needs a HIP device (no CPU fallback)")
-        if not (1 <= int(max_batch) <= MAX_BATCH and 2 <= int(max_labels) <= MAX_LABELS and
-                1 <= int(max_pixels_per_image) <= int(max_total_pixels)):
-            raise ValueError(f"bad bounds: at most {MAX_BATCH} images per batch, 2..{MAX_LABELS} labels, "
-                             f"max_pixels_per_image <= max_total_pixels")
+            raise RuntimeError(f"pnp_ovss.crf.{what} needs a HIP device (no CPU fallback)")
         self.lib = hip.load_library()
         dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self.device = torch.device("cuda", dev.index if dev.index is not None else torch.cuda.current_device())
-        self.bounds = (int(max_batch), int(max_total_pixels), int(max_pixels_per_image), int(max_labels))
+        self.bounds = bounds
         self.h = C.c_void_p()
-        r = self.lib.pnp_crf_create(self.device.index, *self.bounds, C.byref(self.h))
+        r = getattr(self.lib, create)(self.device.index, *self.bounds, *more, C.byref(self.h))
         if r != 0:
-            msg = self.lib.pnp_crf_last_error(self.h).decode() if self.h else "no device"
+            msg = self.lib.pnp_crf_last_error(self.h).decode() if self.h else "bad bounds, or no device"
             self.close()
-            raise RuntimeError(f"pnp_crf_create failed ({r}): {msg}")
+            raise RuntimeError(f"{create} failed ({r}): {msg}")
 
     def close(self):
         if getattr(self, "h", None):
@@ -158,6 +203,45 @@ class DenseCRF:
         return (plan["max_batch"] <= b[0] and plan["max_total_pixels"] <= b[1] and plan["max_pixels_per_image"] <= b[2] and
                 plan["max_labels"] <= b[3])
 
+    def batch_token(self):
+        """Changes with every set_batch: whoever holds a stepwise inference can tell that the batch is no longer theirs."""
+        return getattr(self, "_batches", 0)
+
+    def _outputs(self, what, want_q, want_labels):
+        if getattr(self, "_plan", None) is None:
+            raise RuntimeError(f"pnp_ovss.crf.{type(self).__name__}.{what}: no batch is set (call set_batch or run first)")
+        plan = self._plan[0]
+        d_lab = torch.empty(plan["max_total_pixels"], dtype=torch.uint8, device=self.device) if want_labels else None
+        d_q = torch.empty(plan["total_unary"], dtype=torch.float32, device=self.device) if want_q else None
+        return d_q, d_lab
+
+    def read(self, want_q=True, want_labels=True):
+        """The current marginals and their argmax -> (labels, q) as run() returns them (None where not wanted)."""
+        d_q, d_lab = self._outputs("read", want_q, want_labels)
+        with torch.cuda.device(self.device):
+            r = self.lib.pnp_crf_read(self.h, hip._ptr(d_q), hip._ptr(d_lab), hip._stream())
+        if r != 0:
+            _raise(self.lib, self.h, r, "pnp_crf_read")
+        return self._split(d_q, d_lab)
+
+    def _split(self, d_q, d_lab):
+        plan, sizes, labels = self._plan
+        want_q, want_labels = d_q is not None, d_lab is not None
+        out_l, out_q = [] if want_labels else None, [] if want_q else None
+        for (h, w), k, p0, off in zip(sizes, labels, plan["pix0"], plan["off"]):
+            if want_labels:
+                out_l.append(d_lab[p0:p0 + h * w].view(h, w))
+            if want_q:
+                out_q.append(d_q[off:off + k * h * w].view(k, h, w))
+        return out_l, out_q
+
+
+class DenseCRF(_Solver):
+    """One pnp_crf solver: owns the device workspace for batches up to the given bounds."""
+
+    def __init__(self, max_batch, max_total_pixels, max_pixels_per_image, max_labels, device=None):
+        self._create("DenseCRF", device, _check_bounds(max_batch, max_total_pixels, max_pixels_per_image, max_labels), "pnp_crf_create")
+
     def _gather(self, unaries, images):
         """-> (device unary floats, device rgb bytes, sizes, labels), both concatenated in batch order."""
         if len(unaries) != len(images) or not len(images):
@@ -175,14 +259,7 @@ class DenseCRF:
             labels.append(int(u.shape[0]))
             us.append(u)
             ims.append(im)
-
-        def cat(parts, dtype):
-            if all(isinstance(p, torch.Tensor) and p.is_cuda for p in parts):
-                flat = [p.to(self.device).contiguous().reshape(-1) for p in parts]
-                return torch.cat(flat) if len(flat) > 1 else flat[0]
-            host = [np.ascontiguousarray(p.cpu().numpy() if isinstance(p, torch.Tensor) else p, dtype=dtype).reshape(-1) for p in parts]
-            return torch.from_numpy(np.concatenate(host)).to(self.device)
-        return cat(us, np.float32), cat(ims, np.uint8), sizes, labels
+        return _cat_device(us, np.float32, self.device), _cat_device(ims, np.uint8, self.device), sizes, labels
 
     def run(self, unaries, images, iters=10, pos_w=7.0, pos_xy=3.0, bi_w=10.0, bi_xy=50.0, bi_rgb=5.0, want_q=True,
             pos_compat=None, bi_compat=None):
@@ -231,18 +308,6 @@ class DenseCRF:
         self._plan = (plan, [(int(h), int(w)) for h, w in sizes], [int(k) for k in labels])
         self._batches = self.batch_token() + 1
 
-    def batch_token(self):
-        """Changes with every set_batch: whoever holds a stepwise inference can tell that the batch is no longer theirs."""
-        return getattr(self, "_batches", 0)
-
-    def _outputs(self, what, want_q, want_labels):
-        if getattr(self, "_plan", None) is None:
-            raise RuntimeError(f"pnp_ovss.crf.DenseCRF.{what}: no batch is set (call set_batch or run first)")
-        plan = self._plan[0]
-        d_lab = torch.empty(plan["max_total_pixels"], dtype=torch.uint8, device=self.device) if want_labels else None
-        d_q = torch.empty(plan["total_unary"], dtype=torch.float32, device=self.device) if want_q else None
-        return d_q, d_lab
-
     def infer(self, iters=10, pos_w=7.0, bi_w=10.0, want_q=True, want_labels=True):
         """pnp_crf_infer on the batch of the last set_batch -> (labels, q) as run() returns them (None where not wanted).
         pos_w / bi_w are remembered for step() and kl()."""
@@ -275,15 +340,6 @@ class DenseCRF:
         if r != 0:
             _raise(self.lib, self.h, r, "pnp_crf_step")
 
-    def read(self, want_q=True, want_labels=True):
-        """The current marginals and their argmax -> (labels, q) as run() returns them (None where not wanted)."""
-        d_q, d_lab = self._outputs("read", want_q, want_labels)
-        with torch.cuda.device(self.device):
-            r = self.lib.pnp_crf_read(self.h, hip._ptr(d_q), hip._ptr(d_lab), hip._stream())
-        if r != 0:
-            _raise(self.lib, self.h, r, "pnp_crf_read")
-        return self._split(d_q, d_lab)
-
     def kl(self):
         """KL divergence of the current marginals, one float per image (pnp_crf_kl: densecrf's klDivergence as this project
         reads it).  One filter pass per term; synchronises."""
@@ -296,16 +352,256 @@ class DenseCRF:
             _raise(self.lib, self.h, r, "pnp_crf_kl")
         return [float(v) for v in out]
 
-    def _split(self, d_q, d_lab):
-        plan, sizes, labels = self._plan
-        want_q, want_labels = d_q is not None, d_lab is not None
-        out_l, out_q = [] if want_labels else None, [] if want_q else None
-        for (h, w), k, p0, off in zip(sizes, labels, plan["pix0"], plan["off"]):
-            if want_labels:
-                out_l.append(d_lab[p0:p0 + h * w].view(h, w))
-            if want_q:
-                out_q.append(d_q[off:off + k * h * w].view(k, h, w))
-        return out_l, out_q
+
+MAX_TERMS = 8            # PNP_CRF_MAX_TERMS
+MAX_DIMS = 6             # PNP_CRF_MAX_DIMS: feature axes of one term
+
+
+def plan_terms(sizes, labels, dims):
+    """plan_batch for feature terms -- host arithmetic only.  dims: feature axes of every term.  Adds, per term (lists over the
+    terms): tvoff -- per image, the float offset of its lattice value rows in the value buffers the terms take turns in (d + 1
+    rows of Kp floats per pixel at most); foff -- per image, the float offset of its (d, H*W) block in the term's concatenated
+    features; total_features -- floats of that concatenation.  value_floats: what the widest term needs of a value buffer.
+    And the further bounds a solver needs: max_terms, max_dims."""
+    dims = [int(d) for d in dims]
+    if not 1 <= len(dims) <= MAX_TERMS:
+        raise ValueError(f"{len(dims)} terms: 1..{MAX_TERMS}")
+    for t, d in enumerate(dims):
+        if not 1 <= d <= MAX_DIMS:
+            raise ValueError(f"term {t} has {d} feature axes: 1..{MAX_DIMS}")
+    plan = plan_batch(sizes, labels)
+    pix = [int(h) * int(w) for h, w in sizes]
+    plan.update(tvoff=[], foff=[], total_features=[])
+    for d in dims:
+        voff, rows = [], 0
+        for n, kp in zip(pix, plan["Kp"]):
+            voff.append(rows)
+            rows += (d + 1) * n * kp
+        plan["tvoff"].append(voff)
+        plan["foff"].append([d * p0 for p0 in plan["pix0"]])
+        plan["total_features"].append(d * plan["max_total_pixels"])
+    plan.update(value_floats=max((d + 1) * sum(n * kp for n, kp in zip(pix, plan["Kp"])) for d in dims),
+                max_terms=len(dims), max_dims=max(dims))
+    return plan
+
+
+def _f32_quotient(a, width):
+    return np.asarray(a, dtype=np.float32) / np.float32(width)            # IEEE float32 division of float32 operands
+
+
+def position_features(sizes, sxy):
+    """Per image of sizes [(H, W)] the (2, H, W) float32 features x / sx, y / sy; sxy: a number or (sx, sy)."""
+    sx, sy = _widths(sxy, 2, "sxy")
+    out = []
+    for h, w in sizes:
+        yy, xx = np.mgrid[0:int(h), 0:int(w)]
+        out.append(np.stack([_f32_quotient(xx, sx), _f32_quotient(yy, sy)]))
+    return out
+
+
+def image_features(images, sxy, schan):
+    """Per image -- (H, W) or (H, W, C) of any real dtype, C + 2 <= 6 -- the (2 + C, H, W) float32 features x / sx, y / sy,
+    channel_c / schan_c; sxy: a number or (sx, sy); schan: a number or one width per channel."""
+    out = []
+    for im in images:
+        a = im.detach().cpu().numpy() if isinstance(im, torch.Tensor) else np.asarray(im)
+        if a.ndim == 2:
+            a = a[:, :, None]
+        if a.ndim != 3 or not (np.issubdtype(a.dtype, np.floating) or np.issubdtype(a.dtype, np.integer)):
+            raise ValueError(f"images are (H, W) or (H, W, C) of a real dtype, not {a.shape} {a.dtype}")
+        if a.shape[2] + 2 > MAX_DIMS:
+            raise ValueError(f"{a.shape[2]} channels and two positions are {a.shape[2] + 2} feature axes: at most {MAX_DIMS}")
+        sc = _widths(schan, a.shape[2], "schan")
+        pos = position_features([a.shape[:2]], sxy)[0]
+        out.append(np.concatenate([pos, np.stack([_f32_quotient(a[:, :, c], sc[c]) for c in range(a.shape[2])])]))
+    return out
+
+
+class Term:
+    """One pairwise term: features -- per image one (d, H, W) or (d, H*W) float32 array or device tensor, already divided by the
+    kernel widths -- and a compatibility: a number (the Potts weight), or (K,) / (K, K) float32 message weights, used as given
+    (compat_values)."""
+
+    def __init__(self, features, compat=1.0):
+        self.features = list(features)
+        if not self.features:
+            raise ValueError("a term has one feature array per image, at least one image")
+        for f in self.features:
+            if not hasattr(f, "dtype") or f.dtype not in (np.float32, torch.float32):
+                raise ValueError(f"features are float32, not {getattr(f, 'dtype', type(f).__name__)}")
+            if f.ndim not in (2, 3):
+                raise ValueError(f"features are (d, H, W) or (d, H*W), not {tuple(f.shape)}")
+        self.dims = int(self.features[0].shape[0])
+        if any(int(f.shape[0]) != self.dims for f in self.features):
+            raise ValueError(f"a term has the same feature axes in every image, not {[int(f.shape[0]) for f in self.features]}")
+        if not 1 <= self.dims <= MAX_DIMS:
+            raise ValueError(f"a term has 1..{MAX_DIMS} feature axes, not {self.dims}")
+        if isinstance(compat, (int, float, np.integer, np.floating)) or (hasattr(compat, "ndim") and compat.ndim == 0):
+            self.weight, self.compat = float(compat), None
+        else:
+            self.weight, self.compat = 0.0, compat
+        self.kind, self.values, self.K = compat_values(self.compat, "compat")
+
+
+class FeatureCRF(_Solver):
+    """A pnp_crf solver of pnp_crf_create_terms: up to max_terms pairwise terms of up to max_dims features each, sized for the
+    worst case of max_dims + 1 lattice points per pixel and term."""
+
+    def __init__(self, max_batch, max_total_pixels, max_pixels_per_image, max_labels, max_terms=4, max_dims=6, device=None):
+        if not (1 <= int(max_terms) <= MAX_TERMS and 1 <= int(max_dims) <= MAX_DIMS):
+            raise ValueError(f"bad bounds: 1..{MAX_TERMS} terms of 1..{MAX_DIMS} feature axes")
+        self.max_terms, self.max_dims = int(max_terms), int(max_dims)
+        self._create("FeatureCRF", device, _check_bounds(max_batch, max_total_pixels, max_pixels_per_image, max_labels),
+                     "pnp_crf_create_terms", self.max_terms, self.max_dims)
+
+    def fits(self, plan):
+        return _Solver.fits(self, plan) and plan["max_terms"] <= self.max_terms and plan["max_dims"] <= self.max_dims
+
+    def _check_terms(self, terms):
+        terms = list(terms)
+        if not 1 <= len(terms) <= self.max_terms:
+            raise ValueError(f"{len(terms)} terms: the solver holds 1..{self.max_terms}")
+        for t, term in enumerate(terms):
+            if not isinstance(term, Term):
+                raise ValueError(f"term {t} is a pnp_ovss.crf.Term, not {type(term).__name__}")
+            if term.dims > self.max_dims:
+                raise ValueError(f"term {t} has {term.dims} feature axes: the solver holds 1..{self.max_dims}")
+        return terms
+
+    def _gather(self, unaries, terms):
+        """-> (device unary floats, per term the device feature floats, sizes, labels), concatenated in batch order."""
+        if not len(unaries):
+            raise ValueError("one unary array per image, at least one image")
+        sizes, labels = [], []
+        for i, u in enumerate(unaries):
+            if u.dtype not in (np.float32, torch.float32):
+                raise ValueError(f"unary energies are float32, not {u.dtype}")
+            if u.ndim not in (2, 3):
+                raise ValueError(f"unary energies are (K, H, W) or (K, H*W), not {tuple(u.shape)}")
+            shaped = [a for a in [u] + [t.features[i] for t in terms if i < len(t.features)] if a.ndim == 3]
+            size = (int(shaped[0].shape[1]), int(shaped[0].shape[2])) if shaped else (1, int(u.shape[1]))      # a 1-D signal: one row
+            sizes.append(size)
+            labels.append(int(u.shape[0]))
+        for t, term in enumerate(terms):
+            if len(term.features) != len(sizes):
+                raise ValueError(f"term {t} has features for {len(term.features)} images, the batch has {len(sizes)}")
+            for i, (f, (h, w)) in enumerate(zip(term.features, sizes)):
+                if not (tuple(f.shape[1:]) == (h, w) or (f.ndim == 2 and int(f.shape[1]) == h * w)):
+                    raise ValueError(f"term {t}, image {i}: features are ({term.dims}, {h}, {w}) or ({term.dims}, {h * w}), not {tuple(f.shape)}")
+        for i, (u, (h, w)) in enumerate(zip(unaries, sizes)):
+            if not (tuple(u.shape[1:]) == (h, w) or (u.ndim == 2 and int(u.shape[1]) == h * w)):
+                raise ValueError(f"image {i}: unary energies are (K, {h}, {w}) or (K, {h * w}), not {tuple(u.shape)}")
+        feats = [_cat_device(term.features, np.float32, self.device) for term in terms]
+        return _cat_device(list(unaries), np.float32, self.device), feats, sizes, labels
+
+    def run(self, unaries, terms, iters=10, want_q=True):
+        """unaries: per image (K, H, W) or (K, H*W) float32 energies; terms: Term objects, in the order their messages are
+        added.  The terms' compatibilities replace whatever the solver held.  Returns (labels, q) as DenseCRF.run does."""
+        terms = self._check_terms(terms)
+        d_unary, feats, sizes, labels = self._gather(unaries, terms)
+        for t, term in enumerate(terms):
+            check_compat_labels(term.K, labels, f"term {t}'s compat")
+        self.set_batch(d_unary, feats, [term.dims for term in terms], sizes, labels)
+        self.set_compat([term.compat for term in terms])
+        return self.infer(iters=iters, weights=[term.weight for term in terms], want_q=want_q)
+
+    def set_compat(self, compats):
+        """pnp_crf_set_term_compat for terms 0 .. len(compats) - 1: None -> scalar (the weight of the call), (K,) -> diag(v),
+        (K, K) -> the matrix; message weights, used as given.  Holds until changed, across batches."""
+        for term, compat in enumerate(compats):
+            kind, vals, k = compat_values(compat, f"term {term}'s compat")
+            with torch.cuda.device(self.device):
+                r = self.lib.pnp_crf_set_term_compat(self.h, term, kind, _f32p(vals) if vals is not None else None, k)
+            if r != 0:
+                _raise(self.lib, self.h, r, "pnp_crf_set_term_compat")
+
+    def set_batch(self, d_unary, d_features, dims, sizes, labels):
+        """pnp_crf_set_batch_terms on concatenated device tensors: d_unary float32, the (K_b, H_b * W_b) blocks back to back;
+        d_features[t] float32, term t's (dims[t], H_b * W_b) blocks back to back.  Builds every lattice; synchronises."""
+        self._plan = None
+        plan = plan_terms(sizes, labels, dims)
+        if len(dims) > self.max_terms or plan["max_dims"] > self.max_dims:
+            raise ValueError(f"{len(dims)} terms of up to {plan['max_dims']} feature axes: the solver holds {self.max_terms} of {self.max_dims}")
+        if d_unary.dtype != torch.float32 or d_unary.numel() != plan["total_unary"]:
+            raise ValueError("d_unary does not match the sizes and label counts")
+        if len(d_features) != len(dims) or any(f.dtype != torch.float32 or f.numel() != n for f, n in zip(d_features, plan["total_features"])):
+            raise ValueError("d_features do not match the sizes and the terms' feature axes")
+        H = np.array([s[0] for s in sizes], dtype=np.int32)
+        W = np.array([s[1] for s in sizes], dtype=np.int32)
+        K = np.array(labels, dtype=np.int32)
+        batch = hip.PnpCrfBatch(len(sizes), hip._i32p(H), hip._i32p(W), hip._i32p(K), None, hip._ptr(d_unary))
+        arr = (hip.PnpCrfTerm * len(dims))(*[hip.PnpCrfTerm(int(d), hip._ptr(f)) for d, f in zip(dims, d_features)])
+        with torch.cuda.device(self.device):
+            r = self.lib.pnp_crf_set_batch_terms(self.h, C.byref(batch), len(dims), arr, hip._stream())
+        if r != 0:
+            _raise(self.lib, self.h, r, "pnp_crf_set_batch_terms")
+        self._plan = (plan, [(int(h), int(w)) for h, w in sizes], [int(k) for k in labels])
+        self._batches = self.batch_token() + 1
+        self._w = [1.0] * len(dims)
+
+    def _weights(self, weights):
+        n = len(self._plan[0]["tvoff"])
+        w = self._w if weights is None else [float(x) for x in weights]
+        if len(w) != n:
+            raise ValueError(f"{len(w)} weights for {n} terms")
+        self._w = w
+        return (C.c_float * n)(*w)
+
+    def infer(self, iters=10, weights=None, want_q=True, want_labels=True):
+        """pnp_crf_infer_terms on the batch of the last set_batch -> (labels, q).  weights: one per term, the weight of a term
+        left scalar (default: those of the last call, 1 at first); remembered for step()."""
+        d_q, d_lab = self._outputs("infer", want_q, want_labels)
+        w = self._weights(weights)
+        with torch.cuda.device(self.device):
+            r = self.lib.pnp_crf_infer_terms(self.h, int(iters), w, hip._ptr(d_q), hip._ptr(d_lab), hip._stream())
+        if r != 0:
+            _raise(self.lib, self.h, r, "pnp_crf_infer_terms")
+        return self._split(d_q, d_lab)
+
+    def start(self, weights=None):
+        """Q = softmax(-U) on the batch of the last set_batch; weights: as infer()'s, for the steps that follow."""
+        self._outputs("start", False, False)
+        self._weights(weights)
+        with torch.cuda.device(self.device):
+            r = self.lib.pnp_crf_start(self.h, hip._stream())
+        if r != 0:
+            _raise(self.lib, self.h, r, "pnp_crf_start")
+
+    def step(self, n=1):
+        """n more mean-field updates from the current marginals: start(); step(a); step(b) leaves what infer(a + b) leaves."""
+        self._outputs("step", False, False)
+        with torch.cuda.device(self.device):
+            r = self.lib.pnp_crf_step_terms(self.h, int(n), self._weights(None), hip._stream())
+        if r != 0:
+            _raise(self.lib, self.h, r, "pnp_crf_step_terms")
+
+    def lattice_points(self):
+        """Lattice points of every term over the whole batch of the last set_batch (at most d + 1 per pixel)."""
+        self._outputs("lattice_points", False, False)
+        return [int(self.lib.pnp_crf_lattice_points(self.h, t)) for t in range(len(self._plan[0]["tvoff"]))]
+
+    def kl(self):
+        raise NotImplementedError("pnp_ovss.crf.FeatureCRF.kl: the KL divergence is not available for feature terms (use DenseCRF)")
+
+
+_FEATURE_SOLVERS = {}    # device index -> the solver feature_solver() hands out there
+
+
+def feature_solver(plan, device_index=None):
+    """A module-level FeatureCRF of the device that holds batches of `plan` (plan_terms): re-created larger when a call needs
+    more.  What shims/nd/pydensecrf runs on."""
+    if not torch.cuda.is_available():
+        raise RuntimeError("pnp_ovss.crf.feature_solver needs a HIP device (no CPU fallback)")
+    idx = torch.cuda.current_device() if device_index is None else int(device_index)
+    solver = _FEATURE_SOLVERS.get(idx)
+    if solver is None or not solver.fits(plan):
+        old = solver.bounds + (solver.max_terms, solver.max_dims) if solver is not None else (1, 0, 0, 2, 1, 1)
+        if solver is not None:
+            solver.close()
+        grown = [max(o, plan[k]) for o, k in zip(old, ("max_batch", "max_total_pixels", "max_pixels_per_image", "max_labels",
+                                                       "max_terms", "max_dims"))]
+        solver = _FEATURE_SOLVERS[idx] = FeatureCRF(*grown, device=torch.device("cuda", idx))
+    return solver
 
 
 _SOLVERS = {}            # device index -> the solver densecrf() uses there

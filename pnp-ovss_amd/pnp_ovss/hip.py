@@ -40,6 +40,10 @@ class PnpCrfBatch(C.Structure):
                 ("d_rgb", C.c_void_p), ("d_unary", C.c_void_p)]
 
 
+class PnpCrfTerm(C.Structure):
+    _fields_ = [("dims", C.c_int32), ("d_features", C.c_void_p)]
+
+
 _lib = None
 
 
@@ -132,6 +136,12 @@ def load_library():
         "pnp_crf_step": (i32, [vp, i32, f32, f32, vp]),
         "pnp_crf_read": (i32, [vp, vp, vp, vp]),
         "pnp_crf_kl": (i32, [vp, f32, f32, C.POINTER(C.c_double), vp]),
+        "pnp_crf_create_terms": (i32, [i32, i32, i64, i32, i32, i32, i32, C.POINTER(vp)]),
+        "pnp_crf_set_batch_terms": (i32, [vp, C.POINTER(PnpCrfBatch), i32, C.POINTER(PnpCrfTerm), vp]),
+        "pnp_crf_set_term_compat": (i32, [vp, i32, i32, C.POINTER(f32), i32]),
+        "pnp_crf_infer_terms": (i32, [vp, i32, C.POINTER(f32), vp, vp, vp]),
+        "pnp_crf_step_terms": (i32, [vp, i32, C.POINTER(f32), vp]),
+        "pnp_crf_lattice_points": (i64, [vp, i32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)          # AttributeError here = ABI drift, fail loudly
@@ -155,7 +165,8 @@ EXPORTED = ["pnp_create", "pnp_create_shared", "pnp_destroy", "pnp_last_error", 
             "pnp_op_gemm_args", "pnp_overlay_labels", "pnp_jpeg_encode",
             "pnp_crf_create", "pnp_crf_destroy", "pnp_crf_allocated_bytes", "pnp_crf_last_error", "pnp_crf_set_batch",
             "pnp_crf_infer", "pnp_crf_set_batch_aniso", "pnp_crf_set_compat", "pnp_crf_start", "pnp_crf_step", "pnp_crf_read",
-            "pnp_crf_kl"]
+            "pnp_crf_kl", "pnp_crf_create_terms", "pnp_crf_set_batch_terms", "pnp_crf_set_term_compat", "pnp_crf_infer_terms",
+            "pnp_crf_step_terms", "pnp_crf_lattice_points"]
 
 
 PROJ_NAMES = ("vision_proj.weight", "vision_proj.bias", "text_proj.weight", "text_proj.bias")      # the optional ITC projections

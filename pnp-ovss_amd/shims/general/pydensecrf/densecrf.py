@@ -7,7 +7,7 @@ a (K,) vector or a (K, K) matrix for compat; inference(n); map(n); the startInfe
 Still NotImplementedError, never approximated: a second Gaussian or bilateral term, addPairwiseEnergy / DenseCRF (arbitrary
 features), CONST_KERNEL / FULL_KERNEL, any normalisation but NORMALIZE_SYMMETRIC.
 
-compat is converted to pnp_ovss.crf's message weights HERE and nowhere else: a number w -> Potts weight w; a vector v ->
+compat is converted to pnp_ovss.crf's message weights in ONE place, pnp_ovss.crf.message_weights: a number w -> Potts weight w; a vector v ->
 diag(-v); a matrix m -> -0.5 * (m + m^T).  That is densecrf's PottsCompatibility / DiagonalCompatibility / MatrixCompatibility
 (a label-cost matrix, symmetrised, applied with a minus sign to the filtered marginals) AS REMEMBERED: neither pydensecrf nor
 densecrf's sources were at hand when this was written, and nothing in this repository pins the sign, the symmetrisation or the
@@ -28,18 +28,9 @@ _NORMS = {NO_NORMALIZATION: "NO_NORMALIZATION", NORMALIZE_BEFORE: "NORMALIZE_BEF
 
 def message_weights(compat, nlabels, where):
     """pydensecrf's compat -> (Potts weight, None) for a number, (None, (K, K) float32 message weights) for a vector
-    (diag(-v)) or a matrix (-0.5 * (m + m^T)): see the module docstring."""
-    if isinstance(compat, numbers.Real) and not isinstance(compat, bool):
-        return float(compat), None
-    a = np.asarray(compat)
-    if a.dtype.kind not in "fiu":
-        raise ValueError(f"{where}: compat is a number or a numeric array, not {a.dtype}")
-    a = a.astype(np.float32)
-    if a.shape == (nlabels,):
-        return None, np.ascontiguousarray(np.diag(-a))
-    if a.shape == (nlabels, nlabels):
-        return None, np.ascontiguousarray((-0.5 * (a + a.T)).astype(np.float32))
-    raise ValueError(f"{where}: compat is a number, ({nlabels},) or ({nlabels}, {nlabels}), not shape {a.shape}")
+    (diag(-v)) or a matrix (-0.5 * (m + m^T)): see the module docstring.  The conversion itself is pnp_ovss.crf's."""
+    from pnp_ovss import crf
+    return crf.message_weights(compat, nlabels, where)
 
 
 def _widths(v, n, name, where):

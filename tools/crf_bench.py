@@ -1,6 +1,7 @@
 """Time of the stand-alone DenseCRF (pnp_ovss.crf, the pydensecrf shim) on the bench-shaped problem (GPU box only).
 
     timeout 900 python tools/crf_bench.py [--images 35] [--size 375x500] [--labels 21] [--reps 30] [--out profiles/crf_standalone.json]
+    timeout 900 python tools/crf_bench.py --terms          # crf.FeatureCRF next to DenseCRF.run -> profiles/crf_terms.json
 
 Warm, then `reps` repetitions, device work between HIP events:
   one image through the shim      the host-to-host call (numpy in, numpy out: DenseCRF2D ... inference(10)), and separately the
@@ -114,6 +115,107 @@ def compat_matrix(torch, crf, a):
     return rec
 
 
+def terms_bench(torch, crf, a):
+    """--terms: the feature-terms solver (crf.FeatureCRF) next to DenseCRF.run.  (a) the xy + xy.rgb problem through both, the
+    two alternated repetition by repetition: set_batch and one mean-field step by device events, and whether the results are
+    the same bits; (b) the same plus a third term xy / 80 . rgb / 13 . depth / 0.1 (D = 6): lattice points per pixel, ms per
+    step, allocated bytes.  And the device time per launch of the iteration kernels inside the FeatureCRF steps."""
+    H, W = map(int, a.size.split("x"))
+    B, K = a.images, a.labels
+    rng = np.random.default_rng(0)
+    imgs = [synth_photo(rng, H, W) for _ in range(B)]
+    yy, xx = np.mgrid[0:H, 0:W].astype(np.float64)
+    depth = [(0.5 + 0.4 * np.sin(xx / 7.0) * np.cos(yy / 5.0) + rng.normal(0, 0.02, (H, W))).astype(np.float32) for _ in range(B)]
+    d_rgb = torch.from_numpy(np.concatenate([im.reshape(-1) for im in imgs])).cuda()
+    logits = torch.from_numpy(rng.normal(0, 2, (B, K, H * W)).astype(np.float32)).cuda()
+    d_unary = (-torch.log_softmax(logits, 1).clamp_min(float(np.log(1e-5)))).contiguous().reshape(-1)
+    del logits
+    sizes, labels = [(H, W)] * B, [K] * B
+
+    def dev(parts):
+        return torch.from_numpy(np.concatenate([p.reshape(-1) for p in parts])).cuda()
+    d_pos = dev(crf.position_features(sizes, 3.0))
+    d_bil = dev(crf.image_features(imgs, 50.0, 5.0))
+    d_dep = dev(crf.image_features([np.dstack([im.astype(np.float32), dp]) for im, dp in zip(imgs, depth)], 80.0, (13.0, 13.0, 13.0, 0.1)))
+    two = crf.DenseCRF(B, B * H * W, H * W, K)
+    feat = crf.FeatureCRF(B, B * H * W, H * W, K, max_terms=3, max_dims=6)
+    reps = a.reps
+
+    def set_two():
+        two.set_batch(d_unary, d_rgb, sizes, labels)
+
+    def set_feat2():
+        feat.set_batch(d_unary, [d_pos, d_bil], [2, 5], sizes, labels)
+
+    def set_feat3():
+        feat.set_batch(d_unary, [d_pos, d_bil, d_dep], [2, 5, 6], sizes, labels)
+
+    def alternated(f0, f1, n):
+        """medians of f0 / f1 by device events, one repetition of each in turn"""
+        t0, t1 = [], []
+        for _ in range(n):
+            t0.append(events_ms(torch, f0, 1))
+            t1.append(events_ms(torch, f1, 1))
+        return float(np.median(t0)), float(np.median(t1))
+    set_two()
+    set_feat2()
+    lab2, q2 = two.infer(10, 7.0, 10.0)
+    labf, qf = feat.infer(10, [7.0, 10.0])
+    same = all(bool(torch.equal(x, y)) for x, y in zip(q2, qf)) and all(bool(torch.equal(x, y)) for x, y in zip(lab2, labf))
+    del lab2, q2, labf, qf
+    set_two_ms, set_feat_ms = alternated(set_two, set_feat2, max(reps // 3, 3))
+    two.start(7.0, 10.0)
+    feat.start([7.0, 10.0])
+    two.step(2)
+    feat.step(2)                                                                 # warm
+    step_two, step_feat = alternated(lambda: two.step(10), lambda: feat.step(10), reps)
+    points2 = feat.lattice_points()
+
+    def kernel_us(fn, launches):
+        from torch.profiler import ProfilerActivity, profile
+        torch.cuda.synchronize()
+        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+            fn()
+            torch.cuda.synchronize()
+        fam = {"crf_term_update_kernel": [], "crf_splat_kernel": [], "crf_blur4x2_kernel": [], "crf_blur4_kernel": []}
+        for ev in prof.events():
+            if "DeviceType.CUDA" not in str(getattr(ev, "device_type", "")):
+                continue
+            us = getattr(ev, "device_time", None)
+            if us is None:
+                us = getattr(ev, "cuda_time", 0.0)
+            for name in fam:
+                if name in ev.name:
+                    fam[name].append(float(us))
+                    break
+        return {k: dict(launches_per_step=len(v) / launches, us_per_step=float(np.sum(v)) / launches) for k, v in fam.items() if v}
+    kern2 = kernel_us(lambda: feat.step(5), 5)
+    a_rec = dict(densecrf_set_batch_ms=set_two_ms, featurecrf_set_batch_ms=set_feat_ms, densecrf_step_ms=step_two / 10,
+                 featurecrf_step_ms=step_feat / 10, step_ratio=step_feat / step_two, bit_identical=bool(same),
+                 lattice_points_per_pixel=[p / (B * H * W) for p in points2], featurecrf_kernels_us_per_step=kern2)
+    set_feat3()
+    feat.start([7.0, 10.0, 5.0])
+    feat.step(2)
+    set3_ms = events_ms(torch, set_feat3, max(reps // 3, 3))
+    feat.start([7.0, 10.0, 5.0])
+    step3 = events_ms(torch, lambda: feat.step(10), reps)
+    b_rec = dict(set_batch_ms=set3_ms, step_ms=step3 / 10, lattice_points_per_pixel=[p / (B * H * W) for p in feat.lattice_points()],
+                 allocated_bytes=feat.allocated_bytes(), featurecrf_kernels_us_per_step=kernel_us(lambda: feat.step(5), 5))
+    rec = dict(images=B, size=[H, W], labels=K, reps=reps, two_terms=a_rec, three_terms=b_rec,
+               densecrf_allocated_bytes=two.allocated_bytes(),
+               note="two_terms: xy / 3 and xy / 50 . rgb / 5 with weights 7 / 10 through DenseCRF (the fused two-term update) and "
+                    "through FeatureCRF (one slice-and-accumulate launch per term, the softmax in the last), alternated repetition "
+                    "by repetition in one process; *_step_ms = device events over 10 mean-field steps / 10; set_batch = unary "
+                    "ingest + every lattice build with its read-back (DenseCRF keeps its Gaussian lattice after the first call, "
+                    "FeatureCRF caches none).  three_terms: plus xy / 80 . rgb / 13 . depth / 0.1 (D = 6), weight 5, depth = 0.5 + "
+                    "0.4 sin(x / 7) cos(y / 5) + N(0, 0.02).  featurecrf_kernels_us_per_step: device time of the iteration "
+                    "kernels per mean-field step as torch's profiler reports them.  Random unaries: the arithmetic does not "
+                    "depend on the values")
+    two.close()
+    feat.close()
+    return rec
+
+
 def main():
     import torch
     from oracle import pipeline_np as OP
@@ -129,7 +231,18 @@ def main():
     ap.add_argument("--compat", choices=["matrix"], default=None,
                     help="matrix: measure only the compatibility-matrix update next to the Potts one and merge the result into "
                          "the record at --out as `compat_matrix` (the other fields stay as the last full run wrote them)")
+    ap.add_argument("--terms", action="store_true",
+                    help="measure only the feature-terms solver (crf.FeatureCRF) next to DenseCRF.run and write the record to "
+                         "profiles/crf_terms.json (or --terms_out)")
+    ap.add_argument("--terms_out", default=os.path.join(ROOT, "profiles", "crf_terms.json"))
     a = ap.parse_args()
+    if a.terms:
+        line = json.dumps(terms_bench(torch, crf, a))
+        print(line)
+        if a.terms_out:
+            with open(a.terms_out, "w") as f:
+                f.write(line + "\n")
+        return
     if a.compat == "matrix":
         rec = {}
         if a.out and os.path.exists(a.out):
