@@ -328,6 +328,37 @@ int pnp_crf_step_terms(pnp_crf* c, int32_t n, const float* weights, void* stream
 /* Lattice points of one term over the whole batch, as the last successful set_batch built it: term < T of a terms batch; 0
  * (Gaussian) or 1 (bilateral) of a two-term batch.  -1 for a null solver, no batch, or no such term. */
 int64_t pnp_crf_lattice_points(const pnp_crf* c, int32_t term);
+/* ---- gradients of the feature-term mean-field (reverse mode; densecrf's DenseCRF::gradient) ----
+ * The mean-field of pnp_crf_infer_terms as a differentiable function of the unary energies and of the terms' compatibilities
+ * (scalar weight, vector, matrix).  Features, lattices and normalisers are constants of the batch.  Term t's operator A_t =
+ * alpha N S^T B_d .. B_0 S N (splat S, axis blurs B_j, normaliser N) is not symmetric for d >= 2; its adjoint runs the blur axes in
+ * reverse order, and that is what the backward pass filters with.
+ *
+ * pnp_crf_reserve_grad: allocates the gradient workspace of a solver of pnp_crf_create_terms, once (further calls return
+ * PNP_OK and allocate nothing; a call after one that ran out of memory allocates what is missing): four row arrays of the size
+ * of Q (cotangent, dl, h, unary gradient), a buffer for the per-tile fp32 partials of the compatibility gradients -- a batch
+ * with more tiles than it holds (thin images, 1-D signals) passes through it in spans, with the same bits -- and their fp64 sums.  Counted in pnp_crf_allocated_bytes; a solver that never calls it
+ * allocates what it did before.  PNP_ERR_STATE on a solver of pnp_crf_create.
+ *
+ * pnp_crf_infer_terms_saved: pnp_crf_infer_terms -- the same kernels, launches and arithmetic, d_q and d_labels bit for bit --
+ * which also copies the solver's pixel-major marginal rows into d_history after the start and after every update: iters + 1
+ * blocks of sum_b Kp_b * H_b * W_b floats (Kp_b = K_b rounded up to a multiple of 4), caller-owned device memory.
+ *
+ * pnp_crf_backward_terms: from d_grad_q, the cotangent of the marginals laid out as d_q, the gradient of the unary energies
+ * into d_grad_unary (laid out as d_unary) and, for every t < T with d_grad_compat[t] non-null (device memory; the array itself
+ * is host memory of T pointers and may be NULL for none), the gradient of term t's compatibility: 1 float (scalar), K (vector)
+ * or K * K (matrix, row-major [l][k]), float32 from fp64 sums.  It uses the batch and the compatibilities the solver holds and
+ * `weights` for scalar terms, and d_history as pnp_crf_infer_terms_saved left it for the same iters: that these agree is the
+ * caller's contract, nothing here can check it.  The message A_t Q_{i-1} is recomputed (one forward filter) only for terms whose
+ * compatibility gradient is asked for.  No floating-point atomics: every sum runs in an order the batch fixes, two calls give
+ * the same bits.  The solver's marginals and stepwise state stay as they were (pnp_crf_step_terms / pnp_crf_read go on as if
+ * the call had not happened).  PNP_ERR_STATE: no terms batch is set, or pnp_crf_reserve_grad was not called.  PNP_ERR_ARG:
+ * null pointers, iters < 0. */
+int pnp_crf_reserve_grad(pnp_crf* c);
+int pnp_crf_infer_terms_saved(pnp_crf* c, int32_t iters, const float* weights, float* d_history, float* d_q, uint8_t* d_labels,
+                              void* stream);
+int pnp_crf_backward_terms(pnp_crf* c, int32_t iters, const float* weights, const float* d_history, const float* d_grad_q,
+                           float* d_grad_unary, float* const* d_grad_compat, void* stream);
 
 /* ---- input side ("next" row: the tensors the reference's datasets hand to the model) -------
  * Dataset.py:434-443: transforms.Resize((S, S), BICUBIC) on the PIL image -> ToTensor -> Normalize(mean, std).

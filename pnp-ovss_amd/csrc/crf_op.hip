@@ -11,7 +11,9 @@
 // Beyond the reference's call (include/pnp_hip.h): per-axis widths (pnp_crf_set_batch_aniso), label-compatibility vectors and
 // matrices (pnp_crf_set_compat: crf_update_compat of crf.hip takes the update over from crf_update as soon as a term is not
 // scalar), stepwise inference (pnp_crf_start / _step / _read; pnp_crf_infer is start + step + emit) and the KL divergence
-// (pnp_crf_kl), whose ordered fp64 sums over the per-pixel terms are the only arithmetic of this file.
+// (pnp_crf_kl), whose ordered fp64 sums over the per-pixel terms are the only arithmetic of this file.  Gradients of the
+// feature-term mean-field: pnp_crf_reserve_grad / pnp_crf_infer_terms_saved / pnp_crf_backward_terms around
+// crf_meanfield_backward (crf_solver.h), the cotangent and the unary gradient through the planes <-> rows kernels.
 #include <algorithm>
 #include <cstdarg>
 #include <cstdio>
@@ -244,6 +246,11 @@ struct pnp_crf {
     std::vector<PostDesc> tdesc;
     int tkind[PNP_CRF_MAX_TERMS] = {0}, tcompat_K[PNP_CRF_MAX_TERMS] = {0};
     float *d_TM = nullptr, *d_Tvec = nullptr;
+    // -- gradients (pnp_crf_reserve_grad): the workspace of crf_meanfield_backward; q_floats: the row floats of the batch set
+    bool grad_reserved = false;
+    CrfGradWorkspace gw;
+    size_t q_floats = 0;
+    std::vector<int> h_tile0;
     char err[512] = {0};
 };
 
@@ -335,6 +342,7 @@ int crf_layout(pnp_crf* c, const pnp_crf_batch* b) {
         c->maxHW = std::max(c->maxHW, (int)n);
     }
     c->h_label_off[B] = (size_t)at.pix;
+    c->q_floats = at.qoff;
     if (at.pix > c->max_total_pix) return cfail(c, PNP_ERR_ARG, "batch has %lld pixels, reserved %lld", (long long)at.pix, (long long)c->max_total_pix);
     if (at.voff[1] > c->ws.val_cap || at.voff[0] > c->ws.valg_cap)
         return cfail(c, PNP_ERR_ARG, "batch needs %zu lattice value floats, reserved %zu", at.voff[1], c->ws.val_cap);
@@ -690,11 +698,9 @@ int crf_step(pnp_crf* c, int n, float pos_w, float bi_w, hipStream_t s, const Cr
     return PNP_OK;
 }
 
-// n updates of the T feature terms from the current Q; weights[t]: the weight of a term left scalar
-int crf_step_terms(pnp_crf* c, int n, const float* weights, hipStream_t s, const CrfLabelOut& lab) {
+// What crf_meanfield / crf_meanfield_backward take of the T terms of the batch: descriptors and compatibilities, [PNP_CRF_MAX_TERMS] each
+int crf_terms_args(pnp_crf* c, const PostDesc** desc, const float** wvec, const float** MT) {
     const size_t ld = (size_t)c->ldm;
-    const PostDesc* desc[PNP_CRF_MAX_TERMS];
-    const float *wvec[PNP_CRF_MAX_TERMS], *MT[PNP_CRF_MAX_TERMS];
     for (int t = 0; t < c->T; t++) {
         if (c->tkind[t] != PNP_CRF_COMPAT_SCALAR)
             for (int i = 0; i < c->B; i++)
@@ -705,7 +711,15 @@ int crf_step_terms(pnp_crf* c, int n, const float* weights, hipStream_t s, const
         wvec[t] = c->tkind[t] == PNP_CRF_COMPAT_DIAGONAL ? c->d_Tvec + t * ld : nullptr;
         MT[t] = c->tkind[t] == PNP_CRF_COMPAT_MATRIX ? c->d_TM + t * ld * ld : nullptr;
     }
-    const CrfTermsRun run{c->T, desc, weights, wvec, MT, (int)ld};
+    return PNP_OK;
+}
+
+// n updates of the T feature terms from the current Q; weights[t]: the weight of a term left scalar
+int crf_step_terms(pnp_crf* c, int n, const float* weights, hipStream_t s, const CrfLabelOut& lab) {
+    const PostDesc* desc[PNP_CRF_MAX_TERMS];
+    const float *wvec[PNP_CRF_MAX_TERMS], *MT[PNP_CRF_MAX_TERMS];
+    if (int r = crf_terms_args(c, desc, wvec, MT)) return r;
+    const CrfTermsRun run{c->T, desc, weights, wvec, MT, c->ldm};
     CK(c, crf_meanfield(c->ws, crf_span(c), false, n, 0.f, 0.f, nullptr, nullptr, 0, s, lab, &run));
     return PNP_OK;
 }
@@ -724,6 +738,92 @@ extern "C" int pnp_crf_infer_terms(pnp_crf* c, int32_t iters, const float* weigh
     if (int r = crf_start(c, s, iters == 0 ? lab : CrfLabelOut())) return r;
     if (int r = crf_step_terms(c, iters, weights, s, lab)) return r;
     if (d_q) CK(c, crf_planes_rows(false, c->d_desc, d_q, c->ws.Q, c->B, c->maxHW, c->kp_max, s));
+    return PNP_OK;
+}
+
+extern "C" int pnp_crf_infer_terms_saved(pnp_crf* c, int32_t iters, const float* weights, float* d_history, float* d_q, uint8_t* d_labels,
+                                         void* stream) {
+    if (!c) return PNP_ERR_ARG;
+    if (iters < 0) return cfail(c, PNP_ERR_ARG, "iters = %d", iters);
+    if (!weights) return cfail(c, PNP_ERR_ARG, "weights is null (one float per term)");
+    if (!d_history) return cfail(c, PNP_ERR_ARG, "d_history is null (iters + 1 blocks of the batch's row floats)");
+    if (int r = crf_need_batch(c)) return r;
+    if (int r = crf_need_kind(c, true, "pnp_crf_infer_terms_saved")) return r;
+    hipStream_t s = (hipStream_t)stream;
+    CHIP(c, hipSetDevice(c->device));
+    // pnp_crf_infer_terms' launches one update at a time, the rows of Q copied out in between
+    const CrfLabelOut lab = crf_labels(c, d_labels);
+    const size_t qbytes = c->q_floats * sizeof(float);
+    if (int r = crf_start(c, s, iters == 0 ? lab : CrfLabelOut())) return r;
+    CHIP(c, hipMemcpyAsync(d_history, c->ws.Q, qbytes, hipMemcpyDeviceToDevice, s));
+    for (int it = 1; it <= iters; it++) {
+        if (int r = crf_step_terms(c, 1, weights, s, it == iters ? lab : CrfLabelOut())) return r;
+        CHIP(c, hipMemcpyAsync(d_history + (size_t)it * c->q_floats, c->ws.Q, qbytes, hipMemcpyDeviceToDevice, s));
+    }
+    if (d_q) CK(c, crf_planes_rows(false, c->d_desc, d_q, c->ws.Q, c->B, c->maxHW, c->kp_max, s));
+    return PNP_OK;
+}
+
+extern "C" int pnp_crf_reserve_grad(pnp_crf* c) {
+    if (!c) return PNP_ERR_ARG;
+    if (!c->max_terms) return cfail(c, PNP_ERR_STATE, "gradients serve solvers of feature terms: create it with pnp_crf_create_terms");
+    if (!c->ws.va || !c->d_Tvec) return cfail(c, PNP_ERR_STATE, "the solver's workspace was not allocated (pnp_crf_create_terms failed)");
+    if (c->grad_reserved) return PNP_OK;
+    CHIP(c, hipSetDevice(c->device));
+    const size_t TP = (size_t)c->max_total_pix, B = (size_t)c->maxB, rows = TP * c->maxKp;
+    CrfGradWorkspace& gw = c->gw;
+    // partials: a quarter more tiles than the batch's pixels fill at the widest rows' tile (ragged image edges), a few per image;
+    // a batch with more tiles (thin images, 1-D signals) goes through the buffer in spans (crf_meanfield_backward)
+    size_t smem = 0;
+    const size_t tp = (size_t)crf_backward_tile_pixels(c->maxKp, &smem);
+    gw.max_psz = (size_t)c->maxK * c->maxK;
+    gw.part_cap = (TP / tp + TP / (4 * tp) + 2 * B + 16) * gw.max_psz;
+    // Nothing is zero-filled: every array is written in full before it is read -- the rows of g and gU, pad floats included, by
+    // crf_planes_rows / hipMemsetAsync, those of dl and h by the kernels that own them, the partials and sums tile by tile.
+    // An array is allocated only while its pointer is null, so a call after one that ran out of memory allocates the rest
+    auto want = [c](auto** p, size_t count) { return *p ? PNP_OK : calloc_dev(c, p, count); };
+    for (float** p : {&gw.g, &gw.dl, &gw.h, &gw.gU})
+        if (int r = want(p, rows)) return r;
+    if (int r = want(&gw.part, gw.part_cap)) return r;
+    if (int r = want(&gw.img_sum, B * gw.max_psz)) return r;
+    if (int r = want(&gw.acc, (size_t)c->max_terms * gw.max_psz)) return r;
+    if (int r = want(&gw.tile0, B + 1)) return r;
+    c->grad_reserved = true;
+    return PNP_OK;
+}
+
+extern "C" int pnp_crf_backward_terms(pnp_crf* c, int32_t iters, const float* weights, const float* d_history, const float* d_grad_q,
+                                      float* d_grad_unary, float* const* d_grad_compat, void* stream) {
+    if (!c) return PNP_ERR_ARG;
+    if (iters < 0) return cfail(c, PNP_ERR_ARG, "iters = %d", iters);
+    if (!weights) return cfail(c, PNP_ERR_ARG, "weights is null (one float per term)");
+    if (!d_history || !d_grad_q || !d_grad_unary) return cfail(c, PNP_ERR_ARG, "null pointers (d_history, d_grad_q, d_grad_unary)");
+    if (int r = crf_need_batch(c)) return r;
+    if (int r = crf_need_kind(c, true, "pnp_crf_backward_terms")) return r;
+    if (!c->grad_reserved) return cfail(c, PNP_ERR_STATE, "the gradient workspace is not allocated: call pnp_crf_reserve_grad first");
+    hipStream_t s = (hipStream_t)stream;
+    CHIP(c, hipSetDevice(c->device));
+    const PostDesc* desc[PNP_CRF_MAX_TERMS];
+    const float *wvec[PNP_CRF_MAX_TERMS], *MT[PNP_CRF_MAX_TERMS];
+    if (int r = crf_terms_args(c, desc, wvec, MT)) return r;
+    const CrfTermsRun run{c->T, desc, weights, wvec, MT, c->ldm};
+    int psz[PNP_CRF_MAX_TERMS] = {0};
+    for (int t = 0; t < c->T; t++) {
+        if (!d_grad_compat || !d_grad_compat[t]) continue;
+        const int K = c->tcompat_K[t];
+        psz[t] = c->tkind[t] == PNP_CRF_COMPAT_MATRIX ? K * K : c->tkind[t] == PNP_CRF_COMPAT_DIAGONAL ? K : 1;
+    }
+    size_t smem = 0;
+    const int tp = crf_backward_tile_pixels(c->kp_max, &smem);
+    c->h_tile0.assign(c->B + 1, 0);
+    for (int i = 0; i < c->B; i++) c->h_tile0[i + 1] = c->h_tile0[i] + crf_backward_tiles(c->desc[i].H, c->desc[i].W, tp);
+    // (pageable host memory is staged at enqueue time: h_tile0 may be rewritten by the next call)
+    CHIP(c, hipMemcpyAsync(c->gw.tile0, c->h_tile0.data(), sizeof(int) * (c->B + 1), hipMemcpyHostToDevice, s));
+    CK(c, crf_planes_rows(true, c->d_desc, const_cast<float*>(d_grad_q), c->gw.g, c->B, c->maxHW, c->kp_max, s));
+    CK(c, crf_meanfield_backward(c->ws, c->gw, crf_span(c), c->maxHW, iters, run, d_history, c->q_floats, psz, c->h_tile0.data(), s));
+    CK(c, crf_planes_rows(false, c->d_desc, d_grad_unary, c->gw.gU, c->B, c->maxHW, c->kp_max, s));
+    for (int t = 0; t < c->T; t++)
+        if (psz[t]) CK(c, crf_grad_emit(c->gw.acc + (size_t)t * c->gw.max_psz, psz[t], d_grad_compat[t], s));
     return PNP_OK;
 }
 

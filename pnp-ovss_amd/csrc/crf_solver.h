@@ -100,4 +100,24 @@ int crf_meanfield_filter(const CrfWorkspace& ws, const CrfSpan& v, const float**
 int crf_meanfield(const CrfWorkspace& ws, const CrfSpan& v, bool start, int n, float pos_w, float bi_w, const float* MgT, const float* MbT,
                   int ldm, hipStream_t s, const CrfLabelOut& labels, const CrfTermsRun* terms = nullptr);
 
+// The gradient workspace of a solver of feature terms (pnp_crf_reserve_grad): rows as Q -- g (the cotangent of the marginals,
+// rewritten in place update by update), dl, h, gU (the unary gradient) --, the per-tile partials of one term's compatibility
+// gradient (part_cap >= max_psz floats), their per-image fp64 sums (images x max_psz) and the running sums acc[term][max_psz], and the
+// first tile of every image (tile0: images + 1)
+struct CrfGradWorkspace {
+    float *g = nullptr, *dl = nullptr, *h = nullptr, *gU = nullptr, *part = nullptr;
+    double *img_sum = nullptr, *acc = nullptr;
+    int* tile0 = nullptr;
+    size_t part_cap = 0, max_psz = 0;
+};
+// Reverse mode over n updates of the T feature terms of `terms` on the images of v (crf_meanfield with terms).  history: the
+// n + 1 iterates Q_0 .. Q_n, q_floats apart, as ws.Q held them; gw.g: the cotangent of Q_n on entry.  On return gw.gU holds the
+// gradient of the unary rows and, for every term with psz[t] > 0 (1, K or K * K: the floats of its compatibility), gw.acc +
+// t * gw.max_psz the fp64 gradient of its compatibility; only those terms pay a forward filter per update.  h_tile0: tile0 on
+// the host (crf_backward_tiles per image).  Reads ws.unary's layout only; uses ws.va / ws.vb; ws.Q is not touched.  A term's
+// partials go through gw.part (>= max_psz floats) in spans -- whole images while they fit, else the tiles of one image in runs --
+// and the fp64 sums carry over the spans, so the result does not depend on part_cap
+int crf_meanfield_backward(const CrfWorkspace& ws, const CrfGradWorkspace& gw, const CrfSpan& v, int max_pixels, int n, const CrfTermsRun& terms,
+                           const float* history, size_t q_floats, const int* psz, const int* h_tile0, hipStream_t s);
+
 }  // namespace pnp

@@ -2,6 +2,7 @@
 #include "crf_solver.h"
 
 #include <algorithm>
+#include <climits>
 
 namespace pnp {
 
@@ -161,6 +162,52 @@ int crf_meanfield(const CrfWorkspace& ws, const CrfSpan& v, bool start, int n, f
         if (r) return r;
     }
     return PNP_OK;
+}
+
+int crf_meanfield_backward(const CrfWorkspace& ws, const CrfGradWorkspace& gw, const CrfSpan& v, int max_pixels, int n, const CrfTermsRun& terms,
+                           const float* history, size_t q_floats, const int* psz, const int* h_tile0, hipStream_t s) {
+    if (hipMemsetAsync(gw.gU, 0, q_floats * sizeof(float), s) != hipSuccess) return PNP_ERR_HIP;
+    for (int t = 0; t < terms.T; t++)
+        if (psz[t] > 0 && hipMemsetAsync(gw.acc + (size_t)t * gw.max_psz, 0, (size_t)psz[t] * sizeof(double), s) != hipSuccess) return PNP_ERR_HIP;
+    for (int it = n; it >= 1; it--) {
+        const float* const Qi = history + (size_t)it * q_floats;
+        const float* const Qprev = history + (size_t)(it - 1) * q_floats;
+        if (int r = crf_softmax_backward(v.d_desc, v.img0, v.nimg, Qi, gw.g, gw.dl, gw.gU, max_pixels, v.kp_max, s)) return r;
+        for (int t = 0; t < terms.T; t++) {                  // (gw.g is free from here on: the terms' slices rebuild it)
+            const CrfLattice& L = ws.tlat[t];
+            if (psz[t] > 0) {
+                // the message of the update is recomputed, and the images go in spans whose partials the buffer holds
+                const float* val = nullptr;
+                if (int r = crf_filter(L, terms.d_desc[t], v.img0, v.nimg, Qprev, ws.va, ws.vb, &val, v.kp_max, s)) return r;
+                const int cap_tiles = (int)std::min<size_t>(gw.part_cap / psz[t], INT_MAX);      // >= 1: part_cap >= max_psz
+                double* const acc = gw.acc + (size_t)t * gw.max_psz;
+                for (int i0 = v.img0; i0 < v.img0 + v.nimg;) {
+                    int ni = 0;
+                    while (i0 + ni < v.img0 + v.nimg && h_tile0[i0 + ni + 1] - h_tile0[i0] <= cap_tiles) ni++;
+                    // whole images while they fit; an image with more tiles than the buffer holds goes in spans of its tiles
+                    const int ntiles = ni ? INT_MAX : h_tile0[i0 + 1] - h_tile0[i0];
+                    for (int t_lo = 0; t_lo < ntiles; t_lo += cap_tiles) {
+                        const int t_hi = ni ? INT_MAX : std::min(t_lo + cap_tiles, ntiles);
+                        if (int r = crf_term_backward(L, terms.d_desc[t], i0, ni ? ni : 1, val, ws.tnorm[t], gw.dl, gw.h, terms.w[t],
+                                                      terms.wvec[t], terms.MT[t], terms.ldm, v.kp_max, gw.part, gw.tile0, psz[t], t_lo, t_hi, s))
+                            return r;
+                        if (int r = crf_grad_reduce(gw.part, gw.tile0, i0, ni ? ni : 1, psz[t], gw.img_sum, acc, t_lo, t_hi, t_hi >= ntiles, s))
+                            return r;
+                        if (ni) break;
+                    }
+                    i0 += ni ? ni : 1;
+                }
+            } else if (int r = crf_term_backward(L, terms.d_desc[t], v.img0, v.nimg, nullptr, ws.tnorm[t], gw.dl, gw.h, terms.w[t],
+                                                 terms.wvec[t], terms.MT[t], terms.ldm, v.kp_max, nullptr, nullptr, 0, 0, INT_MAX, s)) {
+                return r;
+            }
+            const float* valT = nullptr;
+            if (int r = crf_filter_transposed(L, terms.d_desc[t], v.img0, v.nimg, gw.h, ws.va, ws.vb, &valT, v.kp_max, s)) return r;
+            if (int r = crf_slice_add(L, terms.d_desc[t], v.img0, v.nimg, valT, ws.tnorm[t], gw.g, t == 0, s)) return r;
+        }
+    }
+    // Q_0 = softmax(-U)
+    return crf_softmax_backward(v.d_desc, v.img0, v.nimg, history, gw.g, gw.dl, gw.gU, max_pixels, v.kp_max, s);
 }
 
 }  // namespace pnp

@@ -214,5 +214,31 @@ int crf_update_compat(const CrfLattice& Lg, const CrfLattice& Lb, const PostDesc
 int crf_term_update(const CrfLattice& L, const PostDesc* d_imgs, int img0, int nimg, const float* val, const float* norm, const float* base,
                     bool first, float* out, bool last, float w, const float* wvec, const float* MT, int ldm, int max_kp, hipStream_t s,
                     const CrfLabelOut& labels);
+// ---- reverse mode of the T-term update (crf.hip; the sequence is crf_meanfield_backward of crf_solver.h)
+// lattice^T(norm * rows): crf_filter with the blur axes in reverse order (the adjoint of the filter)
+int crf_filter_transposed(const CrfLattice& L, const PostDesc* d_imgs, int img0, int nimg, const float* rows, float* va, float* vb,
+                          const float** result, int max_kp, hipStream_t s);
+// dl = Q (.) (g - <g, Q>) per pixel; gU -= dl.  Rows as Q
+int crf_softmax_backward(const PostDesc* d_imgs, int img0, int nimg, const float* Q, const float* g, float* dl, float* gU, int max_pixels,
+                         int max_kp, hipStream_t s);
+// The tile of crf_term_backward (pixels, LDS bytes) for rows of up to max_kp floats, and the tiles of an H x W image
+int crf_backward_tile_pixels(int max_kp, size_t* smem);
+int crf_backward_tiles(int H, int W, int tile_pixels);
+// h = C^T dl for one term (MT / wvec / w as crf_term_update).  val non-null -- the term's forward-filtered values of the update's
+// input marginals -- : also one fp32 partial of psz floats (1, K or K * K) of the compatibility gradient per tile, at
+// part[(tile0[b] - tile0[img0] + tile - t_lo) * psz]; tile0: [images of the batch + 1] first tile of every image (device).
+// The launch takes the tiles [t_lo, t_hi) of every image: (0, INT_MAX) for whole images, else a span of ONE image (nimg = 1)
+int crf_term_backward(const CrfLattice& L, const PostDesc* d_imgs, int img0, int nimg, const float* val, const float* norm, const float* dl,
+                      float* h, float w, const float* wvec, const float* MT, int ldm, int max_kp, float* part, const int* tile0, int psz,
+                      int t_lo, int t_hi, hipStream_t s);
+// The partials of images [img0, img0 + nimg), tiles [t_lo, t_hi) as above, in fp64: tiles in order within an image into img_sum
+// (nimg x psz; continued from what it holds if t_lo > 0), and once an image's last span is in (`done`) acc[0 .. psz) += the
+// images in order
+int crf_grad_reduce(const float* part, const int* tile0, int img0, int nimg, int psz, double* img_sum, double* acc, int t_lo, int t_hi,
+                    bool done, hipStream_t s);
+int crf_grad_emit(const double* acc, int n, float* out, hipStream_t s);
+// g (+)= norm * alpha * slice(val): a store when `first`
+int crf_slice_add(const CrfLattice& L, const PostDesc* d_imgs, int img0, int nimg, const float* val, const float* norm, float* g, bool first,
+                  hipStream_t s);
 
 }  // namespace pnp

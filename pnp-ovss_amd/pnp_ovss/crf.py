@@ -33,6 +33,13 @@ depth channel in the bilateral kernel, two bilateral scales, 1-D signals:
 Features arrive divided by their kernel widths and are used as given; a term has 1 .. 6 of them (max_dims) and the solver is
 sized for the worst case of d + 1 lattice points per pixel -- that is the contract.  [position_features, image_features of an
 RGB image] with scalar weights is DenseCRF.run bit for bit.  The KL divergence is not available for feature terms.
+
+The feature-term mean-field as a differentiable layer (gradients of the unary energies and of the compatibilities; the
+features are constants):
+
+    M = torch.eye(K, device="cuda").mul_(5).requires_grad_()                     # a learnable (K, K) compatibility
+    (q,) = solver.marginals([U_dev.requires_grad_()], [crf.Term(feats, M)], iters=5)          # (K, H, W), on the autograd graph
+    loss(q).backward()                                                            # U_dev.grad, M.grad
 """
 import ctypes as C
 import numbers
@@ -362,6 +369,7 @@ def plan_terms(sizes, labels, dims):
     terms): tvoff -- per image, the float offset of its lattice value rows in the value buffers the terms take turns in (d + 1
     rows of Kp floats per pixel at most); foff -- per image, the float offset of its (d, H*W) block in the term's concatenated
     features; total_features -- floats of that concatenation.  value_floats: what the widest term needs of a value buffer.
+    q_floats: the pixel-major marginal rows of the batch (sum of Kp * H * W), one block of pnp_crf_infer_terms_saved's history.
     And the further bounds a solver needs: max_terms, max_dims."""
     dims = [int(d) for d in dims]
     if not 1 <= len(dims) <= MAX_TERMS:
@@ -381,7 +389,7 @@ def plan_terms(sizes, labels, dims):
         plan["foff"].append([d * p0 for p0 in plan["pix0"]])
         plan["total_features"].append(d * plan["max_total_pixels"])
     plan.update(value_floats=max((d + 1) * sum(n * kp for n, kp in zip(pix, plan["Kp"])) for d in dims),
-                max_terms=len(dims), max_dims=max(dims))
+                max_terms=len(dims), max_dims=max(dims), q_floats=sum(n * kp for n, kp in zip(pix, plan["Kp"])))
     return plan
 
 
@@ -420,7 +428,8 @@ def image_features(images, sxy, schan):
 class Term:
     """One pairwise term: features -- per image one (d, H, W) or (d, H*W) float32 array or device tensor, already divided by the
     kernel widths -- and a compatibility: a number (the Potts weight), or (K,) / (K, K) float32 message weights, used as given
-    (compat_values)."""
+    (compat_values).  A torch.Tensor compatibility -- 0-d, (K,) or (K, K), on the host or the device -- is also kept as given
+    (`tensor`): FeatureCRF.marginals differentiates with respect to it."""
 
     def __init__(self, features, compat=1.0):
         self.features = list(features)
@@ -431,13 +440,14 @@ class Term:
                 raise ValueError(f"features are float32, not {getattr(f, 'dtype', type(f).__name__)}")
             if f.ndim not in (2, 3):
                 raise ValueError(f"features are (d, H, W) or (d, H*W), not {tuple(f.shape)}")
+        self.tensor = compat if isinstance(compat, torch.Tensor) else None
         self.dims = int(self.features[0].shape[0])
         if any(int(f.shape[0]) != self.dims for f in self.features):
             raise ValueError(f"a term has the same feature axes in every image, not {[int(f.shape[0]) for f in self.features]}")
         if not 1 <= self.dims <= MAX_DIMS:
             raise ValueError(f"a term has 1..{MAX_DIMS} feature axes, not {self.dims}")
         if isinstance(compat, (int, float, np.integer, np.floating)) or (hasattr(compat, "ndim") and compat.ndim == 0):
-            self.weight, self.compat = float(compat), None
+            self.weight, self.compat = float(compat.detach()) if isinstance(compat, torch.Tensor) else float(compat), None
         else:
             self.weight, self.compat = 0.0, compat
         self.kind, self.values, self.K = compat_values(self.compat, "compat")
@@ -575,6 +585,38 @@ class FeatureCRF(_Solver):
         if r != 0:
             _raise(self.lib, self.h, r, "pnp_crf_step_terms")
 
+    def marginals(self, unaries, terms, iters=5):
+        """run() as a differentiable function: per image the (K, H, W) float32 marginals after `iters` updates, attached to
+        the autograd graph of the unaries (device tensors) and of every term's compatibility given as a torch.Tensor (0-d, (K,)
+        or (K, K), host or device; its gradient comes back in that shape on that device).  Features are constants.  Labels
+        are not differentiable and not returned.  The backward pass (pnp_crf_backward_terms) needs the batch of the forward
+        still set on this solver and raises RuntimeError otherwise; it recomputes a term's message only where that term's
+        compatibility needs a gradient; no double backward.  The first call allocates the gradient workspace."""
+        if not torch.cuda.is_available():
+            raise RuntimeError("pnp_ovss.crf.FeatureCRF.marginals needs a HIP device (no CPU fallback)")
+        terms = self._check_terms(terms)
+        for i, u in enumerate(unaries):
+            if not (isinstance(u, torch.Tensor) and u.is_cuda):
+                raise ValueError(f"image {i}: marginals() takes the unary energies as device tensors")
+        _, feats, sizes, labels = self._gather([u.detach() for u in unaries], terms)
+        for t, term in enumerate(terms):
+            check_compat_labels(term.K, labels, f"term {t}'s compat")
+        if not getattr(self, "_grad", False):
+            with torch.cuda.device(self.device):
+                r = self.lib.pnp_crf_reserve_grad(self.h)
+            if r != 0:
+                _raise(self.lib, self.h, r, "pnp_crf_reserve_grad")
+            self._grad = True
+        flat = [u.to(self.device).contiguous().reshape(-1) for u in unaries]
+        d_unary = torch.cat(flat) if len(flat) > 1 else flat[0]
+        # a compatibility that is no tensor (a number, a numpy vector or matrix) enters as a constant of the graph
+        compats = [term.tensor if term.tensor is not None else
+                   torch.from_numpy(np.array(term.compat, dtype=np.float32)) if term.compat is not None else torch.tensor(term.weight)
+                   for term in terms]
+        d_q = _Marginals.apply(self, feats, [term.dims for term in terms], sizes, labels, int(iters), d_unary, *compats)
+        plan = self._plan[0]
+        return [d_q[off:off + k * h * w].view(k, h, w) for (h, w), k, off in zip(sizes, labels, plan["off"])]
+
     def lattice_points(self):
         """Lattice points of every term over the whole batch of the last set_batch (at most d + 1 per pixel)."""
         self._outputs("lattice_points", False, False)
@@ -582,6 +624,58 @@ class FeatureCRF(_Solver):
 
     def kl(self):
         raise NotImplementedError("pnp_ovss.crf.FeatureCRF.kl: the KL divergence is not available for feature terms (use DenseCRF)")
+
+
+def _compat_host(t):
+    """A compatibility tensor as run() takes it: None for a 0-d one (the weight of the call), else float32 on the host."""
+    return None if t.ndim == 0 else t.detach().to("cpu", torch.float32).contiguous().numpy()
+
+
+class _Marginals(torch.autograd.Function):
+    """FeatureCRF.marginals: the concatenated unary tensor and one compatibility tensor per term -> the concatenated marginals."""
+
+    @staticmethod
+    def forward(ctx, solver, feats, dims, sizes, labels, iters, d_unary, *compats):
+        solver.set_batch(d_unary.detach(), feats, dims, sizes, labels)
+        solver.set_compat([_compat_host(c) for c in compats])
+        plan = solver._plan[0]
+        w = solver._weights([float(c) if c.ndim == 0 else 0.0 for c in compats])
+        history = torch.empty((iters + 1) * plan["q_floats"], dtype=torch.float32, device=solver.device)
+        d_q = torch.empty(plan["total_unary"], dtype=torch.float32, device=solver.device)
+        with torch.cuda.device(solver.device):
+            r = solver.lib.pnp_crf_infer_terms_saved(solver.h, iters, w, hip._ptr(history), hip._ptr(d_q), None, hip._stream())
+        if r != 0:
+            _raise(solver.lib, solver.h, r, "pnp_crf_infer_terms_saved")
+        ctx.solver, ctx.iters, ctx.token = solver, iters, solver.batch_token()
+        # copies: backward re-sends the compatibilities this history was computed with, whatever an optimiser step (an in-place
+        # update autograd's version check would not see on these) has made of the caller's tensors since
+        ctx.compats = [c.detach().clone() for c in compats]
+        ctx.save_for_backward(history)
+        return d_q
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_q):
+        solver, compats = ctx.solver, ctx.compats
+        if solver.batch_token() != ctx.token or getattr(solver, "_plan", None) is None:
+            raise RuntimeError("pnp_ovss.crf.FeatureCRF.marginals: backward needs the batch of its forward, but the solver has been "
+                               "given another batch since (set_batch / run / marginals); run the forward again")
+        (history,) = ctx.saved_tensors
+        plan = solver._plan[0]
+        solver.set_compat([_compat_host(c) for c in compats])     # the compatibilities of the forward, whatever came since
+        w = (C.c_float * len(compats))(*[float(c) if c.ndim == 0 else 0.0 for c in compats])
+        need = ctx.needs_input_grad[7:]
+        outs = [torch.empty(max(c.numel(), 1), dtype=torch.float32, device=solver.device) if n else None for c, n in zip(compats, need)]
+        ptrs = (C.c_void_p * len(compats))(*[o.data_ptr() if o is not None else None for o in outs])
+        g_unary = torch.empty(plan["total_unary"], dtype=torch.float32, device=solver.device)
+        grad_q = grad_q.to(solver.device, torch.float32).contiguous()
+        with torch.cuda.device(solver.device):
+            r = solver.lib.pnp_crf_backward_terms(solver.h, ctx.iters, w, hip._ptr(history), hip._ptr(grad_q), hip._ptr(g_unary), ptrs,
+                                                  hip._stream())
+        if r != 0:
+            _raise(solver.lib, solver.h, r, "pnp_crf_backward_terms")
+        g_compats = [o.reshape(c.shape).to(c.device, c.dtype) if o is not None else None for o, c in zip(outs, compats)]
+        return (None,) * 6 + (g_unary if ctx.needs_input_grad[6] else None,) + tuple(g_compats)
 
 
 _FEATURE_SOLVERS = {}    # device index -> the solver feature_solver() hands out there

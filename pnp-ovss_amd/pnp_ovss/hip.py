@@ -142,6 +142,9 @@ def load_library():
         "pnp_crf_infer_terms": (i32, [vp, i32, C.POINTER(f32), vp, vp, vp]),
         "pnp_crf_step_terms": (i32, [vp, i32, C.POINTER(f32), vp]),
         "pnp_crf_lattice_points": (i64, [vp, i32]),
+        "pnp_crf_reserve_grad": (i32, [vp]),
+        "pnp_crf_infer_terms_saved": (i32, [vp, i32, C.POINTER(f32), vp, vp, vp, vp]),
+        "pnp_crf_backward_terms": (i32, [vp, i32, C.POINTER(f32), vp, vp, vp, C.POINTER(vp), vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)          # AttributeError here = ABI drift, fail loudly
@@ -166,7 +169,8 @@ EXPORTED = ["pnp_create", "pnp_create_shared", "pnp_destroy", "pnp_last_error", 
             "pnp_crf_create", "pnp_crf_destroy", "pnp_crf_allocated_bytes", "pnp_crf_last_error", "pnp_crf_set_batch",
             "pnp_crf_infer", "pnp_crf_set_batch_aniso", "pnp_crf_set_compat", "pnp_crf_start", "pnp_crf_step", "pnp_crf_read",
             "pnp_crf_kl", "pnp_crf_create_terms", "pnp_crf_set_batch_terms", "pnp_crf_set_term_compat", "pnp_crf_infer_terms",
-            "pnp_crf_step_terms", "pnp_crf_lattice_points"]
+            "pnp_crf_step_terms", "pnp_crf_lattice_points", "pnp_crf_reserve_grad", "pnp_crf_infer_terms_saved",
+            "pnp_crf_backward_terms"]
 
 
 PROJ_NAMES = ("vision_proj.weight", "vision_proj.bias", "text_proj.weight", "text_proj.bias")      # the optional ITC projections

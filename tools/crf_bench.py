@@ -2,6 +2,8 @@
 
     timeout 900 python tools/crf_bench.py [--images 35] [--size 375x500] [--labels 21] [--reps 30] [--out profiles/crf_standalone.json]
     timeout 900 python tools/crf_bench.py --terms          # crf.FeatureCRF next to DenseCRF.run -> profiles/crf_terms.json
+    timeout 900 python tools/crf_bench.py --grad           # the mean-field's backward pass -> profiles/crf_grad.json
+    timeout 300 python tools/crf_bench.py --grad_errors    # its errors against the float64 reference -> `errors` of that record
 
 Warm, then `reps` repetitions, device work between HIP events:
   one image through the shim      the host-to-host call (numpy in, numpy out: DenseCRF2D ... inference(10)), and separately the
@@ -216,6 +218,132 @@ def terms_bench(torch, crf, a):
     return rec
 
 
+def grad_bench(torch, crf, a):
+    """--grad: the reverse mode of the feature-term mean-field (pnp_crf_infer_terms_saved / pnp_crf_backward_terms) on three terms
+    -- xy / 3 (weight 7), xy / 50 . rgb / 5 (weight 10), xy / 80 . rgb / 13 . depth / 0.1 (a K x K matrix) -- and 5 iterations:
+    the forward with and without the history, alternated; the backward with every compatibility gradient and with none,
+    alternated; the bytes pnp_crf_reserve_grad adds; the device time of every kernel family of one backward call."""
+    import ctypes as C
+    from pnp_ovss import hip
+    H, W = map(int, a.size.split("x"))
+    B, K, iters = a.images, a.labels, 5
+    rng = np.random.default_rng(0)
+    imgs = [synth_photo(rng, H, W) for _ in range(B)]
+    yy, xx = np.mgrid[0:H, 0:W].astype(np.float64)
+    depth = [(0.5 + 0.4 * np.sin(xx / 7.0) * np.cos(yy / 5.0) + rng.normal(0, 0.02, (H, W))).astype(np.float32) for _ in range(B)]
+    logits = torch.from_numpy(rng.normal(0, 2, (B, K, H * W)).astype(np.float32)).cuda()
+    d_unary = (-torch.log_softmax(logits, 1).clamp_min(float(np.log(1e-5)))).contiguous().reshape(-1)
+    del logits
+    sizes, labels = [(H, W)] * B, [K] * B
+
+    def dev(parts):
+        return torch.from_numpy(np.concatenate([p.reshape(-1) for p in parts])).cuda()
+    feats = [dev(crf.position_features(sizes, 3.0)), dev(crf.image_features(imgs, 50.0, 5.0)),
+             dev(crf.image_features([np.dstack([im.astype(np.float32), dp]) for im, dp in zip(imgs, depth)], 80.0, (13.0, 13.0, 13.0, 0.1)))]
+    M = (5.0 * np.eye(K) + 0.3 * rng.normal(size=(K, K))).astype(np.float32)
+    feat = crf.FeatureCRF(B, B * H * W, H * W, K, max_terms=3, max_dims=6)
+    before = feat.allocated_bytes()
+    r = feat.lib.pnp_crf_reserve_grad(feat.h)
+    assert r == 0, feat.lib.pnp_crf_last_error(feat.h)
+    reserved = feat.allocated_bytes() - before
+    feat.set_batch(d_unary, feats, [2, 5, 6], sizes, labels)
+    feat.set_compat([None, None, M])
+    plan = feat._plan[0]
+    w = (C.c_float * 3)(7.0, 10.0, 0.0)
+    history = torch.empty((iters + 1) * plan["q_floats"], dtype=torch.float32, device="cuda")
+    d_q = torch.empty(plan["total_unary"], dtype=torch.float32, device="cuda")
+    grad_q = torch.from_numpy(rng.normal(size=plan["total_unary"]).astype(np.float32)).cuda()
+    g_unary = torch.empty_like(d_q)
+    g_compat = [torch.empty(1, device="cuda"), torch.empty(1, device="cuda"), torch.empty(K * K, device="cuda")]
+    all_ptrs = (C.c_void_p * 3)(*[g.data_ptr() for g in g_compat])
+
+    def check(r, what):
+        assert r == 0, (what, feat.lib.pnp_crf_last_error(feat.h))
+
+    def fwd_plain():
+        check(feat.lib.pnp_crf_infer_terms(feat.h, iters, w, hip._ptr(d_q), None, hip._stream()), "infer_terms")
+
+    def fwd_saved():
+        check(feat.lib.pnp_crf_infer_terms_saved(feat.h, iters, w, hip._ptr(history), hip._ptr(d_q), None, hip._stream()), "infer_terms_saved")
+
+    def bwd(ptrs):
+        check(feat.lib.pnp_crf_backward_terms(feat.h, iters, w, hip._ptr(history), hip._ptr(grad_q), hip._ptr(g_unary), ptrs,
+                                              hip._stream()), "backward_terms")
+
+    def alternated(f0, f1, n):
+        t0, t1 = [], []
+        for _ in range(n):
+            t0.append(events_ms(torch, f0, 1))
+            t1.append(events_ms(torch, f1, 1))
+        return float(np.median(t0)), float(np.median(t1)), [float(min(t0)), float(max(t0))], [float(min(t1)), float(max(t1))]
+    fwd_plain()
+    q_plain = d_q.clone()
+    fwd_saved()
+    same = bool(torch.equal(q_plain, d_q))
+    del q_plain
+    bwd(all_ptrs)
+    first = [g.clone() for g in [g_unary] + g_compat]
+    bwd(all_ptrs)                                                                 # warm; and the same bits twice
+    deterministic = all(bool(torch.equal(x, y)) for x, y in zip(first, [g_unary] + g_compat))
+    bwd(None)
+    unary_same = bool(torch.equal(first[0], g_unary))
+    reps = max(a.reps // 3, 5)
+    f_plain, f_saved, f_plain_mm, f_saved_mm = alternated(fwd_plain, fwd_saved, reps)
+    b_all, b_none, b_all_mm, b_none_mm = alternated(lambda: bwd(all_ptrs), lambda: bwd(None), reps)
+
+    from torch.profiler import ProfilerActivity, profile
+    torch.cuda.synchronize()
+    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+        bwd(all_ptrs)
+        torch.cuda.synchronize()
+    fam = {k: [] for k in ("crf_softmax_backward_kernel", "crf_term_backward_kernel", "crf_slice_add_kernel", "crf_grad_image_kernel",
+                           "crf_grad_final_kernel", "crf_splat_kernel", "crf_blur4x2_kernel", "crf_blur4_kernel", "crf_planes_rows")}
+    for ev in prof.events():
+        if "DeviceType.CUDA" not in str(getattr(ev, "device_type", "")):
+            continue
+        us = getattr(ev, "device_time", None)
+        if us is None:
+            us = getattr(ev, "cuda_time", 0.0)
+        for name in fam:
+            if name in ev.name:
+                fam[name].append(float(us))
+                break
+    kernels = {k: dict(launches=len(v), ms=float(np.sum(v)) / 1e3) for k, v in fam.items() if v}
+    rec = dict(images=B, size=[H, W], labels=K, iters=iters, reps=reps,
+               forward_ms=f_plain, forward_saved_ms=f_saved, forward_min_max_ms=f_plain_mm, forward_saved_min_max_ms=f_saved_mm,
+               backward_all_compat_ms=b_all, backward_unary_only_ms=b_none, backward_all_compat_min_max_ms=b_all_mm,
+               backward_unary_only_min_max_ms=b_none_mm, backward_per_forward=b_all / f_plain, backward_unary_only_per_forward=b_none / f_plain,
+               reserve_grad_bytes=reserved, allocated_bytes_before=before, history_bytes=history.numel() * 4,
+               forward_saved_bit_identical=same, backward_deterministic=deterministic, unary_gradient_same_without_compat=unary_same,
+               backward_kernels=kernels,
+               note="forward = pnp_crf_infer_terms with the marginals out and no labels, forward_saved = pnp_crf_infer_terms_saved (the "
+                    "same launches plus iters + 1 device copies of the marginal rows), alternated repetition by repetition, medians of "
+                    "device events; backward_all_compat = pnp_crf_backward_terms with the gradient of every compatibility (two scalars "
+                    "and one K x K matrix: one forward filter per term and update on top), backward_unary_only = with none; "
+                    "backward_kernels = device time of one backward_all_compat call by kernel family as torch's profiler reports it "
+                    "(crf_blur4x2 / crf_splat also serve the recomputed forward filters).  Random unaries, cotangent and matrix: the "
+                    "arithmetic does not depend on the values")
+    feat.close()
+    return rec
+
+
+def grad_errors(crf):
+    """--grad_errors: max|g - g_ref| / max|g_ref| of every gradient tensor of the GPU test's cases (tests/_crf_grad_ref.GRAD_CASES,
+    measured by tests/test_crf_grad_gpu.measure) -- the figures the test's bound (_crf_grad_ref.WORST_MEASURED, BOUND) is set from."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import _crf_grad_ref as R
+    import _crf_terms_ref as TR
+    import test_crf_grad_gpu as G
+    pix = sorted(c[0][1] * c[0][2] for c in TR.CASES)
+    solver = crf.FeatureCRF(2, pix[-1] + pix[-2], pix[-1], 150, max_terms=4, max_dims=6)
+    cases = {name: G.measure(crf, solver, i, k) for (i, k), name in zip(R.GRAD_CASES, G.CASE_IDS)}
+    solver.close()
+    worst = max(v for d in cases.values() for v in d.values())
+    return dict(what="max|g - g_ref| / max|g_ref| per gradient tensor against the float64 reference of tests/_crf_grad_ref.py, "
+                     f"{R.ITERS} iterations (tools/crf_bench.py --grad_errors)",
+                cases=cases, worst=worst, bound=float(10.0 ** np.ceil(np.log10(10 * worst) - 1e-9)))
+
+
 def main():
     import torch
     from oracle import pipeline_np as OP
@@ -235,7 +363,31 @@ def main():
                     help="measure only the feature-terms solver (crf.FeatureCRF) next to DenseCRF.run and write the record to "
                          "profiles/crf_terms.json (or --terms_out)")
     ap.add_argument("--terms_out", default=os.path.join(ROOT, "profiles", "crf_terms.json"))
+    ap.add_argument("--grad", action="store_true",
+                    help="measure only the backward pass of the feature-term mean-field and write the record to profiles/crf_grad.json "
+                         "(or --grad_out), keeping the `errors` entry of the record that is there")
+    ap.add_argument("--grad_out", default=os.path.join(ROOT, "profiles", "crf_grad.json"))
+    ap.add_argument("--grad_errors", action="store_true",
+                    help="measure only the gradients' errors against the float64 reference and write them as the `errors` entry of "
+                         "the record at --grad_out, keeping its other fields")
     a = ap.parse_args()
+    if a.grad or a.grad_errors:
+        old = {}
+        if a.grad_out and os.path.exists(a.grad_out):
+            with open(a.grad_out) as f:
+                old = json.loads(f.read())
+        if a.grad:
+            rec = grad_bench(torch, crf, a)
+            if "errors" in old:
+                rec["errors"] = old["errors"]
+        else:
+            rec = dict(old, errors=grad_errors(crf))
+        line = json.dumps(rec)
+        print(line)
+        if a.grad_out:
+            with open(a.grad_out, "w") as f:
+                f.write(line + "\n")
+        return
     if a.terms:
         line = json.dumps(terms_bench(torch, crf, a))
         print(line)
