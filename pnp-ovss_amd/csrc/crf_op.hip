@@ -1,4 +1,4 @@
-// The stand-alone DenseCRF of include/pnp_hip.h (pnp_crf_create ... pnp_crf_infer): the mean-field of crf.hip on unary energies
+// The stand-alone DenseCRF of include/pnp_hip.h (pnp_crf_create ... pnp_crf_infer): the mean-field of crf_meanfield.hip on unary energies
 // the caller brings, with kernel widths the caller chooses, in a solver that owns its workspace and needs no pnp_engine -- what
 // pydensecrf's DenseCRF2D is to the reference (PnP_OVSS_0514_updated_segmentation.py:1063-1073).
 //
@@ -9,7 +9,7 @@
 // rows the mean-field kernels work on.  The planes <-> rows kernels move floats, and the labels come from the
 // last update's own argmax (CrfLabelOut with an identity table).
 // Beyond the reference's call (include/pnp_hip.h): per-axis widths (pnp_crf_set_batch_aniso), label-compatibility vectors and
-// matrices (pnp_crf_set_compat: crf_update_compat of crf.hip takes the update over from crf_update as soon as a term is not
+// matrices (pnp_crf_set_compat: crf_update_compat of crf_meanfield.hip takes the update over from crf_update as soon as a term is not
 // scalar), stepwise inference (pnp_crf_start / _step / _read; pnp_crf_infer is start + step + emit) and the KL divergence
 // (pnp_crf_kl), whose ordered fp64 sums over the per-pixel terms are the only arithmetic of this file.  Gradients of the
 // feature-term mean-field: pnp_crf_reserve_grad / pnp_crf_infer_terms_saved / pnp_crf_backward_terms around
@@ -411,31 +411,74 @@ int widest_feature(const float* w, const float* extent, int n) {
     return at;
 }
 
-// pnp_crf_set_batch / pnp_crf_set_batch_aniso: pos_xy = (sx, sy) of the Gaussian term, bi_xy / bi_rgb = (sx, sy) / (sr, sg, sb)
-// of the bilateral one
-int crf_set_batch(pnp_crf* c, const pnp_crf_batch* b, const float pos_xy[2], const float bi_xy[2], const float bi_rgb[3], void* stream) {
-    c->ready = false;
-    c->started = false;
-    if (!c->ws.va || !c->kl_out) return cfail(c, PNP_ERR_STATE, "the solver's workspace was not allocated (pnp_crf_create failed)");
-    if (!b) return cfail(c, PNP_ERR_ARG, "batch is null");
-    if (b->B < 1 || b->B > c->maxB) return cfail(c, PNP_ERR_ARG, "batch of %d images, the solver holds 1..%d", b->B, c->maxB);
-    if (!b->H || !b->W || !b->K || !b->d_rgb || !b->d_unary) return cfail(c, PNP_ERR_ARG, "batch has null arrays (H, W, K, d_rgb, d_unary)");
-    const bool iso = pos_xy[0] == pos_xy[1] && bi_xy[0] == bi_xy[1] && bi_rgb[0] == bi_rgb[1] && bi_rgb[0] == bi_rgb[2];
-    if (!(pos_xy[0] > 0.f) || !(pos_xy[1] > 0.f) || !(bi_xy[0] > 0.f) || !(bi_xy[1] > 0.f) || !(bi_rgb[0] > 0.f) || !(bi_rgb[1] > 0.f) ||
-        !(bi_rgb[2] > 0.f)) {
-        if (iso) return cfail(c, PNP_ERR_ARG, "kernel widths must be positive (pos_xy=%g, bi_xy=%g, bi_rgb=%g)", pos_xy[0], bi_xy[0], bi_rgb[0]);
-        return cfail(c, PNP_ERR_ARG, "kernel widths must be positive (pos_xy=(%g, %g), bi_xy=(%g, %g), bi_rgb=(%g, %g, %g))", pos_xy[0],
-                     pos_xy[1], bi_xy[0], bi_xy[1], bi_rgb[0], bi_rgb[1], bi_rgb[2]);
+// The value rows of term t (dims[t] + 1 per pixel at most) image by image, into tdesc[t * B + i]; false: beyond the per-image
+// addressing of the iteration kernels (24-bit row ids, 32-bit byte offsets: crf_meanfield.hip)
+bool crf_layout_terms(pnp_crf* c, int T, const int* dims, size_t* need) {
+    const int B = c->B;
+    c->tdesc.assign((size_t)T * B, PostDesc{});
+    *need = 0;
+    for (int t = 0; t < T; t++) {
+        size_t voff = 0;
+        for (int i = 0; i < B; i++) {
+            PostDesc d = c->desc[i];
+            const int64_t rows = (int64_t)d.H * d.W * (dims[t] + 1);
+            d.voff[0] = d.voff[1] = voff;
+            voff += (size_t)rows * d.Kp;
+            c->tdesc[(size_t)t * B + i] = d;
+            if (rows >= (1 << 24) || rows * d.Kp * 4 >= ((int64_t)1 << 32)) return false;
+        }
+        *need = std::max(*need, voff);
     }
+    return true;
+}
+
+// Both forms of set_batch, once the caller's own arguments are through (b non-null; the state flags went down as the call
+// began): B range, null arrays (`arrays`: the caller's are there), the caller's later checks (`own`), the layout -- of T feature
+// terms too --, then on the stream the descriptors, the label offsets and the unary planes into rows
+template <typename Own>
+int crf_batch_prologue(pnp_crf* c, const pnp_crf_batch* b, bool arrays, const char* arrays_msg, Own own, int T, const int* dims, hipStream_t s) {
+    if (b->B < 1 || b->B > c->maxB) return cfail(c, PNP_ERR_ARG, "batch of %d images, the solver holds 1..%d", b->B, c->maxB);
+    if (!arrays) return cfail(c, PNP_ERR_ARG, "%s", arrays_msg);
+    if (int r = own()) return r;
     if (int r = crf_layout(c, b)) return r;
-    hipStream_t s = (hipStream_t)stream;
+    if (T) {
+        size_t need = 0;
+        if (!crf_layout_terms(c, T, dims, &need))
+            return cfail(c, PNP_ERR_ARG, "an image's lattice value rows exceed the per-image addressing of the mean-field kernels");
+        if (need > c->ws.val_cap) return cfail(c, PNP_ERR_ARG, "batch needs %zu lattice value floats, reserved %zu", need, c->ws.val_cap);
+    }
     CHIP(c, hipSetDevice(c->device));
     const int B = c->B;
     // (pageable host memory: copied into the runtime's staging buffer at enqueue time, so the vectors may be rewritten by the
     // next call without a synchronisation)
     CHIP(c, hipMemcpyAsync(c->d_desc, c->desc.data(), sizeof(PostDesc) * B, hipMemcpyHostToDevice, s));
+    for (int t = 0; t < T; t++)
+        CHIP(c, hipMemcpyAsync(c->d_tdesc + (size_t)t * c->maxB, c->tdesc.data() + (size_t)t * B, sizeof(PostDesc) * B, hipMemcpyHostToDevice, s));
     CHIP(c, hipMemcpyAsync(c->d_label_off, c->h_label_off.data(), sizeof(size_t) * (B + 1), hipMemcpyHostToDevice, s));
     CK(c, crf_planes_rows(true, c->d_desc, const_cast<float*>(b->d_unary), c->ws.unary, B, c->maxHW, c->kp_max, s));
+    return PNP_OK;
+}
+
+// pnp_crf_set_batch / pnp_crf_set_batch_aniso: pos_xy = (sx, sy) of the Gaussian term, bi_xy / bi_rgb = (sx, sy) / (sr, sg, sb)
+// of the bilateral one
+int crf_set_batch(pnp_crf* c, const pnp_crf_batch* b, const float pos_xy[2], const float bi_xy[2], const float bi_rgb[3], void* stream) {
+    c->ready = c->started = false;
+    if (!c->ws.va || !c->kl_out) return cfail(c, PNP_ERR_STATE, "the solver's workspace was not allocated (pnp_crf_create failed)");
+    if (!b) return cfail(c, PNP_ERR_ARG, "batch is null");
+    const bool iso = pos_xy[0] == pos_xy[1] && bi_xy[0] == bi_xy[1] && bi_rgb[0] == bi_rgb[1] && bi_rgb[0] == bi_rgb[2];
+    auto widths = [&] {
+        if ((pos_xy[0] > 0.f) && (pos_xy[1] > 0.f) && (bi_xy[0] > 0.f) && (bi_xy[1] > 0.f) && (bi_rgb[0] > 0.f) && (bi_rgb[1] > 0.f) &&
+            (bi_rgb[2] > 0.f))
+            return (int)PNP_OK;
+        if (iso) return cfail(c, PNP_ERR_ARG, "kernel widths must be positive (pos_xy=%g, bi_xy=%g, bi_rgb=%g)", pos_xy[0], bi_xy[0], bi_rgb[0]);
+        return cfail(c, PNP_ERR_ARG, "kernel widths must be positive (pos_xy=(%g, %g), bi_xy=(%g, %g), bi_rgb=(%g, %g, %g))", pos_xy[0],
+                     pos_xy[1], bi_xy[0], bi_xy[1], bi_rgb[0], bi_rgb[1], bi_rgb[2]);
+    };
+    hipStream_t s = (hipStream_t)stream;
+    if (int r = crf_batch_prologue(c, b, b->H && b->W && b->K && b->d_rgb && b->d_unary, "batch has null arrays (H, W, K, d_rgb, d_unary)",
+                                   widths, 0, nullptr, s))
+        return r;
+    const int B = c->B;
     int range_term = -1;
     const int built = crf_build(c->ws, c->d_desc, c->desc.data(), B, c->h_label_off[B], c->maxHW, b->d_rgb, pos_xy, bi_xy, bi_rgb, &range_term, s);
     if (range_term >= 0) {
@@ -470,27 +513,6 @@ int crf_set_batch(pnp_crf* c, const pnp_crf_batch* b, const float pos_xy[2], con
     return PNP_OK;
 }
 
-// The value rows of term t (dims[t] + 1 per pixel at most) image by image, into tdesc[t * B + i]; false: beyond the per-image
-// addressing of the iteration kernels (24-bit row ids, 32-bit byte offsets: crf.hip)
-bool crf_layout_terms(pnp_crf* c, int T, const int* dims, size_t* need) {
-    const int B = c->B;
-    c->tdesc.assign((size_t)T * B, PostDesc{});
-    *need = 0;
-    for (int t = 0; t < T; t++) {
-        size_t voff = 0;
-        for (int i = 0; i < B; i++) {
-            PostDesc d = c->desc[i];
-            const int64_t rows = (int64_t)d.H * d.W * (dims[t] + 1);
-            d.voff[0] = d.voff[1] = voff;
-            voff += (size_t)rows * d.Kp;
-            c->tdesc[(size_t)t * B + i] = d;
-            if (rows >= (1 << 24) || rows * d.Kp * 4 >= ((int64_t)1 << 32)) return false;
-        }
-        *need = std::max(*need, voff);
-    }
-    return true;
-}
-
 }  // namespace
 
 extern "C" int pnp_crf_set_batch_terms(pnp_crf* c, const pnp_crf_batch* b, int32_t n_terms, const pnp_crf_term* terms, void* stream) {
@@ -514,21 +536,11 @@ extern "C" int pnp_crf_set_batch_terms(pnp_crf* c, const pnp_crf_batch* b, int32
     if (n_terms > c->max_terms) return cfail(c, PNP_ERR_ARG, "%d terms, the solver holds 1..%d", n_terms, c->max_terms);
     for (int t = 0; t < n_terms; t++)
         if (dims[t] > c->max_dims) return cfail(c, PNP_ERR_ARG, "term %d has %d feature axes, the solver holds 1..%d", t, dims[t], c->max_dims);
-    if (b->B < 1 || b->B > c->maxB) return cfail(c, PNP_ERR_ARG, "batch of %d images, the solver holds 1..%d", b->B, c->maxB);
-    if (!b->H || !b->W || !b->K || !b->d_unary) return cfail(c, PNP_ERR_ARG, "batch has null arrays (H, W, K, d_unary)");
-    if (int r = crf_layout(c, b)) return r;
-    size_t need = 0;
-    if (!crf_layout_terms(c, n_terms, dims, &need))
-        return cfail(c, PNP_ERR_ARG, "an image's lattice value rows exceed the per-image addressing of the mean-field kernels");
-    if (need > c->ws.val_cap) return cfail(c, PNP_ERR_ARG, "batch needs %zu lattice value floats, reserved %zu", need, c->ws.val_cap);
     hipStream_t s = (hipStream_t)stream;
-    CHIP(c, hipSetDevice(c->device));
+    if (int r = crf_batch_prologue(c, b, b->H && b->W && b->K && b->d_unary, "batch has null arrays (H, W, K, d_unary)", [] { return (int)PNP_OK; },
+                                   n_terms, dims, s))
+        return r;
     const int B = c->B;
-    CHIP(c, hipMemcpyAsync(c->d_desc, c->desc.data(), sizeof(PostDesc) * B, hipMemcpyHostToDevice, s));
-    for (int t = 0; t < n_terms; t++)
-        CHIP(c, hipMemcpyAsync(c->d_tdesc + (size_t)t * c->maxB, c->tdesc.data() + (size_t)t * B, sizeof(PostDesc) * B, hipMemcpyHostToDevice, s));
-    CHIP(c, hipMemcpyAsync(c->d_label_off, c->h_label_off.data(), sizeof(size_t) * (B + 1), hipMemcpyHostToDevice, s));
-    CK(c, crf_planes_rows(true, c->d_desc, const_cast<float*>(b->d_unary), c->ws.unary, B, c->maxHW, c->kp_max, s));
     int range_term = -1;
     const int built = crf_build_terms(c->ws, c->d_desc, c->desc.data(), B, c->h_label_off[B], c->maxHW, n_terms, dims, feat, &range_term, s);
     if (range_term >= 0)
@@ -549,6 +561,34 @@ extern "C" int64_t pnp_crf_lattice_points(const pnp_crf* c, int32_t term) {
     return c->terms_batch ? c->ws.tlat_points[term] : c->ws.lat_points[term];
 }
 
+namespace {
+
+// A vector or matrix compatibility of K labels from the host to the device: the checks, then a matrix TRANSPOSED into d_matrix
+// (stride ldm), a diagonal as a vector of ldm floats into d_vector or -- d_vector null: the two-term solver's -- as a matrix.
+// d_matrix null: the workspace that `creator` allocates is not there
+int crf_upload_compat(pnp_crf* c, int kind, const float* host_values, int K, const char* creator, float* d_matrix, float* d_vector) {
+    if (kind != PNP_CRF_COMPAT_DIAGONAL && kind != PNP_CRF_COMPAT_MATRIX)
+        return cfail(c, PNP_ERR_ARG, "kind = %d: scalar (0), diagonal (1) or matrix (2)", kind);
+    if (!host_values) return cfail(c, PNP_ERR_ARG, "compatibility values are null");
+    if (K < 2 || K > c->maxK) return cfail(c, PNP_ERR_ARG, "compatibility for %d labels, the solver holds 2..%d", K, c->maxK);
+    if (!d_matrix) return cfail(c, PNP_ERR_STATE, "the solver's workspace was not allocated (%s failed)", creator);
+    const size_t ld = (size_t)c->ldm;
+    const bool diag = kind == PNP_CRF_COMPAT_DIAGONAL, vec = diag && d_vector;
+    c->h_M.assign(vec ? ld : ld * ld, 0.f);
+    for (int l = 0; l < K; l++) {
+        if (diag) c->h_M[vec ? l : l * ld + l] = host_values[l];
+        else
+            for (int k = 0; k < K; k++) c->h_M[k * ld + l] = host_values[(size_t)l * K + k];      // (transposed)
+    }
+    CHIP(c, hipSetDevice(c->device));
+    // (synchronous: the weights may not change under a step still in flight, and host_values may be freed on return)
+    CHIP(c, hipDeviceSynchronize());
+    CHIP(c, hipMemcpy(vec ? d_vector : d_matrix, c->h_M.data(), sizeof(float) * c->h_M.size(), hipMemcpyHostToDevice));
+    return PNP_OK;
+}
+
+}  // namespace
+
 extern "C" int pnp_crf_set_term_compat(pnp_crf* c, int32_t term, int32_t kind, const float* host_values, int32_t K) {
     if (!c) return PNP_ERR_ARG;
     if (term < 0 || term >= PNP_CRF_MAX_TERMS || term >= c->max_terms)
@@ -558,23 +598,11 @@ extern "C" int pnp_crf_set_term_compat(pnp_crf* c, int32_t term, int32_t kind, c
         c->tcompat_K[term] = 0;
         return PNP_OK;
     }
-    if (kind != PNP_CRF_COMPAT_DIAGONAL && kind != PNP_CRF_COMPAT_MATRIX)
-        return cfail(c, PNP_ERR_ARG, "kind = %d: scalar (0), diagonal (1) or matrix (2)", kind);
-    if (!host_values) return cfail(c, PNP_ERR_ARG, "compatibility values are null");
-    if (K < 2 || K > c->maxK) return cfail(c, PNP_ERR_ARG, "compatibility for %d labels, the solver holds 2..%d", K, c->maxK);
-    if (!c->d_TM || !c->d_Tvec) return cfail(c, PNP_ERR_STATE, "the solver's workspace was not allocated (pnp_crf_create_terms failed)");
     const size_t ld = (size_t)c->ldm;
-    const bool diag = kind == PNP_CRF_COMPAT_DIAGONAL;
-    c->h_M.assign(diag ? ld : ld * ld, 0.f);
-    for (int l = 0; l < K; l++) {
-        if (diag) c->h_M[l] = host_values[l];
-        else
-            for (int k = 0; k < K; k++) c->h_M[k * ld + l] = host_values[(size_t)l * K + k];      // (transposed)
-    }
-    CHIP(c, hipSetDevice(c->device));
-    // (synchronous, as pnp_crf_set_compat: the weights may not change under a step still in flight)
-    CHIP(c, hipDeviceSynchronize());
-    CHIP(c, hipMemcpy(diag ? c->d_Tvec + term * ld : c->d_TM + term * ld * ld, c->h_M.data(), sizeof(float) * c->h_M.size(), hipMemcpyHostToDevice));
+    const bool have = c->d_TM && c->d_Tvec;
+    if (int r = crf_upload_compat(c, kind, host_values, K, "pnp_crf_create_terms", have ? c->d_TM + term * ld * ld : nullptr,
+                                  have ? c->d_Tvec + term * ld : nullptr))
+        return r;
     c->tkind[term] = kind;
     c->tcompat_K[term] = K;
     return PNP_OK;
@@ -605,22 +633,8 @@ extern "C" int pnp_crf_set_compat(pnp_crf* c, int32_t term, int32_t kind, const 
         c->m_scalar[term] = false;
         return PNP_OK;
     }
-    if (kind != PNP_CRF_COMPAT_DIAGONAL && kind != PNP_CRF_COMPAT_MATRIX)
-        return cfail(c, PNP_ERR_ARG, "kind = %d: scalar (0), diagonal (1) or matrix (2)", kind);
-    if (!host_values) return cfail(c, PNP_ERR_ARG, "compatibility values are null");
-    if (K < 2 || K > c->maxK) return cfail(c, PNP_ERR_ARG, "compatibility for %d labels, the solver holds 2..%d", K, c->maxK);
-    if (!c->d_M) return cfail(c, PNP_ERR_STATE, "the solver's workspace was not allocated (pnp_crf_create failed)");
     const size_t ld = (size_t)c->ldm;
-    c->h_M.assign(ld * ld, 0.f);
-    for (int l = 0; l < K; l++) {
-        if (kind == PNP_CRF_COMPAT_DIAGONAL) c->h_M[l * ld + l] = host_values[l];
-        else
-            for (int k = 0; k < K; k++) c->h_M[k * ld + l] = host_values[(size_t)l * K + k];      // (transposed)
-    }
-    CHIP(c, hipSetDevice(c->device));
-    // (synchronous: the matrix may not change under a step still in flight, and host_values may be freed on return)
-    CHIP(c, hipDeviceSynchronize());
-    CHIP(c, hipMemcpy(c->d_M + term * ld * ld, c->h_M.data(), sizeof(float) * ld * ld, hipMemcpyHostToDevice));
+    if (int r = crf_upload_compat(c, kind, host_values, K, "pnp_crf_create", c->d_M ? c->d_M + term * ld * ld : nullptr, nullptr)) return r;
     c->kind[term] = kind;
     c->compat_K[term] = K;
     c->m_scalar[term] = false;
@@ -641,16 +655,22 @@ int crf_need_kind(pnp_crf* c, bool terms, const char* call) {
     return cfail(c, PNP_ERR_STATE, "%s needs a two-term batch (pnp_crf_set_batch); the batch set has feature terms (pnp_crf_infer_terms / _step_terms)", call);
 }
 
-// Both terms as matrices on the device: a term left scalar as w * I.  Vector / matrix kinds fix the label count of the batch
+// A vector or matrix compatibility fixes the label count of the batch: every image has the K it was set for.  whose: the
+// term as the message names it
+int crf_compat_labels(pnp_crf* c, const char* whose, int K) {
+    for (int i = 0; i < c->B; i++)
+        if (c->desc[i].K != K)
+            return cfail(c, PNP_ERR_ARG, "%s's compatibility is for %d labels, image %d of the batch has %d: a vector or matrix "
+                         "compatibility needs that many labels in every image", whose, K, i, c->desc[i].K);
+    return PNP_OK;
+}
+
+// Both terms as matrices on the device: a term left scalar as w * I
 int crf_matrices(pnp_crf* c, float pos_w, float bi_w, hipStream_t s) {
     const size_t ld = (size_t)c->ldm;
     for (int t = 0; t < 2; t++) {
         if (c->kind[t] != PNP_CRF_COMPAT_SCALAR) {
-            for (int i = 0; i < c->B; i++)
-                if (c->desc[i].K != c->compat_K[t])
-                    return cfail(c, PNP_ERR_ARG, "the %s term's compatibility is for %d labels, image %d of the batch has %d: a vector or "
-                                 "matrix compatibility needs that many labels in every image", t == 0 ? "Gaussian" : "bilateral",
-                                 c->compat_K[t], i, c->desc[i].K);
+            if (int r = crf_compat_labels(c, t == 0 ? "the Gaussian term" : "the bilateral term", c->compat_K[t])) return r;
             continue;
         }
         const float w = t == 0 ? pos_w : bi_w;
@@ -682,7 +702,7 @@ CrfSpan crf_span(const pnp_crf* c) { return CrfSpan{c->d_desc, 0, c->B, c->kp_ma
 
 // Q0 = softmax(-U)
 int crf_start(pnp_crf* c, hipStream_t s, const CrfLabelOut& lab) {
-    CK(c, crf_meanfield(c->ws, crf_span(c), true, 0, 0.f, 0.f, nullptr, nullptr, 0, s, lab));
+    CK(c, crf_meanfield_start(c->ws, crf_span(c), s, lab));
     c->started = true;
     return PNP_OK;
 }
@@ -694,74 +714,83 @@ int crf_step(pnp_crf* c, int n, float pos_w, float bi_w, hipStream_t s, const Cr
     const size_t ld = (size_t)c->ldm;
     if (!potts && n > 0)
         if (int r = crf_matrices(c, pos_w, bi_w, s)) return r;
-    CK(c, crf_meanfield(c->ws, crf_span(c), false, n, pos_w, bi_w, potts ? nullptr : c->d_M, c->d_M + ld * ld, (int)ld, s, lab));
+    CK(c, crf_meanfield(c->ws, crf_span(c), n, CrfPairRun{pos_w, bi_w, potts ? nullptr : c->d_M, c->d_M + ld * ld, (int)ld}, s, lab));
     return PNP_OK;
 }
 
-// What crf_meanfield / crf_meanfield_backward take of the T terms of the batch: descriptors and compatibilities, [PNP_CRF_MAX_TERMS] each
-int crf_terms_args(pnp_crf* c, const PostDesc** desc, const float** wvec, const float** MT) {
-    const size_t ld = (size_t)c->ldm;
-    for (int t = 0; t < c->T; t++) {
-        if (c->tkind[t] != PNP_CRF_COMPAT_SCALAR)
-            for (int i = 0; i < c->B; i++)
-                if (c->desc[i].K != c->tcompat_K[t])
-                    return cfail(c, PNP_ERR_ARG, "term %d's compatibility is for %d labels, image %d of the batch has %d: a vector or matrix "
-                                 "compatibility needs that many labels in every image", t, c->tcompat_K[t], i, c->desc[i].K);
-        desc[t] = c->d_tdesc + (size_t)t * c->maxB;
-        wvec[t] = c->tkind[t] == PNP_CRF_COMPAT_DIAGONAL ? c->d_Tvec + t * ld : nullptr;
-        MT[t] = c->tkind[t] == PNP_CRF_COMPAT_MATRIX ? c->d_TM + t * ld * ld : nullptr;
-    }
+// The marginals out: the rows of Q into the caller's planes (d_q null: not asked for)
+int crf_emit_q(pnp_crf* c, float* d_q, hipStream_t s) {
+    if (d_q) CK(c, crf_planes_rows(false, c->d_desc, d_q, c->ws.Q, c->B, c->maxHW, c->kp_max, s));
     return PNP_OK;
 }
 
-// n updates of the T feature terms from the current Q; weights[t]: the weight of a term left scalar
-int crf_step_terms(pnp_crf* c, int n, const float* weights, hipStream_t s, const CrfLabelOut& lab) {
+// What crf_meanfield_terms / crf_meanfield_backward take of the T terms of the batch (`run`), and the arrays it points into:
+// descriptors and compatibilities per term.  weights[t]: the weight of a term left scalar
+struct CrfTermsArgs {
     const PostDesc* desc[PNP_CRF_MAX_TERMS];
     const float *wvec[PNP_CRF_MAX_TERMS], *MT[PNP_CRF_MAX_TERMS];
-    if (int r = crf_terms_args(c, desc, wvec, MT)) return r;
-    const CrfTermsRun run{c->T, desc, weights, wvec, MT, c->ldm};
-    CK(c, crf_meanfield(c->ws, crf_span(c), false, n, 0.f, 0.f, nullptr, nullptr, 0, s, lab, &run));
+    CrfTermsRun run;
+    int fill(pnp_crf* c, const float* weights) {
+        const size_t ld = (size_t)c->ldm;
+        for (int t = 0; t < c->T; t++) {
+            char whose[16];
+            snprintf(whose, sizeof(whose), "term %d", t);
+            if (c->tkind[t] != PNP_CRF_COMPAT_SCALAR)
+                if (int r = crf_compat_labels(c, whose, c->tcompat_K[t])) return r;
+            desc[t] = c->d_tdesc + (size_t)t * c->maxB;
+            wvec[t] = c->tkind[t] == PNP_CRF_COMPAT_DIAGONAL ? c->d_Tvec + t * ld : nullptr;
+            MT[t] = c->tkind[t] == PNP_CRF_COMPAT_MATRIX ? c->d_TM + t * ld * ld : nullptr;
+        }
+        run = CrfTermsRun{c->T, desc, weights, wvec, MT, c->ldm};
+        return PNP_OK;
+    }
+};
+
+// n updates of the T feature terms from the current Q
+int crf_step_terms(pnp_crf* c, int n, const float* weights, hipStream_t s, const CrfLabelOut& lab) {
+    CrfTermsArgs a;
+    if (int r = a.fill(c, weights)) return r;
+    CK(c, crf_meanfield_terms(c->ws, crf_span(c), n, a.run, s, lab));
     return PNP_OK;
+}
+
+// pnp_crf_infer_terms (`call`), and pnp_crf_infer_terms_saved (saved): the same launches one update at a time, the rows of Q
+// copied out to d_history in between
+int crf_infer_terms(pnp_crf* c, const char* call, bool saved, int32_t iters, const float* weights, float* d_history, float* d_q,
+                    uint8_t* d_labels, void* stream) {
+    if (iters < 0) return cfail(c, PNP_ERR_ARG, "iters = %d", iters);
+    if (!weights) return cfail(c, PNP_ERR_ARG, "weights is null (one float per term)");
+    if (saved && !d_history) return cfail(c, PNP_ERR_ARG, "d_history is null (iters + 1 blocks of the batch's row floats)");
+    if (int r = crf_need_batch(c)) return r;
+    if (int r = crf_need_kind(c, true, call)) return r;
+    hipStream_t s = (hipStream_t)stream;
+    CHIP(c, hipSetDevice(c->device));
+    const CrfLabelOut lab = crf_labels(c, d_labels);
+    const size_t qbytes = c->q_floats * sizeof(float);
+    if (int r = crf_start(c, s, iters == 0 ? lab : CrfLabelOut())) return r;
+    if (!saved) {
+        if (int r = crf_step_terms(c, iters, weights, s, lab)) return r;
+        return crf_emit_q(c, d_q, s);
+    }
+    CHIP(c, hipMemcpyAsync(d_history, c->ws.Q, qbytes, hipMemcpyDeviceToDevice, s));
+    for (int it = 1; it <= iters; it++) {
+        if (int r = crf_step_terms(c, 1, weights, s, it == iters ? lab : CrfLabelOut())) return r;
+        CHIP(c, hipMemcpyAsync(d_history + (size_t)it * c->q_floats, c->ws.Q, qbytes, hipMemcpyDeviceToDevice, s));
+    }
+    return crf_emit_q(c, d_q, s);
 }
 
 }  // namespace
 
 extern "C" int pnp_crf_infer_terms(pnp_crf* c, int32_t iters, const float* weights, float* d_q, uint8_t* d_labels, void* stream) {
     if (!c) return PNP_ERR_ARG;
-    if (iters < 0) return cfail(c, PNP_ERR_ARG, "iters = %d", iters);
-    if (!weights) return cfail(c, PNP_ERR_ARG, "weights is null (one float per term)");
-    if (int r = crf_need_batch(c)) return r;
-    if (int r = crf_need_kind(c, true, "pnp_crf_infer_terms")) return r;
-    hipStream_t s = (hipStream_t)stream;
-    CHIP(c, hipSetDevice(c->device));
-    const CrfLabelOut lab = crf_labels(c, d_labels);
-    if (int r = crf_start(c, s, iters == 0 ? lab : CrfLabelOut())) return r;
-    if (int r = crf_step_terms(c, iters, weights, s, lab)) return r;
-    if (d_q) CK(c, crf_planes_rows(false, c->d_desc, d_q, c->ws.Q, c->B, c->maxHW, c->kp_max, s));
-    return PNP_OK;
+    return crf_infer_terms(c, "pnp_crf_infer_terms", false, iters, weights, nullptr, d_q, d_labels, stream);
 }
 
 extern "C" int pnp_crf_infer_terms_saved(pnp_crf* c, int32_t iters, const float* weights, float* d_history, float* d_q, uint8_t* d_labels,
                                          void* stream) {
     if (!c) return PNP_ERR_ARG;
-    if (iters < 0) return cfail(c, PNP_ERR_ARG, "iters = %d", iters);
-    if (!weights) return cfail(c, PNP_ERR_ARG, "weights is null (one float per term)");
-    if (!d_history) return cfail(c, PNP_ERR_ARG, "d_history is null (iters + 1 blocks of the batch's row floats)");
-    if (int r = crf_need_batch(c)) return r;
-    if (int r = crf_need_kind(c, true, "pnp_crf_infer_terms_saved")) return r;
-    hipStream_t s = (hipStream_t)stream;
-    CHIP(c, hipSetDevice(c->device));
-    // pnp_crf_infer_terms' launches one update at a time, the rows of Q copied out in between
-    const CrfLabelOut lab = crf_labels(c, d_labels);
-    const size_t qbytes = c->q_floats * sizeof(float);
-    if (int r = crf_start(c, s, iters == 0 ? lab : CrfLabelOut())) return r;
-    CHIP(c, hipMemcpyAsync(d_history, c->ws.Q, qbytes, hipMemcpyDeviceToDevice, s));
-    for (int it = 1; it <= iters; it++) {
-        if (int r = crf_step_terms(c, 1, weights, s, it == iters ? lab : CrfLabelOut())) return r;
-        CHIP(c, hipMemcpyAsync(d_history + (size_t)it * c->q_floats, c->ws.Q, qbytes, hipMemcpyDeviceToDevice, s));
-    }
-    if (d_q) CK(c, crf_planes_rows(false, c->d_desc, d_q, c->ws.Q, c->B, c->maxHW, c->kp_max, s));
-    return PNP_OK;
+    return crf_infer_terms(c, "pnp_crf_infer_terms_saved", true, iters, weights, d_history, d_q, d_labels, stream);
 }
 
 extern "C" int pnp_crf_reserve_grad(pnp_crf* c) {
@@ -803,10 +832,8 @@ extern "C" int pnp_crf_backward_terms(pnp_crf* c, int32_t iters, const float* we
     if (!c->grad_reserved) return cfail(c, PNP_ERR_STATE, "the gradient workspace is not allocated: call pnp_crf_reserve_grad first");
     hipStream_t s = (hipStream_t)stream;
     CHIP(c, hipSetDevice(c->device));
-    const PostDesc* desc[PNP_CRF_MAX_TERMS];
-    const float *wvec[PNP_CRF_MAX_TERMS], *MT[PNP_CRF_MAX_TERMS];
-    if (int r = crf_terms_args(c, desc, wvec, MT)) return r;
-    const CrfTermsRun run{c->T, desc, weights, wvec, MT, c->ldm};
+    CrfTermsArgs a;
+    if (int r = a.fill(c, weights)) return r;
     int psz[PNP_CRF_MAX_TERMS] = {0};
     for (int t = 0; t < c->T; t++) {
         if (!d_grad_compat || !d_grad_compat[t]) continue;
@@ -820,7 +847,7 @@ extern "C" int pnp_crf_backward_terms(pnp_crf* c, int32_t iters, const float* we
     // (pageable host memory is staged at enqueue time: h_tile0 may be rewritten by the next call)
     CHIP(c, hipMemcpyAsync(c->gw.tile0, c->h_tile0.data(), sizeof(int) * (c->B + 1), hipMemcpyHostToDevice, s));
     CK(c, crf_planes_rows(true, c->d_desc, const_cast<float*>(d_grad_q), c->gw.g, c->B, c->maxHW, c->kp_max, s));
-    CK(c, crf_meanfield_backward(c->ws, c->gw, crf_span(c), c->maxHW, iters, run, d_history, c->q_floats, psz, c->h_tile0.data(), s));
+    CK(c, crf_meanfield_backward(c->ws, c->gw, crf_span(c), c->maxHW, iters, a.run, d_history, c->q_floats, psz, c->h_tile0.data(), s));
     CK(c, crf_planes_rows(false, c->d_desc, d_grad_unary, c->gw.gU, c->B, c->maxHW, c->kp_max, s));
     for (int t = 0; t < c->T; t++)
         if (psz[t]) CK(c, crf_grad_emit(c->gw.acc + (size_t)t * c->gw.max_psz, psz[t], d_grad_compat[t], s));
@@ -849,8 +876,7 @@ extern "C" int pnp_crf_infer(pnp_crf* c, int32_t iters, float pos_w, float bi_w,
     const CrfLabelOut lab = crf_labels(c, d_labels);
     if (int r = crf_start(c, s, iters == 0 ? lab : CrfLabelOut())) return r;
     if (int r = crf_step(c, iters, pos_w, bi_w, s, lab)) return r;
-    if (d_q) CK(c, crf_planes_rows(false, c->d_desc, d_q, c->ws.Q, c->B, c->maxHW, c->kp_max, s));
-    return PNP_OK;
+    return crf_emit_q(c, d_q, s);
 }
 
 extern "C" int pnp_crf_start(pnp_crf* c, void* stream) {
@@ -876,7 +902,7 @@ extern "C" int pnp_crf_read(pnp_crf* c, float* d_q, uint8_t* d_labels, void* str
     if (!c->started) return cfail(c, PNP_ERR_STATE, "no inference was started on this batch: call pnp_crf_start (or pnp_crf_infer) first");
     hipStream_t s = (hipStream_t)stream;
     CHIP(c, hipSetDevice(c->device));
-    if (d_q) CK(c, crf_planes_rows(false, c->d_desc, d_q, c->ws.Q, c->B, c->maxHW, c->kp_max, s));
+    if (int r = crf_emit_q(c, d_q, s)) return r;
     if (d_labels) CK(c, argmax_remap(c->ws.Q, c->d_desc, c->d_lut, 0, d_labels, c->d_label_off, 1, 0, c->B, c->maxHW, s));
     return PNP_OK;
 }

@@ -1,7 +1,7 @@
 // Internal to csrc/: the host side of the DenseCRF mean-field, shared by its two owners -- the engine's post-processing
 // (pnp_engine::Post, post.hip) and the stand-alone solver (pnp_crf, crf_op.hip).  Host code only: the kernels and their
-// launchers are in crf.hip and sort.hip (kernels.h).  Functions return PNP_* codes and format no text: each owner keeps its own
-// error buffer, messages and allocator.
+// launchers are in crf_lattice.hip, crf_meanfield.hip, crf_grad.hip and sort.hip (kernels.h).  Functions return PNP_* codes
+// and format no text: each owner keeps its own error buffer, messages and allocator.
 #pragma once
 #include <vector>
 
@@ -10,7 +10,7 @@
 
 namespace pnp {
 
-constexpr int CRF_MAX_IMAGES = 64;                // IMG_BITS of the packed lattice key (crf.hip)
+constexpr int CRF_MAX_IMAGES = 64;                // IMG_BITS of the packed lattice key (crf_lattice.hip)
 constexpr int CRF_MAX_LABELS = 255;               // uint8 labels
 // |coordinate| a bilateral lattice key may reach: 11 bits per coordinate less the d + 1 = 6 of the canonical simplex
 // (lattice_embed_kernel's range flag)
@@ -56,7 +56,7 @@ struct CrfOffsets {                               // running offsets of a batch 
     size_t off = 0, qoff = 0, voff[2] = {0, 0};
 };
 // Where d (H, W, K are set) lies in a batch with `groups` channel groups per row -- pix0, off, G, Kp, qoff, voff -- and `at`
-// advanced past it.  False: beyond the per-image addressing of the iteration kernels (24-bit row ids, 32-bit byte offsets: crf.hip)
+// advanced past it.  False: beyond the per-image addressing of the iteration kernels (24-bit row ids, 32-bit byte offsets: crf_meanfield.hip)
 bool crf_layout_image(PostDesc& d, int groups, CrfOffsets& at);
 
 // Both lattices of a batch (the features are fixed per batch) and their normalisers.  The Gaussian (xy-only) lattice depends on
@@ -92,13 +92,22 @@ struct CrfSpan {                                  // the images [img0, img0 + ni
 };
 // one filter pass per term at the current Q, which stays as it is: *rg / *rb = the filtered values
 int crf_meanfield_filter(const CrfWorkspace& ws, const CrfSpan& v, const float** rg, const float** rb, hipStream_t s);
-// The mean-field on the images of v.  start: Q0 = softmax(-U) first; then n updates from the current Q, each both filters and the
-// Potts kernel with the weights of the call or, with matrices (MgT, MbT, ldm as crf_update_compat takes them; one group only),
-// the compatibility kernel.  labels: the label output of the last update.  terms non-null: each update is instead the T feature
-// terms in order -- filter, then crf_term_update into the logit rows, the last one ending in the softmax -- and the two-term
-// arguments are not read
-int crf_meanfield(const CrfWorkspace& ws, const CrfSpan& v, bool start, int n, float pos_w, float bi_w, const float* MgT, const float* MbT,
-                  int ldm, hipStream_t s, const CrfLabelOut& labels, const CrfTermsRun* terms = nullptr);
+// The mean-field on the images of v, in the order start, updates.  labels: the label output, asked of the launch that leaves
+// the final marginals -- of the start when no update follows, else of the last update.
+// Q0 = softmax(-U)
+int crf_meanfield_start(const CrfWorkspace& ws, const CrfSpan& v, hipStream_t s, const CrfLabelOut& labels);
+// What a two-term update takes: the weights of the Potts kernel or, MgT non-null, the matrices of the compatibility kernel
+// (MgT, MbT, ldm as crf_update_compat takes them; one group only)
+struct CrfPairRun {
+    float pos_w, bi_w;
+    const float *MgT, *MbT;
+    int ldm;
+};
+// n updates from the current Q, each both filters and the update kernel
+int crf_meanfield(const CrfWorkspace& ws, const CrfSpan& v, int n, const CrfPairRun& run, hipStream_t s, const CrfLabelOut& labels);
+// n updates from the current Q, each the T feature terms in order -- filter, then crf_term_update into the logit rows, the last
+// one ending in the softmax
+int crf_meanfield_terms(const CrfWorkspace& ws, const CrfSpan& v, int n, const CrfTermsRun& terms, hipStream_t s, const CrfLabelOut& labels);
 
 // The gradient workspace of a solver of feature terms (pnp_crf_reserve_grad): rows as Q -- g (the cotangent of the marginals,
 // rewritten in place update by update), dl, h, gU (the unary gradient) --, the per-tile partials of one term's compatibility
@@ -110,7 +119,7 @@ struct CrfGradWorkspace {
     int* tile0 = nullptr;
     size_t part_cap = 0, max_psz = 0;
 };
-// Reverse mode over n updates of the T feature terms of `terms` on the images of v (crf_meanfield with terms).  history: the
+// Reverse mode over n updates of the T feature terms of `terms` on the images of v (crf_meanfield_terms).  history: the
 // n + 1 iterates Q_0 .. Q_n, q_floats apart, as ws.Q held them; gw.g: the cotangent of Q_n on entry.  On return gw.gU holds the
 // gradient of the unary rows and, for every term with psz[t] > 0 (1, K or K * K: the floats of its compatibility), gw.acc +
 // t * gw.max_psz the fp64 gradient of its compatibility; only those terms pay a forward filter per update.  h_tile0: tile0 on

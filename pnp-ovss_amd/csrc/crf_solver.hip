@@ -12,20 +12,21 @@ std::vector<CrfAlloc> crf_reserve_plan(CrfWorkspace& ws, size_t B, size_t TP, si
     auto want = [&plan](size_t count, bool zero, auto**... dst) {      // `count` elements for each of dst, in order
         (plan.push_back({reinterpret_cast<void**>(dst), count * sizeof(**dst), zero}), ...);
     };
-    want(TP * Kp * groups, false, &ws.unary, &ws.Q);
-    want(TP, false, &ws.norm[0], &ws.norm[1]);
-    for (int t = 0; t < 2; t++) {
-        CrfLattice& L = ws.lat[t];
-        L.D1 = t == 0 ? 3 : 6;
-        L.which = t;
-        L.cap = TP * L.D1;
+    auto want_lattice = [&](CrfLattice& L, size_t D1, int which) {     // a lattice's arrays for D1 points per pixel at most
+        L.D1 = (int)D1;
+        L.which = which;
+        L.cap = TP * D1;
         want(L.cap, false, &L.bary, &L.vals, &L.ent, &L.offset);
         want(L.cap + 1, false, &L.seg_start);
         want(L.cap, false, &L.seg_lo, &L.seg_hi, &L.ukeys);
         want(B + 1, false, &L.idbase);
-        want(L.cap * L.D1, false, &L.n1, &L.n2);
-        want(L.cap * (L.D1 / 2), false, &L.nbr8);
-    }
+        want(L.cap * D1, false, &L.n1, &L.n2);
+        want(L.cap * (D1 / 2), false, &L.nbr8);
+    };
+    want(TP * Kp * groups, false, &ws.unary, &ws.Q);
+    want(TP, false, &ws.norm[0], &ws.norm[1]);
+    want_lattice(ws.lat[0], 3, 0);
+    want_lattice(ws.lat[1], 6, 1);
     // feature terms: every lattice for the worst case of max_dims + 1 points per pixel
     const size_t tD1 = max_terms ? max_dims + 1 : 0;
     ws.max_terms = (int)max_terms;
@@ -34,16 +35,7 @@ std::vector<CrfAlloc> crf_reserve_plan(CrfWorkspace& ws, size_t B, size_t TP, si
     ws.tnorm.assign(max_terms, nullptr);
     ws.tlat_points.assign(max_terms, 0);
     for (size_t t = 0; t < max_terms; t++) {
-        CrfLattice& L = ws.tlat[t];
-        L.D1 = (int)tD1;                          // (crf_build_terms sets the term's own d + 1)
-        L.which = 1;
-        L.cap = TP * tD1;
-        want(L.cap, false, &L.bary, &L.vals, &L.ent, &L.offset);
-        want(L.cap + 1, false, &L.seg_start);
-        want(L.cap, false, &L.seg_lo, &L.seg_hi, &L.ukeys);
-        want(B + 1, false, &L.idbase);
-        want(L.cap * tD1, false, &L.n1, &L.n2);
-        want(L.cap * (tD1 / 2), false, &L.nbr8);
+        want_lattice(ws.tlat[t], tD1, 1);         // (crf_build_terms sets the term's own d + 1)
         want(TP, false, &ws.tnorm[t]);
     }
     if (max_terms) want(TP * Kp * groups, false, &ws.logit);
@@ -81,6 +73,23 @@ bool crf_layout_image(PostDesc& d, int groups, CrfOffsets& at) {
     return n * 6 < (1 << 24) && n * 6 * d.Kp * 4 < ((int64_t)1 << 32);
 }
 
+// One lattice of a batch and its normaliser: over the feature planes d_feat or, null, over the pixel positions and d_rgb with
+// the widths sxy, srgb.  A raised key-range flag is cleared on the device: *raised, PNP_ERR_ARG
+static int crf_build_one(CrfWorkspace& ws, CrfLattice& L, float* norm, int* points, const PostDesc* d_desc, const PostDesc* h_desc, int B,
+                         size_t total_pix, int maxHW, const uint8_t* d_rgb, const float* sxy, const float* srgb, const float* d_feat,
+                         bool* raised, hipStream_t s) {
+    const size_t entries = total_pix * L.D1;
+    int range_err = 0;
+    if (int r = d_feat ? crf_build_lattice_features(L.D1 - 1, L, d_desc, h_desc, d_feat, B, entries, maxHW, ws.scratch, &range_err, points, s)
+                       : crf_build_lattice(L.D1 - 1, L, d_desc, h_desc, d_rgb, sxy, srgb, B, entries, maxHW, ws.scratch, &range_err, points, s))
+        return r;
+    if (int r = crf_lattice_norm(L, d_desc, B, maxHW, entries, ws.va, ws.vb, norm, s)) return r;
+    *raised = range_err != 0;
+    if (!range_err) return PNP_OK;
+    (void)hipMemsetAsync(ws.scratch.range_err, 0, sizeof(int), s);
+    return PNP_ERR_ARG;
+}
+
 int crf_build(CrfWorkspace& ws, const PostDesc* d_desc, const PostDesc* h_desc, int B, size_t total_pix, int maxHW, const uint8_t* d_rgb,
               const float pos_xy[2], const float bi_xy[2], const float bi_rgb[3], int* range_term, hipStream_t s) {
     std::vector<double> sig = {pos_xy[0], pos_xy[1]};
@@ -89,17 +98,14 @@ int crf_build(CrfWorkspace& ws, const PostDesc* d_desc, const PostDesc* h_desc, 
     for (int t = 0; t < 2; t++) {
         if (t == 0 && sig == ws.gauss_sig) continue;
         if (t == 0) ws.gauss_sig.clear();         // until the new one stands
-        const size_t entries = total_pix * ws.lat[t].D1;
-        int range_err = 0;
-        if (int r = crf_build_lattice(ws.lat[t].D1 - 1, ws.lat[t], d_desc, h_desc, d_rgb, t == 0 ? pos_xy : bi_xy, bi_rgb, B, entries,
-                                      maxHW, ws.scratch, &range_err, &ws.lat_points[t], s))
+        bool raised = false;
+        if (int r = crf_build_one(ws, ws.lat[t], ws.norm[t], &ws.lat_points[t], d_desc, h_desc, B, total_pix, maxHW, d_rgb,
+                                  t == 0 ? pos_xy : bi_xy, bi_rgb, nullptr, &raised, s)) {
+            if (raised) {                         // leave no stale state behind
+                ws.gauss_sig.clear();
+                *range_term = t;
+            }
             return r;
-        if (int r = crf_lattice_norm(ws.lat[t], d_desc, B, maxHW, entries, ws.va, ws.vb, ws.norm[t], s)) return r;
-        if (range_err) {                          // leave no stale state behind
-            ws.gauss_sig.clear();
-            (void)hipMemsetAsync(ws.scratch.range_err, 0, sizeof(int), s);
-            *range_term = t;
-            return PNP_ERR_ARG;
         }
         if (t == 0) ws.gauss_sig = sig;
     }
@@ -112,17 +118,12 @@ int crf_build_terms(CrfWorkspace& ws, const PostDesc* d_desc, const PostDesc* h_
     if (T < 1 || T > ws.max_terms) return PNP_ERR_ARG;
     for (int t = 0; t < T; t++) {
         if (dims[t] < 1 || dims[t] > ws.max_dims) return PNP_ERR_ARG;
-        CrfLattice& L = ws.tlat[t];
-        L.D1 = dims[t] + 1;
-        const size_t entries = total_pix * L.D1;
-        int range_err = 0;
-        if (int r = crf_build_lattice_features(dims[t], L, d_desc, h_desc, d_feat[t], B, entries, maxHW, ws.scratch, &range_err, &ws.tlat_points[t], s))
+        ws.tlat[t].D1 = dims[t] + 1;
+        bool raised = false;
+        if (int r = crf_build_one(ws, ws.tlat[t], ws.tnorm[t], &ws.tlat_points[t], d_desc, h_desc, B, total_pix, maxHW, nullptr, nullptr, nullptr,
+                                  d_feat[t], &raised, s)) {
+            if (raised) *range_term = t;
             return r;
-        if (int r = crf_lattice_norm(L, d_desc, B, maxHW, entries, ws.va, ws.vb, ws.tnorm[t], s)) return r;
-        if (range_err) {
-            (void)hipMemsetAsync(ws.scratch.range_err, 0, sizeof(int), s);
-            *range_term = t;
-            return PNP_ERR_ARG;
         }
     }
     return PNP_OK;
@@ -133,34 +134,36 @@ int crf_meanfield_filter(const CrfWorkspace& ws, const CrfSpan& v, const float**
     return crf_filter(ws.lat[1], v.d_desc, v.img0, v.nimg, ws.Q, ws.va, ws.vb, rb, v.kp_max, s);
 }
 
-int crf_meanfield(const CrfWorkspace& ws, const CrfSpan& v, bool start, int n, float pos_w, float bi_w, const float* MgT, const float* MbT,
-                  int ldm, hipStream_t s, const CrfLabelOut& labels, const CrfTermsRun* terms) {
-    if (start)
-        if (int r = crf_update(ws.lat[0], ws.lat[1], v.d_desc, v.img0, v.nimg, ws.vga, ws.va, ws.norm[0], ws.norm[1], ws.unary, ws.Q, 0.f, 0.f,
-                               0, v.kp_max, v.groups, s, n == 0 ? labels : CrfLabelOut()))
-            return r;
+int crf_meanfield_start(const CrfWorkspace& ws, const CrfSpan& v, hipStream_t s, const CrfLabelOut& labels) {
+    return crf_update(ws.lat[0], ws.lat[1], v.d_desc, v.img0, v.nimg, ws.vga, ws.va, ws.norm[0], ws.norm[1], ws.unary, ws.Q, 0.f, 0.f, 0,
+                      v.kp_max, v.groups, s, labels);
+}
+
+int crf_meanfield(const CrfWorkspace& ws, const CrfSpan& v, int n, const CrfPairRun& run, hipStream_t s, const CrfLabelOut& labels) {
     for (int it = 0; it < n; it++) {
-        if (terms) {
-            for (int t = 0; t < terms->T; t++) {
-                const bool first = t == 0, last = t == terms->T - 1;
-                const float* val = nullptr;
-                if (int r = crf_filter(ws.tlat[t], terms->d_desc[t], v.img0, v.nimg, ws.Q, ws.va, ws.vb, &val, v.kp_max, s)) return r;
-                if (int r = crf_term_update(ws.tlat[t], terms->d_desc[t], v.img0, v.nimg, val, ws.tnorm[t], first ? ws.unary : ws.logit, first,
-                                            last ? ws.Q : ws.logit, last, terms->w[t], terms->wvec[t], terms->MT[t], terms->ldm, v.kp_max, s,
-                                            last && it == n - 1 ? labels : CrfLabelOut()))
-                    return r;
-            }
-            continue;
-        }
         const float *rg = nullptr, *rb = nullptr;
         if (int r = crf_meanfield_filter(ws, v, &rg, &rb, s)) return r;
         const CrfLabelOut out = it == n - 1 ? labels : CrfLabelOut();
-        const int r = MgT ? crf_update_compat(ws.lat[0], ws.lat[1], v.d_desc, v.img0, v.nimg, rg, rb, ws.norm[0], ws.norm[1], ws.unary, ws.Q, MgT,
-                                              MbT, ldm, v.kp_max, s, out, nullptr)
-                          : crf_update(ws.lat[0], ws.lat[1], v.d_desc, v.img0, v.nimg, rg, rb, ws.norm[0], ws.norm[1], ws.unary, ws.Q, pos_w, bi_w,
-                                       1, v.kp_max, v.groups, s, out);
+        const int r = run.MgT ? crf_update_compat(ws.lat[0], ws.lat[1], v.d_desc, v.img0, v.nimg, rg, rb, ws.norm[0], ws.norm[1], ws.unary, ws.Q,
+                                                  run.MgT, run.MbT, run.ldm, v.kp_max, s, out, nullptr)
+                              : crf_update(ws.lat[0], ws.lat[1], v.d_desc, v.img0, v.nimg, rg, rb, ws.norm[0], ws.norm[1], ws.unary, ws.Q,
+                                           run.pos_w, run.bi_w, 1, v.kp_max, v.groups, s, out);
         if (r) return r;
     }
+    return PNP_OK;
+}
+
+int crf_meanfield_terms(const CrfWorkspace& ws, const CrfSpan& v, int n, const CrfTermsRun& terms, hipStream_t s, const CrfLabelOut& labels) {
+    for (int it = 0; it < n; it++)
+        for (int t = 0; t < terms.T; t++) {
+            const bool first = t == 0, last = t == terms.T - 1;
+            const float* val = nullptr;
+            if (int r = crf_filter(ws.tlat[t], terms.d_desc[t], v.img0, v.nimg, ws.Q, ws.va, ws.vb, &val, v.kp_max, s)) return r;
+            if (int r = crf_term_update(ws.tlat[t], terms.d_desc[t], v.img0, v.nimg, val, ws.tnorm[t], first ? ws.unary : ws.logit, first,
+                                        last ? ws.Q : ws.logit, last, terms.w[t], terms.wvec[t], terms.MT[t], terms.ldm, v.kp_max, s,
+                                        last && it == n - 1 ? labels : CrfLabelOut()))
+                return r;
+        }
     return PNP_OK;
 }
 
@@ -202,7 +205,7 @@ int crf_meanfield_backward(const CrfWorkspace& ws, const CrfGradWorkspace& gw, c
                 return r;
             }
             const float* valT = nullptr;
-            if (int r = crf_filter_transposed(L, terms.d_desc[t], v.img0, v.nimg, gw.h, ws.va, ws.vb, &valT, v.kp_max, s)) return r;
+            if (int r = crf_filter(L, terms.d_desc[t], v.img0, v.nimg, gw.h, ws.va, ws.vb, &valT, v.kp_max, s, true)) return r;
             if (int r = crf_slice_add(L, terms.d_desc[t], v.img0, v.nimg, valT, ws.tnorm[t], gw.g, t == 0, s)) return r;
         }
     }

@@ -145,12 +145,12 @@ int jpeg_decode(const uint8_t* d_data, const JpegImage* d_imgs, const JpegTables
                 int n_segments, uint8_t* d_clean, int* d_seg_bits, int16_t* d_coef, size_t coef_elems, uint8_t* d_planes, uint8_t* d_rgb,
                 int max_blocks, int max_pixels, int* d_err, hipStream_t s);
 
-// crf.hip
 // sort.hip: stable LSD radix sort of (u64 key, u32 value) pairs and int32 prefix sum (the lattice build's device-wide primitives)
 size_t sort_temp_bytes(size_t n);
 int radix_sort_pairs(uint64_t* keys_in, uint64_t* keys_out, uint32_t* vals_in, uint32_t* vals_out, size_t n, int begin_bit, int end_bit,
                      const size_t* seg_off, int nseg, void* temp, size_t temp_bytes, hipStream_t s);
 int device_scan_i32(const int* in, int* out, size_t n, bool inclusive, void* temp, size_t temp_bytes, hipStream_t s);
+// crf_lattice.hip: the lattice build and the normaliser
 size_t crf_sort_temp_bytes(size_t max_entries);
 // Device scratch of crf_build_lattice, sized once for the largest build: E = (pixels of a batch) x 6 entries of the bilateral
 // lattice (the Gaussian one has 3 per pixel; a workspace with feature terms: x max(6, max_dims + 1), and n1k / n2k that many rows
@@ -185,8 +185,11 @@ int crf_build_lattice_features(int D, const CrfLattice& L, const PostDesc* d_img
 int crf_feature_key_limit(int D);
 int crf_lattice_norm(const CrfLattice& L, const PostDesc* d_imgs, int B, int max_pixels, size_t ent_total, float* va, float* vb,
                      float* norm_out, hipStream_t s);
+// crf_meanfield.hip: the forward mean-field
+// lattice(norm * Q): splat and the d + 1 blur axes; *result = the buffer that holds the filtered values (va or vb).  reverse:
+// lattice^T(norm * Q), the blur axes in reverse order (the adjoint of the filter: the reverse mode's)
 int crf_filter(const CrfLattice& L, const PostDesc* d_imgs, int img0, int nimg, const float* Q,
-               float* va, float* vb, const float** result, int max_kp, hipStream_t s);
+               float* va, float* vb, const float** result, int max_kp, hipStream_t s, bool reverse = false);
 // label output of the LAST mean-field update (argmax over the marginals it has just normalised, np.argmax semantics, remapped
 // through the per-image LUT): lab[g] = label map of channel group g, null = no labels from this launch
 struct CrfLabelOut {
@@ -214,10 +217,7 @@ int crf_update_compat(const CrfLattice& Lg, const CrfLattice& Lb, const PostDesc
 int crf_term_update(const CrfLattice& L, const PostDesc* d_imgs, int img0, int nimg, const float* val, const float* norm, const float* base,
                     bool first, float* out, bool last, float w, const float* wvec, const float* MT, int ldm, int max_kp, hipStream_t s,
                     const CrfLabelOut& labels);
-// ---- reverse mode of the T-term update (crf.hip; the sequence is crf_meanfield_backward of crf_solver.h)
-// lattice^T(norm * rows): crf_filter with the blur axes in reverse order (the adjoint of the filter)
-int crf_filter_transposed(const CrfLattice& L, const PostDesc* d_imgs, int img0, int nimg, const float* rows, float* va, float* vb,
-                          const float** result, int max_kp, hipStream_t s);
+// crf_grad.hip: reverse mode of the T-term update (the sequence is crf_meanfield_backward of crf_solver.h)
 // dl = Q (.) (g - <g, Q>) per pixel; gU -= dl.  Rows as Q
 int crf_softmax_backward(const PostDesc* d_imgs, int img0, int nimg, const float* Q, const float* g, float* dl, float* gU, int max_pixels,
                          int max_kp, hipStream_t s);

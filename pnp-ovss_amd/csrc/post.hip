@@ -1,6 +1,6 @@
 // The post-processing entry points of include/pnp_hip.h (pnp_post_reserve ... pnp_postprocess_pair): token merge, threshold,
 // upsample, blur and DenseCRF of a batch of differently sized images.  Host logic only: the kernels are in
-// pipeline_kernels.hip, crf.hip and sort.hip; the state is pnp_engine::Post (engine.h).  The DenseCRF arrays, lattice build and
+// pipeline_kernels.hip, crf_lattice.hip, crf_meanfield.hip and sort.hip; the state is pnp_engine::Post (engine.h).  The DenseCRF arrays, lattice build and
 // mean-field sequence are crf_solver.h's, shared with the stand-alone solver (crf_op.hip); the engine's own are the chunking, the
 // paired two-group layout, the stage profile and the reference's fixed parameters.
 #include <algorithm>
@@ -299,7 +299,8 @@ static int crf_iterate(pnp_engine* e, CrfSpan v, int32_t iters, float pos_w, flo
     for (int c0 = 0; c0 < p.B; c0 += p.chunk) {
         v.img0 = c0;
         v.nimg = std::min(p.chunk, p.B - c0);
-        KCHK(e, crf_meanfield(p.crf, v, true, iters, pos_w, bi_w, nullptr, nullptr, 0, s, labels));
+        KCHK(e, crf_meanfield_start(p.crf, v, s, iters == 0 ? labels : CrfLabelOut()));
+        KCHK(e, crf_meanfield(p.crf, v, iters, CrfPairRun{pos_w, bi_w, nullptr, nullptr, 0}, s, labels));
     }
     if (timed) {
         crf_timer_stop(e, s);

@@ -1,4 +1,4 @@
-// Device-wide primitives of the DenseCRF lattice build (crf.hip), hand-written for gfx950: a STABLE least-significant-digit
+// Device-wide primitives of the DenseCRF lattice build (crf_lattice.hip), hand-written for gfx950: a STABLE least-significant-digit
 // radix sort of (64-bit key, 32-bit value) pairs and an int32 prefix sum.  Stability is part of the numerical contract: the
 // contributor list of a lattice point must stay in ascending pixel order so that the splat adds in the order of the sequential
 // CPU algorithm (oracle/densecrf_ref.c) -- a sort that is only "a" sort changes Q in the last bit.

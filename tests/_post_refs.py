@@ -1,5 +1,5 @@
 """Case generators, references and planted faults for the post-processing operator tests (test_post_ops_cpu.py,
-test_post_ops_gpu.py): pipeline_kernels.hip, crf.hip and the post-processing entry points of post.hip.
+test_post_ops_gpu.py): pipeline_kernels.hip, crf_lattice.hip / crf_meanfield.hip and the post-processing entry points of post.hip.
 
 The reference is the oracle alone (oracle/pipeline_np.py, `OP.*`): threshold / upsample, blur and labels are compared bit for
 bit, DenseCRF marginals to atol = 1e-6 (the criterion of test_hip_parity.test_postprocess_stages_bit_exact_vs_oracle).
@@ -304,7 +304,7 @@ def drop_maps(kind, P, T, iters=3, seed=0):
 # ------------------------------------------------------------------------------------------ lattice key range
 def bilateral_key_extent(x, y, rgb, sxy=50.0, srgb=5.0):
     """Largest |coordinate| of the six bilateral lattice keys of one pixel, by lattice_embed_kernel's float32 rule
-    (crf.hip; oracle/densecrf_ref.c::lattice_init).  The kernel packs 11 bits per coordinate and refuses a key with
+    (crf_lattice.hip; oracle/densecrf_ref.c::lattice_init).  The kernel packs 11 bits per coordinate and refuses a key with
     |coordinate| >= 2^10 - (D + 1) = 1018."""
     D = 5
     f = [F32(x) / F32(sxy), F32(y) / F32(sxy)] + [F32(c) / F32(srgb) for c in rgb]

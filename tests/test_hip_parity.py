@@ -80,7 +80,7 @@ def _lib():
 @pytest.mark.parametrize("bits", [(0, 8), (0, 32), (0, 61), (3, 46)])
 def test_lattice_sort_pairs_is_a_stable_sort(n, bits):
     """csrc/sort.hip against numpy's stable argsort on the selected key bits: equal keys keep their input order (the order
-    the DenseCRF splat adds a lattice point's contributors in; crf.hip header).  Few distinct keys (heavy ties), keys with
+    the DenseCRF splat adds a lattice point's contributors in; crf_lattice.hip header).  Few distinct keys (heavy ties), keys with
     one digit populated, and random keys."""
     lib = _lib()
     lo, hi = bits

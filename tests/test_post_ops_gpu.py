@@ -1,4 +1,4 @@
-"""GPU: operator-level tests of the post-processing half -- pipeline_kernels.hip, crf.hip and the post-processing entry points
+"""GPU: operator-level tests of the post-processing half -- pipeline_kernels.hip, crf_lattice.hip / crf_meanfield.hip and the post-processing entry points
 of post.hip -- against the oracle (oracle/pipeline_np.py), at the chunkings, arguments, geometries and values no other test
 runs.  Cases, references and planted faults live in tests/_post_refs.py; tests/test_post_ops_cpu.py proves that they
 discriminate.  Everything runs on the 8 x 8 patch grid of blip_itm_small(128) unless stated.
