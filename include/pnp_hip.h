@@ -545,6 +545,34 @@ int pnp_op_gemm_x3(const void* d_A_hi, const void* d_A_lo, int32_t lda, const vo
 int pnp_op_gemm_x3a(const float* d_A, int32_t lda, const void* d_B_hi, const void* d_B_lo, int32_t ldb, int32_t M, int32_t N,
                     int32_t K, const float* d_bias, const float* d_resid, int32_t ldr, float* d_out_f32, int32_t ldo, int32_t mode,
                     float* d_aux, int32_t ld_aux, void* stream);
+/* What the GEMM entry points above would launch for one problem: the library's own dispatch, computed on the host from the
+ * launch's scalars.  Touches no device and takes no device pointer.
+ *   form    : PNP_GEMM_FORM_* -- pnp_op_gemm* with bf16 = 0 / 1, pnp_op_gemm_x3, pnp_op_gemm_x3a
+ *   has     : PNP_GEMM_HAS_* bits, the operands and outputs that are present
+ *   n_cu    : compute units of the device; streamk_mode as pnp_set_tuning("streamk"); sk_wgs: workgroups the stream-K
+ *             workspace was sized for (0 = none; the op-level entry points use n_cu)
+ * plan->status is PNP_OK or the PNP_ERR_ARG the launch would return (also the return value); the other fields then are 0. */
+enum { PNP_GEMM_FORM_F32 = 0, PNP_GEMM_FORM_BF16 = 1, PNP_GEMM_FORM_X3 = 2, PNP_GEMM_FORM_X3A = 3 };
+enum { PNP_GEMM_HAS_BIAS = 1, PNP_GEMM_HAS_BIAS_ON_ROWS = 2, PNP_GEMM_HAS_RESID = 4, PNP_GEMM_HAS_OUT_F32 = 8, PNP_GEMM_HAS_OUT_T = 16,
+       PNP_GEMM_HAS_OUT_LO = 32, PNP_GEMM_HAS_AUX = 64 };
+enum { PNP_GEMM_G64 = 0, PNP_GEMM_G128 = 1, PNP_GEMM_G256 = 2, PNP_GEMM_WIDE = 3, PNP_GEMM_X3_WIDE = 4, PNP_GEMM_SMALL_X3 = 5 };
+typedef struct pnp_gemm_plan {
+    int32_t status;
+    int32_t family;        /* PNP_GEMM_G64 .. PNP_GEMM_SMALL_X3: generic 64 / 128 / 256 tiles, wide bf16, wide split-bf16, text-side split */
+    int32_t variant;       /* wide families: the compile-time epilogue (0 +bias -> bf16 | 1 +bias GELU -> bf16 | 2 +bias +resid -> fp32 |
+                            * 3 token columns -> bf16 | 4 +bias -> fp32 | 5 token columns -> fp32 | 6 +bias GELU -> pair | 7 +bias -> pair);
+                            * PNP_GEMM_SMALL_X3: 0 = 32-deep slabs, three-slot ring | 1 = 64-deep slabs | 2 = 32-deep slabs; else 0 */
+    int32_t dtype_bf16;    /* effective operand type of the kernel (1 for the wide split form whatever was asked) */
+    int32_t n_pad;         /* N rounded up to the family's column tile */
+    int32_t grid, block, smem;     /* workgroups, threads per workgroup, bytes of dynamic LDS */
+    int32_t keeps_stamps;  /* the launch records clock stamps while "gemm_stamps" is on (at most 8192 workgroups) */
+    int32_t profiled;      /* the launch belongs to the families pnp_profile_enable brackets */
+    int32_t sk_full, sk_upw;       /* stream-K: tiles walked whole, slab pairs per workgroup in the split tail (0, 0 = whole tiles only).
+                                    * A stream that is being captured runs the plan of streamk_mode 0 instead */
+} pnp_gemm_plan;
+int pnp_op_gemm_plan(int32_t form, int32_t M, int32_t N, int32_t K, int32_t lda, int32_t ldb, int32_t mode, int32_t has,
+                     int32_t row_div, int32_t col_div, int32_t col_pad, int32_t n_cu, int32_t streamk_mode, int32_t sk_wgs,
+                     pnp_gemm_plan* plan);
 /* ViT self-attention of one block (B/vit.py:93-117): ctx = softmax(q k^T * scale) v per (image, head), head_dim 64.
  * d_qk [B*N, ld_qk]: q of head h at column h*64, k at column D + h*64; d_ctx [B*N, D].
  * fp32 mode: d_vt [D, ld_vt] = V^T, row h*64+d, column b*n_pad + token (n_pad a multiple of 64, pad columns zero).

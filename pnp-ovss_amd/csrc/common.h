@@ -210,8 +210,7 @@ static inline int current_device() {
 
 // `done`: one bit per device ordinal, owned by the call site (function-local static).  hipFuncSetAttribute is idempotent, so two
 // threads that race on the first call of a device both set it.
-static inline int lds_opt_in(std::atomic<uint32_t>& done, const void* kernel, int bytes) {
-    const int d = current_device();
+static inline int lds_opt_in(std::atomic<uint32_t>& done, const void* kernel, int bytes, int d = current_device()) {
     if (d < 0) return -5;
     if (done.load(std::memory_order_acquire) & (1u << d)) return 0;
     if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) return -5;
@@ -220,9 +219,8 @@ static inline int lds_opt_in(std::atomic<uint32_t>& done, const void* kernel, in
 }
 
 // compute units of the current device (0: the query failed; not cached then)
-static inline int device_cu_count() {
+static inline int device_cu_count(int d = current_device()) {
     static std::atomic<int> cus[kMaxDevices];
-    const int d = current_device();
     if (d < 0) return 0;
     int n = cus[d].load(std::memory_order_relaxed);
     if (n) return n;

@@ -2,6 +2,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
+
+#include "../../include/pnp_hip.h"
+
 namespace pnp {
 
 enum { GEMM_EPI_LINEAR = 0, GEMM_EPI_GELU = 1, GEMM_EPI_GELU_GRAD = 2 };
@@ -61,6 +65,21 @@ struct GemmArgs {
     int reserved = 0;              // unused: keeps sizeof(GemmArgs) and with it the offsets of the hidden kernel arguments (grid size),
                                    // which sit behind the struct in the kernarg segment
 };
+
+// the kernels take the struct by value and the hidden kernel arguments sit behind it (see `reserved`)
+static_assert(sizeof(GemmArgs) == 232 && offsetof(GemmArgs, sk_part) == 184 && offsetof(GemmArgs, stamps) == 216,
+              "GemmArgs layout is part of the kernels' argument segment");
+
+// Everything gemm_nt decides about one launch, from the launch's scalars alone (no HIP call, no global): the argument checks,
+// the kernel (family + variant), N rounded to its tile, grid / block / LDS bytes and the stream-K split it would take on
+// n_cu compute units with a workspace of sk_wgs workgroups under streamk_mode.  Fields: include/pnp_hip.h (pnp_gemm_plan).
+typedef pnp_gemm_plan GemmPlan;
+// variants of PNP_GEMM_SMALL_X3: 32-deep slabs on a three-slot ring | 64-deep slabs | 32-deep slabs (four slots)
+enum { SMALL_X3_K32_NS3 = 0, SMALL_X3_K64 = 1, SMALL_X3_K32 = 2 };
+// rows of the clock-stamp buffer (gemm_set_stamps): one per workgroup.  The persistent kernels launch at most one workgroup per CU
+// (and the stream-K rows sit at grid + block id); the generic kernels launch one per tile, with no bound
+constexpr int kStampBlocks = 8192;
+GemmPlan gemm_plan(int dtype_bf16, const GemmArgs& g, int n_cu, int streamk_mode, int sk_wgs);
 
 int gemm_nt(int dtype_bf16, GemmArgs g, hipStream_t s);
 

@@ -309,21 +309,6 @@ __global__ __launch_bounds__((BM / WTM) * (BN / WTN) * 64) void gemm_nt_big_kern
     }
 }
 
-// rows of the clock-stamp buffer (gemm_set_stamps): one per workgroup.  The persistent kernels launch at most one workgroup per CU
-// (and the stream-K rows sit at grid + block id); the generic kernel launches one per tile, with no bound
-static constexpr int kStampBlocks = 8192;
-
-template <typename T, int BM, int BN, int WTM, int WTN, int NS, bool PIPE = true>
-static int launch_big(GemmArgs g, hipStream_t s) {
-    const int nbm = (g.M + BM - 1) / BM, nbn = g.N / BN;
-    if ((long)nbm * nbn > kStampBlocks) g.stamps = nullptr;            // more workgroups than stamp rows: this launch records none
-    const size_t smem = (size_t)NS * (BM + BN) * 128;
-    static std::atomic<uint32_t> opted{0};            // per device ordinal (common.h: lds_opt_in)
-    if (lds_opt_in(opted, reinterpret_cast<const void*>(gemm_nt_big_kernel<T, BM, BN, WTM, WTN, NS, PIPE>), (int)smem) != PNP_OK) return PNP_ERR_HIP;
-    hipLaunchKernelGGL((gemm_nt_big_kernel<T, BM, BN, WTM, WTN, NS, PIPE>), dim3(nbm * nbn), dim3((BM / WTM) * (BN / WTN) * 64), smem, s, g);
-    return hipGetLastError() == hipSuccess ? PNP_OK : PNP_ERR_HIP;
-}
-
 // ------------------------------------------------------------------------------------------
 // Wide-tile bf16 kernel: 256 x 256 block tile, 8 waves (2 x 4) of 128 x 64, v_mfma_f32_32x32x16_bf16,
 // PERSISTENT: one workgroup per CU walks tiles blockIdx.x, blockIdx.x + gridDim.x, ...
@@ -723,48 +708,6 @@ __global__ __launch_bounds__(512) void gemm_nt_wide_kernel(const GemmArgs g) {
     }
 }
 
-// the wide kernel's compile-time epilogues cover the ViT block's dense layers; anything else (row / column
-// remaps, per-row bias, stashes, dual outputs) stays on the generic kernels
-static int wide_epilogue_kind(const GemmArgs& g) {
-    if (g.aux || g.row_div) return -1;
-    // the token-column epilogues store token PAIRS when col_div is even (pairs then never straddle an image): N has to be even
-    // too, or the last pair would write column N.  Otherwise the generic kernels take the launch (no split-bf16 form: refused)
-    const bool pair_ok = (g.col_div & 1) || !(g.Nvalid & 1);
-    if (g.A_lo || g.B_lo) {                         // split-bf16 operands: the fp32-facing epilogues
-        if (!g.A_lo || !g.B_lo) return -1;
-        if (g.mode == GEMM_EPI_LINEAR && !g.resid && g.out_f32 && !g.out_t && (g.bias_on_rows || !g.bias) && (g.col_div > 0 || g.bias_on_rows) &&
-            pair_ok)
-            return WIDE_TOKCOLS_F32;
-        if (g.col_div || g.bias_on_rows || (g.Nvalid & 3)) return -1;
-        if (g.mode == GEMM_EPI_LINEAR && g.resid && g.out_f32 && !g.out_t) return WIDE_RESID_F32;
-        if (g.mode == GEMM_EPI_LINEAR && !g.resid && g.out_f32 && !g.out_t) return WIDE_BIAS_F32;
-        if (g.mode == GEMM_EPI_GELU && !g.resid && g.out_t && g.out_lo && !g.out_f32) return WIDE_GELU_SPLIT;
-        if (g.mode == GEMM_EPI_LINEAR && !g.resid && g.out_t && g.out_lo && !g.out_f32) return WIDE_SPLIT;
-        return -1;
-    }
-    if (g.mode == GEMM_EPI_LINEAR && !g.resid && g.out_t && !g.out_f32 && (g.bias_on_rows || !g.bias) && (g.col_div > 0 || g.bias_on_rows) &&
-        pair_ok)
-        return WIDE_TOKCOLS_BF16;
-    if (g.col_div || g.bias_on_rows || (g.Nvalid & 3)) return -1;
-    if (g.mode == GEMM_EPI_LINEAR && !g.resid && g.out_t && !g.out_f32) return WIDE_BF16;
-    if (g.mode == GEMM_EPI_GELU && !g.resid && g.out_t && !g.out_f32) return WIDE_GELU_BF16;
-    if (g.mode == GEMM_EPI_LINEAR && g.resid && g.out_f32 && !g.out_t) return WIDE_RESID_F32;
-    return -1;
-}
-
-template <int EPI>
-static int launch_wide(const GemmArgs& g, hipStream_t s) {
-    const int nbm = (g.M + 255) / 256, nbn = g.N / 256;
-    const int n_cu = device_cu_count();
-    if (!n_cu) return PNP_ERR_HIP;
-    static std::atomic<uint32_t> opted{0};            // per device ordinal (common.h: lds_opt_in)
-    if (lds_opt_in(opted, reinterpret_cast<const void*>(gemm_nt_wide_kernel<EPI>), kWideSmem) != PNP_OK) return PNP_ERR_HIP;
-    const int ntiles = nbm * nbn;
-    const int grid = ntiles > n_cu ? n_cu : ntiles;      // one workgroup per CU (LDS-limited) walks the tiles
-    hipLaunchKernelGGL((gemm_nt_wide_kernel<EPI>), dim3(grid), dim3(512), kWideSmem, s, g);
-    return hipGetLastError() == hipSuccess ? PNP_OK : PNP_ERR_HIP;
-}
-
 // ------------------------------------------------------------------------------------------
 // Text-side GEMM of the split-bf16 mode: C[M,N] = A[M,K] . B[N,K]^T with A = fp32 activations (M = B*L rows, a few hundred
 // to a few thousand) and B = a weight stored as a bf16 (hi | lo) pair.  The fp32 MFMA runs at 1/16 of the bf16 rate, so the
@@ -963,25 +906,6 @@ __global__ __launch_bounds__(NW * 64) void gemm_nt_small_x3_kernel(const GemmArg
     }
 }
 
-template <int NW, int KS, int NS = 4>
-static int launch_small_x3_t(const GemmArgs& g, hipStream_t s) {
-    const int nbm = (g.M + 63) / 64, nbn = g.N / 64;
-    constexpr int smem = NS * 4 * 64 * 64 * KS;
-    static std::atomic<uint32_t> opted{0};            // per device ordinal (common.h: lds_opt_in)
-    if (lds_opt_in(opted, reinterpret_cast<const void*>(gemm_nt_small_x3_kernel<NW, KS, NS>), smem) != PNP_OK) return PNP_ERR_HIP;
-    hipLaunchKernelGGL((gemm_nt_small_x3_kernel<NW, KS, NS>), dim3(nbm * nbn), dim3(NW * 64), smem, s, g);
-    return hipGetLastError() == hipSuccess ? PNP_OK : PNP_ERR_HIP;
-}
-
-static int launch_small_x3(const GemmArgs& g, hipStream_t s) {
-    // many more workgroups than CUs (the N = 3072 launches at M = 875: 672): three co-resident workgroups per CU on 48 KB rings
-    // (3 slots of 32-deep slabs) run the launch as ONE round instead of three rounds of one 128 KB workgroup per CU: 28.9 -> 25.2 us.
-    // Not more than that, and nothing at 504 workgroups (21.2 against 21.4 us) or on the deep-K shapes (58 against 29 us): these
-    // launches run at what a CU ingests from L2 (~20-27 B/clk, tools/micro/lds_dma_rate.hip), whoever is resident on it.
-    if ((long)((g.M + 63) / 64) * (g.N / 64) > 600 && g.K <= 1024) return launch_small_x3_t<8, 1, 3>(g, s);
-    return g.K % 64 == 0 ? launch_small_x3_t<8, 2>(g, s) : launch_small_x3_t<8, 1>(g, s);
-}
-
 static std::mutex g_stamp_mu;
 static unsigned long long* g_stamp_buf = nullptr;                  // allocated by the first gemm_set_stamps(1), never freed
 static std::atomic<int> g_stamp_dev{-1};                           // device ordinal the buffer lives on: launches elsewhere record nothing
@@ -1005,44 +929,188 @@ int gemm_read_stamps(unsigned long long* host_out, int max_blocks) {
     return hipMemcpy(host_out, g_stamp_buf, (size_t)n * 64, hipMemcpyDeviceToHost) == hipSuccess ? PNP_OK : PNP_ERR_HIP;
 }
 
-// Host entry.  N is rounded up to the tile internally (loads clamp, stores mask on Nvalid).
-int gemm_nt(int dtype_bf16, GemmArgs g, hipStream_t s) {
-    if (g.M <= 0 || g.N <= 0 || g.K <= 0) return PNP_ERR_ARG;
+// ------------------------------------------------------------------------------------------ host: plan -> kernel -> launch
+// the wide kernels' compile-time epilogues cover the ViT block's dense layers; anything else (row / column
+// remaps, per-row bias, stashes, dual outputs) stays on the generic kernels
+static int wide_epilogue_kind(const GemmArgs& g) {
+    if (g.aux || g.row_div) return -1;
+    // the token-column epilogues store token PAIRS when col_div is even (pairs then never straddle an image): N has to be even
+    // too, or the last pair would write column N.  Otherwise the generic kernels take the launch (no split-bf16 form: refused)
+    const bool pair_ok = (g.col_div & 1) || !(g.N & 1);
+    if (g.A_lo || g.B_lo) {                         // split-bf16 operands: the fp32-facing epilogues
+        if (!g.A_lo || !g.B_lo) return -1;
+        if (g.mode == GEMM_EPI_LINEAR && !g.resid && g.out_f32 && !g.out_t && (g.bias_on_rows || !g.bias) && (g.col_div > 0 || g.bias_on_rows) &&
+            pair_ok)
+            return WIDE_TOKCOLS_F32;
+        if (g.col_div || g.bias_on_rows || (g.N & 3)) return -1;
+        if (g.mode == GEMM_EPI_LINEAR && g.resid && g.out_f32 && !g.out_t) return WIDE_RESID_F32;
+        if (g.mode == GEMM_EPI_LINEAR && !g.resid && g.out_f32 && !g.out_t) return WIDE_BIAS_F32;
+        if (g.mode == GEMM_EPI_GELU && !g.resid && g.out_t && g.out_lo && !g.out_f32) return WIDE_GELU_SPLIT;
+        if (g.mode == GEMM_EPI_LINEAR && !g.resid && g.out_t && g.out_lo && !g.out_f32) return WIDE_SPLIT;
+        return -1;
+    }
+    if (g.mode == GEMM_EPI_LINEAR && !g.resid && g.out_t && !g.out_f32 && (g.bias_on_rows || !g.bias) && (g.col_div > 0 || g.bias_on_rows) &&
+        pair_ok)
+        return WIDE_TOKCOLS_BF16;
+    if (g.col_div || g.bias_on_rows || (g.N & 3)) return -1;
+    if (g.mode == GEMM_EPI_LINEAR && !g.resid && g.out_t && !g.out_f32) return WIDE_BF16;
+    if (g.mode == GEMM_EPI_GELU && !g.resid && g.out_t && !g.out_f32) return WIDE_GELU_BF16;
+    if (g.mode == GEMM_EPI_LINEAR && g.resid && g.out_f32 && !g.out_t) return WIDE_RESID_F32;
+    return -1;
+}
+
+// Stream-K tail policy, in units of one slab pair of one workgroup (4.2 us at the clock these launches hold).  Measured with the
+// in-kernel stamps (tools/gemm_x3_streamk_stamps.py, profiles/r06_streamk_stamps.txt) and per launch shape
+// (tools/gemm_x3_streamk.py, profiles/r06_streamk.txt):
+//   whole tiles : the tail round costs a tile, nk2 pairs + ~2 of epilogue -- x 0.82 when the tail holds under a quarter of the CUs
+//                 (the few workgroups of such a round run beside idle CUs, at a higher rate: 58 against 75 us at K = 1024);
+//   stream-K    : 1.05 x upw pairs in two parts, each with its own pipeline fill (~2 pairs each); the partial tile stored and
+//                 the flag raised: 3-7 us when up to ~64 tiles are split, 19 us when most workgroups store 256 KB at the same time
+//                 beside the others' operand streams (220 producers of the 732-tile launch); ~4 us per partial tile an owner
+//                 adds (np of them, one after the other); the epilogue.
+// So the hand-off costs 8-12 pairs = 35-50 us: it pays for a SMALL tail of DEEP tiles (8 x 2305 rows, fc2: 292 tiles of K = 4096,
+// 501 -> 382 us; 12 x 442 rows: 84 tiles, 202 -> 146 us), is worth +-5 % for small tails at K = 1024 (left off), and loses 10-35 us
+// on the bench batch's launches (732 / 976 / 244 tiles), where a whole tile is 75 us.  mode: 0 = never, 1 = when this model says it pays, 2 = whenever
+// there is a tail (tests, A/B runs); set process-wide by pnp_set_tuning("streamk", mode).
+static bool streamk_pays(int tail, int cap, int nk2, int upw, int np) {
+    // a tail round that leaves CUs idle runs its tiles FASTER than a full round (clock and memory system to itself): 0.73-0.82 of
+    // the full-round tile time up to ~60 % of the CUs, 0.96 at 80 %, 1.05 at 95 % (K = 4096 launches of 84 ... 244 tiles)
+    const double x = (double)tail / cap;
+    const double whole = (nk2 + 2.0) * (x <= 0.6 ? 0.75 : 0.75 + (x - 0.6) * 0.857);
+    const double sk = 1.05 * upw + 4.0 + (tail <= 64 ? 1.0 : 4.5) + 0.75 * np + 1.5;
+    return sk * 1.05 + 0.5 < whole;                 // at least 5 % of the tail round, or it is not worth a second code path
+}
+
+// The launch plan (gemm.h).  N is rounded up to the chosen tile once (the kernels' loads clamp and their stores mask on Nvalid).
+GemmPlan gemm_plan(int dtype_bf16, const GemmArgs& g, int n_cu, int streamk_mode, int sk_wgs) {
+    GemmPlan p = {PNP_ERR_ARG};
+    if (g.M <= 0 || g.N <= 0 || g.K <= 0) return p;
+    // one workgroup per bm x bn tile
+    auto tiled = [&](int family, int variant, int bm, int bn, int block, int smem) {
+        const int n_pad = (g.N + bn - 1) / bn * bn;
+        p = {PNP_OK, family, variant, dtype_bf16 ? 1 : 0, n_pad, ((g.M + bm - 1) / bm) * (n_pad / bn), block, smem};
+    };
     if (g.a_f32) {
         // split-bf16 with fp32 activations (text side): A is split by the kernel, B is a (hi, lo) bf16 pair; fp32 epilogues
         if (!g.B_lo || g.A_lo || g.K % 32 || (g.lda * 4) % 16 || (g.ldb * 2) % 16 || g.row_div || g.col_div || g.bias_on_rows ||
             (g.N & 3))
-            return PNP_ERR_ARG;
-        g.Nvalid = g.N;
-        g.N = (g.N + 63) / 64 * 64;
-        return launch_small_x3(g, s);
+            return p;
+        dtype_bf16 = 0;
+        // many more workgroups than CUs (the N = 3072 launches at M = 875: 672): three co-resident workgroups per CU on 48 KB rings
+        // (3 slots of 32-deep slabs) run the launch as ONE round instead of three rounds of one 128 KB workgroup per CU: 28.9 -> 25.2 us.
+        // Not more than that, and nothing at 504 workgroups (21.2 against 21.4 us) or on the deep-K shapes (58 against 29 us): these
+        // launches run at what a CU ingests from L2 (~20-27 B/clk, tools/micro/lds_dma_rate.hip), whoever is resident on it.
+        const int v = ((long)((g.M + 63) / 64) * ((g.N + 63) / 64) > 600 && g.K <= 1024) ? SMALL_X3_K32_NS3
+                      : g.K % 64 == 0 ? SMALL_X3_K64 : SMALL_X3_K32;
+        tiled(PNP_GEMM_SMALL_X3, v, 64, 64, 512, (v == SMALL_X3_K32_NS3 ? 3 : 4) * 4 * 64 * 64 * (v == SMALL_X3_K64 ? 2 : 1));
+        return p;                                          // the kernel takes no stamps
     }
     const bool x3 = g.A_lo || g.B_lo;                      // split-bf16 operands (bf16 pairs), fp32-facing epilogues
     if (x3) dtype_bf16 = 1;
     const int bk = dtype_bf16 ? 64 : 32;
-    if (g.K % bk) return PNP_ERR_ARG;
-    if ((g.lda * (dtype_bf16 ? 2 : 4)) % 16 || (g.ldb * (dtype_bf16 ? 2 : 4)) % 16) return PNP_ERR_ARG;
+    if (g.K % bk) return p;
+    if ((g.lda * (dtype_bf16 ? 2 : 4)) % 16 || (g.ldb * (dtype_bf16 ? 2 : 4)) % 16) return p;
     // store_frag and the accumulator preload read the per-column bias, the residual row and the GELU stash as one 16-byte
     // group of four columns (and write the stash that way): with N % 4 != 0 the last group would reach past column N -- past
     // the end of bias and of the last residual row, and, the stash, a WRITE past column N of every row.  Refused as a whole
     // (broader than the fault: a padded residual only over-reads on its last row): no engine launch uses the combination
-    if ((g.N & 3) && ((g.bias && !g.bias_on_rows) || g.resid || g.aux)) return PNP_ERR_ARG;
-    g.Nvalid = g.N;
-    g.stamps = g_stamps.load(std::memory_order_relaxed);
-    if (g.stamps && current_device() != g_stamp_dev.load(std::memory_order_relaxed)) g.stamps = nullptr;
-    // small problems (text side: M = B*L rows) use 64x64 tiles to fill more CUs
+    if ((g.N & 3) && ((g.bias && !g.bias_on_rows) || g.resid || g.aux)) return p;
     const long tiles128 = (long)((g.M + 127) / 128) * ((g.N + 127) / 128);
-    const bool small = tiles128 < 192 && !x3;
-    if (small) {
-        // text side (M = B*L rows): 64 x 64 tiles, 4 waves of 32 x 32, 3-slot DMA ring -- the deep
-        // prefetch matters more than tile efficiency for these latency-bound launches
-        g.N = (g.N + 63) / 64 * 64;
-        return dtype_bf16 ? launch_big<bf16, 64, 64, 32, 32, 3>(g, s) : launch_big<float, 64, 64, 32, 32, 3>(g, s);
+    const long tiles256 = (long)((g.M + 255) / 256) * ((g.N + 255) / 256);
+    const int wide = dtype_bf16 ? wide_epilogue_kind(g) : -1;
+    if (tiles128 < 192 && !x3) {
+        // small problems (text side: M = B*L rows): 64 x 64 tiles, 4 waves of 32 x 32, 3-slot DMA ring -- more CUs filled, and
+        // the deep prefetch matters more than tile efficiency for these latency-bound launches
+        tiled(PNP_GEMM_G64, 0, 64, 64, 256, 3 * (64 + 64) * 128);
+    } else if (x3 || (wide >= 0 && tiles256 >= 128)) {
+        // the persistent 256 x 256 kernels: one workgroup per CU (LDS-limited) walks the tiles.  Split-bf16 operands always
+        // (gemm_nt_x3_kernel, gemm_x3.hip), bf16 with one of the ViT block's epilogues from 128 tiles (gemm_nt_wide_kernel)
+        if (wide < 0) return p;
+        tiled(x3 ? PNP_GEMM_X3_WIDE : PNP_GEMM_WIDE, wide, 256, 256, 512, kWideSmem);
+        const int ntiles = p.grid, tail = n_cu > 0 ? ntiles % n_cu : 0, nk2 = g.K / 64;
+        p.grid = ntiles < n_cu ? ntiles : n_cu > 0 ? n_cu : 0;
+        if (x3 && streamk_mode && tail > 0 && sk_wgs >= n_cu) {            // a last round that is not full, and a workspace for it
+            const int upw = (int)(((long)tail * nk2 + n_cu - 1) / n_cu);
+            const int np = (nk2 - 1 + upw - 1) / upw;                    // parts in front of the last one of a tile, at most
+            if (streamk_mode == 2 || streamk_pays(tail, n_cu, nk2, upw, np)) p.sk_full = ntiles - tail, p.sk_upw = upw, p.grid = n_cu;
+        }
+    } else if (dtype_bf16 && g.K >= 2048 && g.N >= 512) {
+        tiled(PNP_GEMM_G256, 0, 256, 256, 512, 2 * (256 + 256) * 128);       // 16x16x32 MFMA, simple ring
+    } else {
+        tiled(PNP_GEMM_G128, 0, 128, 128, 256, 2 * (128 + 128) * 128);       // two workgroups per CU
+    }
+    p.profiled = p.family != PNP_GEMM_G64;
+    p.keeps_stamps = p.grid <= kStampBlocks;               // more workgroups than stamp rows: the launch records none
+    return p;
+}
+
+// The one table from a plan to its kernel, with the kernel's one-time opt-in to its dynamic LDS per device ordinal
+// (common.h: lds_opt_in) beside the pointer.
+struct GemmKernelRow {
+    int family, variant, dtype_bf16, sk;
+    GemmKernel kernel;
+    std::atomic<uint32_t> opted{0};
+};
+static GemmKernelRow* gemm_kernel_row(const GemmPlan& p) {
+#define X3_ROWS(E) {PNP_GEMM_X3_WIDE, E, 1, 0, gemm_x3_kernel(E, 0)}, {PNP_GEMM_X3_WIDE, E, 1, 1, gemm_x3_kernel(E, 1)}
+    static GemmKernelRow rows[] = {
+        {PNP_GEMM_G64, 0, 0, 0, gemm_nt_big_kernel<float, 64, 64, 32, 32, 3>},
+        {PNP_GEMM_G64, 0, 1, 0, gemm_nt_big_kernel<bf16, 64, 64, 32, 32, 3>},
+        {PNP_GEMM_G128, 0, 0, 0, gemm_nt_big_kernel<float, 128, 128, 64, 64, 2>},
+        {PNP_GEMM_G128, 0, 1, 0, gemm_nt_big_kernel<bf16, 128, 128, 64, 64, 2>},
+        {PNP_GEMM_G256, 0, 1, 0, gemm_nt_big_kernel<bf16, 256, 256, 128, 64, 2, false>},
+        {PNP_GEMM_WIDE, WIDE_BF16, 1, 0, gemm_nt_wide_kernel<WIDE_BF16>},
+        {PNP_GEMM_WIDE, WIDE_GELU_BF16, 1, 0, gemm_nt_wide_kernel<WIDE_GELU_BF16>},
+        {PNP_GEMM_WIDE, WIDE_RESID_F32, 1, 0, gemm_nt_wide_kernel<WIDE_RESID_F32>},
+        {PNP_GEMM_WIDE, WIDE_TOKCOLS_BF16, 1, 0, gemm_nt_wide_kernel<WIDE_TOKCOLS_BF16>},
+        X3_ROWS(WIDE_RESID_F32), X3_ROWS(WIDE_BIAS_F32), X3_ROWS(WIDE_TOKCOLS_F32), X3_ROWS(WIDE_GELU_SPLIT), X3_ROWS(WIDE_SPLIT),
+        {PNP_GEMM_SMALL_X3, SMALL_X3_K32_NS3, 0, 0, gemm_nt_small_x3_kernel<8, 1, 3>},
+        {PNP_GEMM_SMALL_X3, SMALL_X3_K64, 0, 0, gemm_nt_small_x3_kernel<8, 2>},
+        {PNP_GEMM_SMALL_X3, SMALL_X3_K32, 0, 0, gemm_nt_small_x3_kernel<8, 1>},
+    };
+#undef X3_ROWS
+    const int sk = p.sk_upw > 0;
+    for (GemmKernelRow& r : rows)
+        if (r.family == p.family && r.variant == p.variant && r.sk == sk && r.dtype_bf16 == p.dtype_bf16) return &r;
+    return nullptr;
+}
+
+// The one launch: `g` as the kernel sees it (N padded, stamps and the stream-K split filled in), on device ordinal `dev`.
+static int launch_plan(const GemmPlan& p, const GemmArgs& g, int dev, hipStream_t s) {
+    GemmKernelRow* const k = gemm_kernel_row(p);
+    if (!k || !k->kernel) return PNP_ERR_ARG;
+    if (lds_opt_in(k->opted, reinterpret_cast<const void*>(k->kernel), p.smem, dev) != PNP_OK) return PNP_ERR_HIP;
+    if (p.sk_upw) return streamk_chain_launch(k->kernel, g, p.grid, g.sk, s);
+    hipLaunchKernelGGL(k->kernel, dim3(p.grid), dim3(p.block), p.smem, s, g);
+    return hipGetLastError() == hipSuccess ? PNP_OK : PNP_ERR_HIP;
+}
+
+// Host entry: plan -> (profile bracket) -> launch.  A refused launch returns before anything is created, recorded or launched.
+int gemm_nt(int dtype_bf16, GemmArgs g, hipStream_t s) {
+    const int dev = current_device();
+    const int n_cu = device_cu_count(dev);
+    StreamKWs* const ws = g.sk;
+    GemmPlan p = gemm_plan(dtype_bf16, g, n_cu, streamk_mode(), ws && ws->part ? ws->wgs : 0);
+    if (p.status != PNP_OK) return p.status;
+    if (p.sk_upw) {
+        // a stream that is being captured into a graph keeps whole tiles: the event chain of streamk_chain_launch reaches across
+        // streams, which a capture must not, and one-launch-at-a-time cannot be promised for replays
+        hipStreamCaptureStatus cap_st = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(s, &cap_st) == hipSuccess && cap_st != hipStreamCaptureStatusNone) p = gemm_plan(dtype_bf16, g, n_cu, 0, 0);
+    }
+    if (p.grid <= 0) return PNP_ERR_HIP;                   // a persistent kernel without a CU count
+    g.Nvalid = g.N;
+    g.N = p.n_pad;
+    g.stamps = p.keeps_stamps ? g_stamps.load(std::memory_order_relaxed) : nullptr;
+    if (g.stamps && dev != g_stamp_dev.load(std::memory_order_relaxed)) g.stamps = nullptr;
+    if (p.sk_upw) {
+        g.sk_part = ws->part; g.sk_flag = ws->flag; g.sk_tmo = ws->flag + ws->wgs;
+        g.sk_full = p.sk_full; g.sk_upw = p.sk_upw;
     }
     static GemmProfile never_on;                           // launches outside an engine (pnp_op_*) are not timed
     GemmProfile& pf = g.prof ? *g.prof : never_on;
-    // every `period`-th launch of the family is bracketed (1 = all of them: ~2.5 us of stream serialisation per launch)
-    const bool timed = pf.on && pf.used < GemmProfile::kMax && (pf.seq++ % pf.period) == 0;
+    // every `period`-th launch of the bracketed families (1 = all of them: ~2.5 us of stream serialisation per launch)
+    const bool timed = p.profiled && pf.on && pf.used < GemmProfile::kMax && (pf.seq++ % pf.period) == 0;
     if (timed) {
         while (pf.created <= pf.used) {
             if (hipEventCreate(&pf.ev0[pf.created]) != hipSuccess || hipEventCreate(&pf.ev1[pf.created]) != hipSuccess)
@@ -1051,39 +1119,12 @@ int gemm_nt(int dtype_bf16, GemmArgs g, hipStream_t s) {
         }
         (void)hipEventRecord(pf.ev0[pf.used], s);
     }
-    const double fl = 2.0 * g.M * (double)g.N * g.K;       // algorithmic FLOPs (the split-bf16 form issues 3x as MFMA work)
-    g.N = (g.N + 127) / 128 * 128;
-    // Tile choice (in-kernel clock stamps, tools/gemm_stamps.py):
-    //   bf16 ViT-block epilogues (bias -> bf16 | bias+GELU -> bf16 | bias+residual -> f32), >= 128 tiles:
-    //       gemm_nt_wide_kernel, 256 x 256, 32x32x16 MFMA; main loop ~2350 clk per 64-deep slab against
-    //       2048 MFMA clk, epilogue staged through LDS (full-line stores)
-    //   split-bf16 operands       : always gemm_nt_x3_kernel (gemm_x3.hip)
-    //   other bf16 with K >= 2048 : generic 256 x 256 (16x16x32 MFMA, simple ring)
-    //   otherwise                 : generic 128 x 128, two workgroups per CU
-    int r;
-    const bool big_k = g.K >= 2048 && g.Nvalid >= 512;
-    const int wide = dtype_bf16 ? wide_epilogue_kind(g) : -1;
-    const long tiles256 = (long)((g.M + 255) / 256) * ((g.Nvalid + 255) / 256);
-    if (x3) {
-        if (wide < 0) return PNP_ERR_ARG;
-        g.N = (g.Nvalid + 255) / 256 * 256;
-        r = launch_x3_wide(wide, g, s);
-    } else if (wide >= 0 && tiles256 >= 128) {
-        g.N = (g.Nvalid + 255) / 256 * 256;
-        r = wide == WIDE_BF16 ? launch_wide<WIDE_BF16>(g, s)
-            : wide == WIDE_GELU_BF16 ? launch_wide<WIDE_GELU_BF16>(g, s)
-            : wide == WIDE_RESID_F32 ? launch_wide<WIDE_RESID_F32>(g, s) : launch_wide<WIDE_TOKCOLS_BF16>(g, s);
-    } else if (dtype_bf16 && big_k) {
-        g.N = (g.Nvalid + 255) / 256 * 256;
-        r = launch_big<bf16, 256, 256, 128, 64, 2, false>(g, s);
-    } else {
-        r = dtype_bf16 ? launch_big<bf16, 128, 128, 64, 64, 2>(g, s) : launch_big<float, 128, 128, 64, 64, 2>(g, s);
-    }
+    const int r = launch_plan(p, g, dev, s);
     if (timed) {
         (void)hipEventRecord(pf.ev1[pf.used], s);
         pf.used++;
         pf.launches++;
-        pf.flops += fl;
+        pf.flops += 2.0 * g.M * (double)g.Nvalid * g.K;    // algorithmic FLOPs (the split-bf16 form issues 3x as MFMA work)
     }
     return r;
 }

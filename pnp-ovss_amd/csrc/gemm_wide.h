@@ -33,7 +33,10 @@ constexpr int kWideStageRow = 68;                                  // floats per
 constexpr int kWideStageBytes = 8 * 32 * kWideStageRow * 4;        // 8 waves x 32 rows
 constexpr int kWideSmem = 65536 + kWideStageBytes;                 // slot 0 | slot 1 overlaid by the staging area
 
-// split-bf16 launches (gemm_x3.hip); epi = one of the fp32-facing WIDE_* kinds
-int launch_x3_wide(int epi, const GemmArgs& g, hipStream_t s);
+// what gemm.hip's kernel table and launcher take from gemm_x3.hip: the split-bf16 kernel of one of the fp32-facing WIDE_* kinds
+// (sk: its stream-K instantiation; null for any other kind), and the launch of a stream-K kernel behind the device's chain
+typedef void (*GemmKernel)(const GemmArgs);
+GemmKernel gemm_x3_kernel(int epi, int sk);
+int streamk_chain_launch(GemmKernel kernel, const GemmArgs& g, int grid, StreamKWs* ws, hipStream_t s);
 
 }  // namespace pnp

@@ -599,41 +599,20 @@ __global__ __launch_bounds__(512) void gemm_nt_x3_kernel(const GemmArgs g) {
     }
 }
 
-// Stream-K tail policy, in units of one slab pair of one workgroup (4.2 us at the clock these launches hold).  Measured with the
-// in-kernel stamps (tools/gemm_x3_streamk_stamps.py, profiles/r06_streamk_stamps.txt) and per launch shape
-// (tools/gemm_x3_streamk.py, profiles/r06_streamk.txt):
-//   whole tiles : the tail round costs a tile, nk2 pairs + ~2 of epilogue -- x 0.82 when the tail holds under a quarter of the CUs
-//                 (the few workgroups of such a round run beside idle CUs, at a higher rate: 58 against 75 us at K = 1024);
-//   stream-K    : 1.05 x upw pairs in two parts, each with its own pipeline fill (~2 pairs each); the partial tile stored and
-//                 the flag raised: 3-7 us when up to ~64 tiles are split, 19 us when most workgroups store 256 KB at the same time
-//                 beside the others' operand streams (220 producers of the 732-tile launch); ~4 us per partial tile an owner
-//                 adds (np of them, one after the other); the epilogue.
-// So the hand-off costs 8-12 pairs = 35-50 us: it pays for a SMALL tail of DEEP tiles (8 x 2305 rows, fc2: 292 tiles of K = 4096,
-// 501 -> 382 us; 12 x 442 rows: 84 tiles, 202 -> 146 us), is worth +-5 % for small tails at K = 1024 (left off), and loses 10-35 us
-// on the bench batch's launches (732 / 976 / 244 tiles), where a whole tile is 75 us.  mode: 0 = never, 1 = when this model says it pays, 2 = whenever
-// there is a tail (tests, A/B runs); set process-wide by pnp_set_tuning("streamk", mode).
+// pnp_set_tuning("streamk", mode): 0 = never, 1 = when the cost model says it pays, 2 = whenever there is a tail (gemm.hip gemm_plan)
 static std::atomic<int> g_streamk_mode{1};
 void set_streamk_mode(int m) { g_streamk_mode.store(m, std::memory_order_relaxed); }
 int streamk_mode() { return g_streamk_mode.load(std::memory_order_relaxed); }
-static bool streamk_pays(int tail, int cap, int nk2, int upw, int np) {
-    // a tail round that leaves CUs idle runs its tiles FASTER than a full round (clock and memory system to itself): 0.73-0.82 of
-    // the full-round tile time up to ~60 % of the CUs, 0.96 at 80 %, 1.05 at 95 % (K = 4096 launches of 84 ... 244 tiles)
-    const double x = (double)tail / cap;
-    const double whole = (nk2 + 2.0) * (x <= 0.6 ? 0.75 : 0.75 + (x - 0.6) * 0.857);
-    const double sk = 1.05 * upw + 4.0 + (tail <= 64 ? 1.0 : 4.5) + 0.75 * np + 1.5;
-    return sk * 1.05 + 0.5 < whole;                 // at least 5 % of the tail round, or it is not worth a second code path
-}
-
 // ONE stream-K launch in flight per device, WHATEVER its epilogue: an owner spins on workgroups of its own launch with lower ids,
 // which the dispatcher started before it -- true within a launch, but two such launches from two streams, each resident on part
 // of the chip, could hold the CUs the other's missing producers need.  Every launch waits for the event behind the previous one
-// (whatever stream it was on, whichever instantiation of launch_x3 issued it) and leaves its own; kernels that never spin overlap
+// (whatever stream it was on, whichever instantiation of the kernel it launched) and leaves its own; kernels that never spin overlap
 // with it as before.  The chain's state lives HERE, once per process, and not in the launcher template (a function-local static
 // of a template exists once per instantiation: five chains, and launches with different epilogues unordered).  The lock is held
 // over wait, launch and record -- and over the workspace's launch count, which op-level callers on several threads share.
 static std::mutex g_sk_chain_mu;
 static hipEvent_t g_sk_chain_last[kMaxDevices];
-static int streamk_chain_launch(void (*kernel)(const GemmArgs), const GemmArgs& g, int grid, StreamKWs* ws, hipStream_t s) {
+int streamk_chain_launch(GemmKernel kernel, const GemmArgs& g, int grid, StreamKWs* ws, hipStream_t s) {
     const int d = current_device();
     if (d < 0) return PNP_ERR_HIP;
     std::lock_guard<std::mutex> lk(g_sk_chain_mu);
@@ -647,42 +626,6 @@ static int streamk_chain_launch(void (*kernel)(const GemmArgs), const GemmArgs& 
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(512), kWideSmem, s, g);
     const bool ok = hipGetLastError() == hipSuccess && hipEventRecord(last, s) == hipSuccess;
     return ok ? PNP_OK : PNP_ERR_HIP;
-}
-
-template <int EPI>
-static int launch_x3(GemmArgs g, hipStream_t s) {
-    const int nbm = (g.M + 255) / 256, nbn = g.N / 256;
-    const int n_cu = device_cu_count();
-    if (!n_cu) return PNP_ERR_HIP;
-    static std::atomic<uint32_t> opted{0}, opted_sk{0};            // per device ordinal (common.h: lds_opt_in)
-    const int ntiles = nbm * nbn;
-    const int cap = n_cu;                                          // workgroups of a launch: one per CU (LDS-limited)
-    const int mode = streamk_mode();
-    StreamKWs* const ws = g.sk;
-    if (mode && ws && ws->part && ws->wgs >= cap) {
-        const int rounds = ntiles / cap, tail = ntiles - rounds * cap, nk2 = g.K / 64;
-        if (tail > 0) {
-            const int upw = (int)(((long)tail * nk2 + cap - 1) / cap);
-            const int np = (nk2 - 1 + upw - 1) / upw;                    // parts in front of the last one of a tile, at most
-            // (a stream that is being captured into a graph keeps whole tiles: the event chain above reaches across streams, which
-            // a capture must not, and one-launch-at-a-time cannot be promised for replays)
-            hipStreamCaptureStatus cap_st = hipStreamCaptureStatusNone;
-            const bool capturing = hipStreamIsCapturing(s, &cap_st) == hipSuccess && cap_st != hipStreamCaptureStatusNone;
-            if (!capturing && (mode == 2 || streamk_pays(tail, cap, nk2, upw, np))) {
-                if (lds_opt_in(opted_sk, reinterpret_cast<const void*>(gemm_nt_x3_kernel<EPI, true>), kWideSmem) != PNP_OK) return PNP_ERR_HIP;
-                g.sk_part = ws->part;
-                g.sk_flag = ws->flag;
-                g.sk_tmo = ws->flag + ws->wgs;
-                g.sk_full = rounds * cap;
-                g.sk_upw = upw;
-                return streamk_chain_launch(gemm_nt_x3_kernel<EPI, true>, g, cap, ws, s);
-            }
-        }
-    }
-    if (lds_opt_in(opted, reinterpret_cast<const void*>(gemm_nt_x3_kernel<EPI, false>), kWideSmem) != PNP_OK) return PNP_ERR_HIP;
-    const int grid = ntiles > cap ? cap : ntiles;        // one workgroup per CU (LDS-limited) walks the tiles
-    hipLaunchKernelGGL((gemm_nt_x3_kernel<EPI, false>), dim3(grid), dim3(512), kWideSmem, s, g);
-    return hipGetLastError() == hipSuccess ? PNP_OK : PNP_ERR_HIP;
 }
 
 int streamk_ws_create(StreamKWs* ws, int wgs) {
@@ -725,15 +668,11 @@ StreamKWs* streamk_ws_default() {
     return &ws[d];
 }
 
-int launch_x3_wide(int epi, const GemmArgs& g, hipStream_t s) {
-    switch (epi) {
-        case WIDE_RESID_F32: return launch_x3<WIDE_RESID_F32>(g, s);
-        case WIDE_BIAS_F32: return launch_x3<WIDE_BIAS_F32>(g, s);
-        case WIDE_GELU_SPLIT: return launch_x3<WIDE_GELU_SPLIT>(g, s);
-        case WIDE_SPLIT: return launch_x3<WIDE_SPLIT>(g, s);
-        case WIDE_TOKCOLS_F32: return launch_x3<WIDE_TOKCOLS_F32>(g, s);
-    }
-    return PNP_ERR_ARG;
+GemmKernel gemm_x3_kernel(int epi, int sk) {
+#define X3_CASE(E) case E: return sk ? gemm_nt_x3_kernel<E, true> : gemm_nt_x3_kernel<E, false>
+    switch (epi) { X3_CASE(WIDE_RESID_F32); X3_CASE(WIDE_BIAS_F32); X3_CASE(WIDE_TOKCOLS_F32); X3_CASE(WIDE_GELU_SPLIT); X3_CASE(WIDE_SPLIT); }
+#undef X3_CASE
+    return nullptr;
 }
 
 }  // namespace pnp

@@ -14,22 +14,30 @@ extern "C" int pnp_itc_similarity(const float* d_img_feat, const float* d_txt_fe
     return itc_similarity(d_img_feat, d_txt_feat, d_sim, B, T, E, (hipStream_t)stream);
 }
 
-extern "C" int pnp_op_gemm(int32_t bf, const void* d_A, int32_t lda, const void* d_B, int32_t ldb, int32_t M, int32_t N,
-                           int32_t K, const float* d_bias, const float* d_resid, int32_t ldr, float* d_out_f32, int32_t ldo,
-                           int32_t gelu, void* stream) {
-    GemmArgs g = G_(d_A, lda, d_B, ldb, M, N, K);
-    g.bias = d_bias; g.resid = d_resid; g.ldr = ldr; g.out_f32 = d_out_f32; g.ldo = ldo;
-    g.mode = gelu ? GEMM_EPI_GELU : GEMM_EPI_LINEAR;
-    return gemm_nt(bf, g, (hipStream_t)stream);
+// The GemmArgs of an operator entry: every field an entry can set, in pnp_op_gemm_args' order with the split forms' low parts beside
+// their high parts.  No checks: each entry keeps its own.
+static GemmArgs gemm_op_args(const void* A, const void* A_lo, int lda, const void* B, const void* B_lo, int ldb, int M, int N, int K,
+                             const float* bias, int bias_on_rows, const float* resid, int ldr, float* out_f32, int ldo, void* out_t,
+                             void* out_lo, int ldo_t, int mode, float* aux, int ld_aux, int row_div, int col_div, int col_pad) {
+    GemmArgs g = G_(A, lda, B, ldb, M, N, K);
+    g.A_lo = A_lo; g.B_lo = B_lo;
+    g.bias = bias; g.bias_on_rows = bias_on_rows; g.resid = resid; g.ldr = ldr;
+    g.out_f32 = out_f32; g.ldo = ldo; g.out_t = out_t; g.out_lo = out_lo; g.ldo_t = ldo_t;
+    g.mode = mode; g.aux = aux; g.ld_aux = ld_aux; g.row_div = row_div; g.col_div = col_div; g.col_pad = col_pad;
+    return g;
 }
 
 extern "C" int pnp_op_gemm_ex(int32_t bf, const void* d_A, int32_t lda, const void* d_B, int32_t ldb, int32_t M, int32_t N,
                               int32_t K, const float* d_bias, const float* d_resid, int32_t ldr, float* d_out_f32, int32_t ldo,
                               void* d_out_t, int32_t ldo_t, int32_t mode, void* stream) {
-    GemmArgs g = G_(d_A, lda, d_B, ldb, M, N, K);
-    g.bias = d_bias; g.resid = d_resid; g.ldr = ldr; g.out_f32 = d_out_f32; g.ldo = ldo; g.out_t = d_out_t; g.ldo_t = ldo_t;
-    g.mode = mode ? GEMM_EPI_GELU : GEMM_EPI_LINEAR;
-    return gemm_nt(bf, g, (hipStream_t)stream);
+    return gemm_nt(bf, gemm_op_args(d_A, nullptr, lda, d_B, nullptr, ldb, M, N, K, d_bias, 0, d_resid, ldr, d_out_f32, ldo, d_out_t, nullptr, ldo_t,
+                                    mode ? GEMM_EPI_GELU : GEMM_EPI_LINEAR, nullptr, 0, 0, 0, 0), (hipStream_t)stream);
+}
+
+extern "C" int pnp_op_gemm(int32_t bf, const void* d_A, int32_t lda, const void* d_B, int32_t ldb, int32_t M, int32_t N,
+                           int32_t K, const float* d_bias, const float* d_resid, int32_t ldr, float* d_out_f32, int32_t ldo,
+                           int32_t gelu, void* stream) {
+    return pnp_op_gemm_ex(bf, d_A, lda, d_B, ldb, M, N, K, d_bias, d_resid, ldr, d_out_f32, ldo, nullptr, 0, gelu, stream);
 }
 
 extern "C" int pnp_op_split(const float* d_in, void* d_hi, void* d_lo, int64_t n, void* stream) {
@@ -42,11 +50,8 @@ extern "C" int pnp_op_gemm_x3(const void* d_A_hi, const void* d_A_lo, int32_t ld
                               const float* d_resid, int32_t ldr, float* d_out_f32, int32_t ldo, void* d_out_hi, void* d_out_lo,
                               int32_t ldo_t, int32_t gelu, int32_t col_div, int32_t col_pad, void* stream) {
     if (!d_A_hi || !d_A_lo || !d_B_hi || !d_B_lo) return PNP_ERR_ARG;
-    GemmArgs g = G_(d_A_hi, lda, d_B_hi, ldb, M, N, K);
-    g.A_lo = d_A_lo; g.B_lo = d_B_lo;
-    g.bias = d_bias; g.bias_on_rows = bias_on_rows; g.resid = d_resid; g.ldr = ldr; g.out_f32 = d_out_f32; g.ldo = ldo;
-    g.out_t = d_out_hi; g.out_lo = d_out_lo; g.ldo_t = ldo_t; g.col_div = col_div; g.col_pad = col_pad;
-    g.mode = gelu ? GEMM_EPI_GELU : GEMM_EPI_LINEAR;
+    GemmArgs g = gemm_op_args(d_A_hi, d_A_lo, lda, d_B_hi, d_B_lo, ldb, M, N, K, d_bias, bias_on_rows, d_resid, ldr, d_out_f32, ldo, d_out_hi,
+                              d_out_lo, ldo_t, gelu ? GEMM_EPI_GELU : GEMM_EPI_LINEAR, nullptr, 0, 0, col_div, col_pad);
     g.sk = streamk_mode() ? streamk_ws_default() : nullptr;     // op level: the per-device workspace (shared by all callers: the launcher serialises)
     return gemm_nt(1, g, (hipStream_t)stream);
 }
@@ -85,10 +90,9 @@ extern "C" int pnp_op_gemm_x3a(const float* d_A, int32_t lda, const void* d_B_hi
                                int32_t N, int32_t K, const float* d_bias, const float* d_resid, int32_t ldr, float* d_out_f32,
                                int32_t ldo, int32_t mode, float* d_aux, int32_t ld_aux, void* stream) {
     if (!d_A || !d_B_hi || !d_B_lo || !d_out_f32 || mode < 0 || mode > 2) return PNP_ERR_ARG;
-    GemmArgs g = G_(d_A, lda, d_B_hi, ldb, M, N, K);
-    g.B_lo = d_B_lo; g.a_f32 = 1;
-    g.bias = d_bias; g.resid = d_resid; g.ldr = ldr; g.out_f32 = d_out_f32; g.ldo = ldo;
-    g.mode = mode; g.aux = d_aux; g.ld_aux = ld_aux;
+    GemmArgs g = gemm_op_args(d_A, nullptr, lda, d_B_hi, d_B_lo, ldb, M, N, K, d_bias, 0, d_resid, ldr, d_out_f32, ldo, nullptr, nullptr, 0, mode,
+                              d_aux, ld_aux, 0, 0, 0);
+    g.a_f32 = 1;
     return gemm_nt(0, g, (hipStream_t)stream);
 }
 
@@ -96,9 +100,8 @@ extern "C" int pnp_op_gemm_tokcols(int32_t bf, const void* d_A, int32_t lda, con
                                    int32_t K, const float* d_bias_rows, void* d_out_t, int32_t ldo_t, int32_t col_div,
                                    int32_t col_pad, void* stream) {
     if (!d_out_t || col_div < 0 || (col_div > 0 && col_pad < col_div)) return PNP_ERR_ARG;
-    GemmArgs g = G_(d_A, lda, d_B, ldb, M, N, K);
-    g.bias = d_bias_rows; g.bias_on_rows = 1; g.out_t = d_out_t; g.ldo_t = ldo_t; g.col_div = col_div; g.col_pad = col_pad;
-    return gemm_nt(bf, g, (hipStream_t)stream);
+    return gemm_nt(bf, gemm_op_args(d_A, nullptr, lda, d_B, nullptr, ldb, M, N, K, d_bias_rows, 1, nullptr, 0, nullptr, 0, d_out_t, nullptr, ldo_t,
+                                    GEMM_EPI_LINEAR, nullptr, 0, 0, col_div, col_pad), (hipStream_t)stream);
 }
 
 extern "C" int pnp_op_gemm_args(int32_t bf, const void* d_A, int32_t lda, const void* d_B, int32_t ldb, int32_t M, int32_t N,
@@ -108,11 +111,26 @@ extern "C" int pnp_op_gemm_args(int32_t bf, const void* d_A, int32_t lda, const 
     if (!d_A || !d_B || (!d_out_f32 && !d_out_t) || M <= 0 || N <= 0 || K <= 0 || lda < K || ldb < K) return PNP_ERR_ARG;
     if (mode < 0 || mode > 2 || (mode == GEMM_EPI_GELU_GRAD && !d_aux)) return PNP_ERR_ARG;
     if (row_div < 0 || col_div < 0 || (col_div > 0 && col_pad < col_div)) return PNP_ERR_ARG;
-    GemmArgs g = G_(d_A, lda, d_B, ldb, M, N, K);
-    g.bias = d_bias; g.bias_on_rows = bias_on_rows ? 1 : 0; g.resid = d_resid; g.ldr = ldr;
-    g.out_f32 = d_out_f32; g.ldo = ldo; g.out_t = d_out_t; g.ldo_t = ldo_t;
-    g.mode = mode; g.aux = d_aux; g.ld_aux = ld_aux; g.row_div = row_div; g.col_div = col_div; g.col_pad = col_pad;
-    return gemm_nt(bf ? 1 : 0, g, (hipStream_t)stream);
+    return gemm_nt(bf ? 1 : 0, gemm_op_args(d_A, nullptr, lda, d_B, nullptr, ldb, M, N, K, d_bias, bias_on_rows ? 1 : 0, d_resid, ldr, d_out_f32, ldo,
+                                            d_out_t, nullptr, ldo_t, mode, d_aux, ld_aux, row_div, col_div, col_pad), (hipStream_t)stream);
+}
+
+// The launch plan of the entry points above (include/pnp_hip.h): the same GemmArgs with a placeholder for every pointer that is
+// present -- gemm_plan looks at which are set, never at what they hold.  The wide split form needs both low parts, the text-side
+// form the weight's.
+extern "C" int pnp_op_gemm_plan(int32_t form, int32_t M, int32_t N, int32_t K, int32_t lda, int32_t ldb, int32_t mode, int32_t has,
+                                int32_t row_div, int32_t col_div, int32_t col_pad, int32_t n_cu, int32_t streamk_mode, int32_t sk_wgs,
+                                pnp_gemm_plan* plan) {
+    if (!plan || form < PNP_GEMM_FORM_F32 || form > PNP_GEMM_FORM_X3A) return PNP_ERR_ARG;
+    static float there[4];
+    auto p = [&](int bit) { return (has & bit) ? there : nullptr; };
+    const bool x3 = form == PNP_GEMM_FORM_X3, x3a = form == PNP_GEMM_FORM_X3A;
+    GemmArgs g = gemm_op_args(there, x3 ? there : nullptr, lda, there, x3 || x3a ? there : nullptr, ldb, M, N, K, p(PNP_GEMM_HAS_BIAS),
+                              (has & PNP_GEMM_HAS_BIAS_ON_ROWS) ? 1 : 0, p(PNP_GEMM_HAS_RESID), 0, p(PNP_GEMM_HAS_OUT_F32), 0, p(PNP_GEMM_HAS_OUT_T),
+                              p(PNP_GEMM_HAS_OUT_LO), 0, mode, p(PNP_GEMM_HAS_AUX), 0, row_div, col_div, col_pad);
+    g.a_f32 = x3a;
+    *plan = gemm_plan(form == PNP_GEMM_FORM_BF16 || x3, g, n_cu, streamk_mode, sk_wgs);
+    return plan->status;
 }
 
 extern "C" int pnp_op_vit_attention(int32_t bf, const void* d_qk, int32_t ld_qk, int32_t D, const void* d_vt, int32_t ld_vt,

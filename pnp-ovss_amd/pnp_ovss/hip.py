@@ -44,6 +44,11 @@ class PnpCrfTerm(C.Structure):
     _fields_ = [("dims", C.c_int32), ("d_features", C.c_void_p)]
 
 
+class PnpGemmPlan(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("status", "family", "variant", "dtype_bf16", "n_pad", "grid", "block", "smem",
+                                         "keeps_stamps", "profiled", "sk_full", "sk_upw")]
+
+
 _lib = None
 
 
@@ -98,6 +103,7 @@ def load_library():
         "pnp_op_gemm_tokcols": (i32, [i32, vp, i32, vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, vp]),
         "pnp_op_gemm_args": (i32, [i32, vp, i32, vp, i32, i32, i32, i32, vp, i32, vp, i32, vp, i32, vp, i32, i32, vp, i32, i32, i32,
                                    i32, vp]),
+        "pnp_op_gemm_plan": (i32, [i32] * 14 + [C.POINTER(PnpGemmPlan)]),
         "pnp_op_vit_attention": (i32, [i32, vp, i32, i32, vp, i32, i32, vp, i32, i32, i32, f32, vp]),
         "pnp_op_vit_attention_x3": (i32, [vp, vp, i32, i32, vp, vp, i32, i32, i32, f32, vp]),
         "pnp_preprocess_images": (i32, [vp, vp, i32, i32, i32, vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_float), vp, vp]),
@@ -165,7 +171,7 @@ EXPORTED = ["pnp_create", "pnp_create_shared", "pnp_destroy", "pnp_last_error", 
             "pnp_streamk_status", "pnp_text_forward_text", "pnp_project_normalize", "pnp_itc_similarity",
             "pnp_op_text_self_attn", "pnp_op_text_self_attn_bwd", "pnp_op_layernorm_ex", "pnp_op_layernorm_bwd",
             "pnp_op_text_embed", "pnp_op_itm_head", "pnp_op_itm_grad_seed", "pnp_op_patchify", "pnp_op_cls_rows",
-            "pnp_op_gemm_args", "pnp_overlay_labels", "pnp_jpeg_encode",
+            "pnp_op_gemm_args", "pnp_op_gemm_plan", "pnp_overlay_labels", "pnp_jpeg_encode",
             "pnp_crf_create", "pnp_crf_destroy", "pnp_crf_allocated_bytes", "pnp_crf_last_error", "pnp_crf_set_batch",
             "pnp_crf_infer", "pnp_crf_set_batch_aniso", "pnp_crf_set_compat", "pnp_crf_start", "pnp_crf_step", "pnp_crf_read",
             "pnp_crf_kl", "pnp_crf_create_terms", "pnp_crf_set_batch_terms", "pnp_crf_set_term_compat", "pnp_crf_infer_terms",
@@ -811,3 +817,20 @@ def streamk_status_ops():
     if r != 0:
         raise RuntimeError(f"pnp_streamk_status -> {r}")
     return n.value, t.value
+
+
+GEMM_FORMS = ("f32", "bf16", "x3", "x3a")
+GEMM_FAMILIES = ("g64", "g128", "g256", "wide", "x3_wide", "small_x3")
+GEMM_HAS = {"bias": 1, "bias_on_rows": 2, "resid": 4, "out_f32": 8, "out_t": 16, "out_lo": 32, "aux": 64}
+
+
+def gemm_plan(form, M, N, K, has=(), mode=0, row_div=0, col_div=0, col_pad=0, n_cu=256, streamk=1, sk_wgs=None, lda=None, ldb=None):
+    """What the library would launch for one GEMM (include/pnp_hip.h: pnp_op_gemm_plan), on the host: a PnpGemmPlan whose
+    `family` is also given by name (plan.name, one of GEMM_FAMILIES; None for a refused launch).  form: one of GEMM_FORMS;
+    has: names out of GEMM_HAS; sk_wgs: default n_cu, as the op-level entry points' workspace."""
+    plan = PnpGemmPlan()
+    bits = sum(GEMM_HAS[h] for h in has)
+    load_library().pnp_op_gemm_plan(GEMM_FORMS.index(form), M, N, K, K if lda is None else lda, K if ldb is None else ldb, mode, bits,
+                                    row_div, col_div, col_pad, n_cu, streamk, n_cu if sk_wgs is None else sk_wgs, C.byref(plan))
+    plan.name = GEMM_FAMILIES[plan.family] if plan.status == 0 else None
+    return plan

@@ -138,25 +138,6 @@ def gelu_grad_bound(lin_bound, lin):
     return GELU_SLOPE * lin_bound + 2e-6 * lin.abs().clamp_min(1.0)
 
 
-# ------------------------------------------------------------------------------------------ dispatch (mirror of gemm_nt)
-def gemm_branch(form, M, N, K, wide_ok):
-    """Which kernel csrc/gemm.hip gemm_nt launches.  form: "f32" | "bf16" | "x3" | "x3a"; wide_ok: the epilogue is one of
-    wide_epilogue_kind's (no aux / row_div, single output of the expected type, N % 4 == 0 unless token columns)."""
-    if form == "x3a":
-        return "small_x3"
-    if form == "x3":
-        return "x3_wide"
-    t128 = ((M + 127) // 128) * ((N + 127) // 128)
-    t256 = ((M + 255) // 256) * ((N + 255) // 256)
-    if t128 < 192:
-        return "g64"
-    if form == "bf16" and wide_ok and t256 >= 128:
-        return "wide"
-    if form == "bf16" and K >= 2048 and N >= 512:
-        return "g256"
-    return "g128"
-
-
 # ------------------------------------------------------------------------------------------ tiled product + planted faults
 def tiled_product(A, B, tile_n=64, slab=32, order="fwd", fault=None, dtype=torch.float32, sk_parts=0):
     """numpy-style emulation of the kernels' tiling: C[:, tile] = sum over k-slabs of A[:, slab] . B[tile, slab]^T, partial

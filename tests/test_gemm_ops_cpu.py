@@ -208,10 +208,103 @@ def test_softmax_restatement_uses_a_quarter_of_the_bound(case, kind):
     assert worst <= 0.25, (kind, case, worst)
 
 
-def test_dispatch_mirror_matches_the_documented_thresholds():
-    assert R.gemm_branch("f32", 100, 191 * 128, 64, False) == "g64" and R.gemm_branch("f32", 100, 191 * 128 + 1, 64, False) == "g128"
-    assert R.gemm_branch("bf16", 200, 127 * 256, 64, True) == "g128" and R.gemm_branch("bf16", 200, 127 * 256 + 4, 64, True) == "wide"
-    assert R.gemm_branch("bf16", 257, 8192, 1984, False) == "g128" and R.gemm_branch("bf16", 257, 8192, 2048, False) == "g256"
-    assert R.gemm_branch("bf16", 6144, 508, 2048, False) == "g128" and R.gemm_branch("bf16", 6144, 512, 2048, False) == "g256"
-    assert R.gemm_branch("f32", 6144, 512, 2048, False) == "g128"
+# ------------------------------------------------------------------------------------------ the library's launch plan
+# pnp_op_gemm_plan is the function gemm_nt launches from; it needs no device.  The literals below are the independent statement of
+# the dispatch (csrc/gemm.hip): they are written out, not computed from the library.
+WIDE = dict(has=("bias", "out_t"))                  # + bias -> bf16: one of the wide kernel's epilogues
+BOTH = dict(has=("bias", "out_f32", "out_t"))       # dual output: generic kernels only
+X3 = dict(has=("bias", "out_f32"))                  # + bias -> fp32 of the split forms
+
+
+def _plan(*a, **kw):
+    from pnp_ovss import hip
+    return hip.gemm_plan(*a, **kw)
+
+
+def test_gemm_plan_matches_the_documented_thresholds():
+    name = lambda *a, **kw: _plan(*a, **kw).name
+    assert name("f32", 100, 191 * 128, 64, **BOTH) == "g64" and name("f32", 100, 191 * 128 + 1, 64, has=("out_f32",)) == "g128"
+    assert name("bf16", 200, 127 * 256, 64, **WIDE) == "g128" and name("bf16", 200, 127 * 256 + 4, 64, **WIDE) == "wide"
+    assert name("bf16", 257, 8192, 1984, **BOTH) == "g128" and name("bf16", 257, 8192, 2048, **BOTH) == "g256"
+    assert name("bf16", 6144, 508, 2048, **BOTH) == "g128" and name("bf16", 6144, 512, 2048, **BOTH) == "g256"
+    assert name("f32", 6144, 512, 2048, **BOTH) == "g128"
+    assert name("bf16", 200, 127 * 256, 2048, **WIDE) == "g256" and name("bf16", 200, 127 * 256 + 4, 2048, **WIDE) == "wide"
+    assert name("x3", 1, 4, 64, **X3) == "x3_wide" and name("x3a", 1, 4, 32, **X3) == "small_x3"
     assert math.isclose(R.GELU_SLOPE, 1.13)
+
+
+def test_gemm_plan_tile_rounding_grid_and_lds_of_each_family():
+    """N is rounded to the family's own tile; the generic and text-side kernels launch one workgroup per tile, the persistent
+    ones min(tiles, CUs)."""
+    f = lambda p: (p.name, p.variant, p.dtype_bf16, p.n_pad, p.grid, p.block, p.smem, p.keeps_stamps, p.profiled)
+    assert f(_plan("f32", 100, 100, 64, **BOTH)) == ("g64", 0, 0, 128, 2 * 2, 256, 49152, 1, 0)
+    assert f(_plan("bf16", 100, 191 * 128 + 1, 64, has=("out_f32", "out_t"))) == ("g128", 0, 1, 192 * 128, 192, 256, 65536, 1, 1)
+    assert f(_plan("bf16", 257, 8196, 2048, **BOTH)) == ("g256", 0, 1, 8448, 2 * 33, 512, 131072, 1, 1)
+    assert f(_plan("bf16", 200, 127 * 256 + 4, 64, n_cu=256, **WIDE)) == ("wide", 0, 1, 128 * 256, 128, 512, 135168, 1, 1)
+    assert f(_plan("bf16", 200, 127 * 256 + 4, 64, n_cu=64, **WIDE)) == ("wide", 0, 1, 128 * 256, 64, 512, 135168, 1, 1)
+    assert f(_plan("x3", 300, 300, 128, streamk=0, **X3)) == ("x3_wide", 4, 1, 512, 4, 512, 135168, 1, 1)
+    assert f(_plan("x3", 4100, 2048, 256, streamk=0, n_cu=100, **X3)) == ("x3_wide", 4, 1, 2048, 100, 512, 135168, 1, 1)
+    assert f(_plan("x3a", 641, 3900, 64, **X3)) == ("small_x3", 0, 0, 3904, 671, 512, 49152, 0, 0)
+    # the wide epilogue kinds (the kernels' compile-time variants)
+    assert _plan("bf16", 4096, 2048, 64, has=("bias", "out_t"), mode=1).variant == 1
+    assert _plan("bf16", 4096, 2048, 64, has=("bias", "resid", "out_f32")).variant == 2
+    assert _plan("bf16", 4096, 2048, 64, has=("bias", "bias_on_rows", "out_t"), col_div=442, col_pad=448).variant == 3
+    assert _plan("x3", 64, 64, 64, has=("bias", "resid", "out_f32")).variant == 2
+    assert _plan("x3", 64, 64, 64, has=("bias", "bias_on_rows", "out_f32"), col_div=442, col_pad=448).variant == 5
+    assert _plan("x3", 64, 64, 64, has=("bias", "out_t", "out_lo"), mode=1).variant == 6
+    assert _plan("x3", 64, 64, 64, has=("bias", "out_t", "out_lo")).variant == 7
+    # more workgroups than stamp rows: a generic launch of 8193 tiles records no stamps
+    assert _plan("bf16", 1, 8192 * 128, 64, has=("out_f32",)).keeps_stamps == 1
+    assert _plan("bf16", 1, 8193 * 128, 64, has=("out_f32",)).keeps_stamps == 0
+
+
+def test_gemm_plan_text_side_forms():
+    """gemm_nt_small_x3_kernel: more than 600 workgroups and K <= 1024 -> 32-deep slabs on a three-slot 48 KB ring (variant 0);
+    else 64-deep slabs when K % 64 == 0 (1, 128 KB), 32-deep otherwise (2, 64 KB)."""
+    f = lambda M, N, K: (lambda p: (p.name, p.variant, p.grid, p.smem))(_plan("x3a", M, N, K, **X3))
+    assert f(640, 3840, 1024) == ("small_x3", 1, 600, 131072)              # 600 workgroups: not more than 600
+    assert f(640, 3844, 1024) == ("small_x3", 0, 610, 49152)
+    assert f(640, 3844, 32) == ("small_x3", 0, 610, 49152)
+    assert f(640, 3844, 1088) == ("small_x3", 1, 610, 131072)              # K > 1024
+    assert f(640, 3844, 1056) == ("small_x3", 2, 610, 65536)
+    assert f(64, 64, 64) == ("small_x3", 1, 1, 131072)
+    assert f(64, 64, 96) == ("small_x3", 2, 1, 65536)
+    assert _plan("x3a", 64, 64, 48, **X3).status == -22 and _plan("x3a", 64, 66, 64, **X3).status == -22
+
+
+def test_gemm_plan_stream_k_split():
+    """sk_full = rounds * CUs tiles are walked whole, the tail's K / 64 slab pairs are dealt sk_upw = ceil(tail * (K / 64) / CUs) per
+    workgroup over a grid of all CUs.  5000 x 2304 is 20 x 9 = 180 tiles."""
+    f = lambda p: (p.name, p.grid, p.sk_full, p.sk_upw)
+    sk = lambda **kw: f(_plan("x3", 5000, 2304, 1024, **X3, **kw))
+    assert sk(streamk=2, n_cu=64) == ("x3_wide", 64, 128, 13)             # 2 rounds, tail 52: ceil(52 * 16 / 64)
+    assert sk(streamk=2, n_cu=256) == ("x3_wide", 256, 0, 12)             # no whole round, tail 180: ceil(180 * 16 / 256)
+    assert sk(streamk=0, n_cu=64) == ("x3_wide", 64, 0, 0)
+    assert sk(streamk=2, n_cu=64, sk_wgs=63) == ("x3_wide", 64, 0, 0)     # workspace smaller than the grid
+    assert sk(streamk=2, n_cu=64, sk_wgs=0) == ("x3_wide", 64, 0, 0)
+    assert sk(streamk=2, n_cu=60) == ("x3_wide", 60, 0, 0)                # 180 = 3 x 60: no tail
+    assert sk(streamk=2, n_cu=256, sk_wgs=256) == sk(streamk=2, n_cu=256)
+    # the cost model (mode 1) on the two launches csrc/gemm.hip names: a small tail of deep tiles pays (8 x 2305 rows, fc2: 292
+    # tiles of K = 4096 -> tail 36, 9 pairs each), the bench batch's 732 tiles of K = 1024 do not
+    assert f(_plan("x3", 8 * 2305, 1024, 4096, streamk=1, n_cu=256, **X3)) == ("x3_wide", 256, 256, 9)
+    assert f(_plan("x3", 15470, 3072, 1024, streamk=1, n_cu=256, **X3)) == ("x3_wide", 256, 0, 0)
+    # only the split-bf16 wide kernel has the tail: the bf16 wide kernel of the same shape keeps whole tiles
+    assert f(_plan("bf16", 5000, 2304 * 4, 1024, streamk=2, n_cu=64, **WIDE)) == ("wide", 64, 0, 0)
+
+
+def test_gemm_plan_refusals():
+    """The checks of gemm_nt, in front of any launch: PNP_ERR_ARG = -22 and an empty plan."""
+    bad = lambda *a, **kw: (lambda p: (p.status, p.name, p.grid))(_plan(*a, **kw)) == (-22, None, 0)
+    assert bad("f32", 0, 64, 64, **BOTH) and bad("f32", 8, 0, 64, **BOTH) and bad("f32", 8, 64, 0, **BOTH)
+    assert bad("f32", 8, 64, 48, **BOTH) and bad("bf16", 8, 64, 32, **BOTH) and bad("x3", 8, 64, 32, **X3)
+    assert bad("f32", 8, 64, 64, lda=66, **BOTH) and bad("bf16", 8, 64, 64, ldb=68, **BOTH)
+    for N in (65, 66, 67):                                               # four-column reads past column N
+        assert bad("bf16", 8, N, 64, has=("bias", "out_f32")) and bad("f32", 8, N, 64, has=("resid", "out_f32"))
+        assert bad("f32", 8, N, 64, has=("aux", "out_f32"), mode=1)
+        assert _plan("f32", 8, N, 64, has=("bias", "bias_on_rows", "out_f32")).name == "g64"
+    # a split launch whose epilogue is not one of the wide kinds: dual output, a GELU without the pair, token pairs with an odd N
+    assert bad("x3", 64, 64, 64, has=("bias", "out_f32", "out_t")) and bad("x3", 64, 64, 64, has=("bias", "out_f32"), mode=1)
+    assert bad("x3", 64, 63, 64, has=("bias", "bias_on_rows", "out_f32"), col_div=442, col_pad=448)
+    assert bad("x3", 64, 63, 64, has=("bias", "bias_on_rows", "out_f32"))
+    assert bad("x3", 64, 66, 64, **X3) and bad("x3", 64, 64, 64, has=("bias", "out_f32", "aux"))
+    assert _plan("bf16", 255, 128 * 256 + 37, 64, has=("bias", "bias_on_rows", "out_t"), col_div=442, col_pad=448).name == "g128"

@@ -9,7 +9,7 @@ by element with float64 (tests/_gemm_refs.py), with both input families:
 Common to every case: operands sit in buffers with leading dimensions larger than their width whose pad columns (and the
 elements behind the last row, the bias and the residual) hold NaN; every output and stash is a NaN-filled Guarded2D whose pad
 columns, skipped rows, columns past N and guard blocks must keep their sentinel bit for bit.  The branch a shape lands on is
-asserted with _gemm_refs.gemm_branch (a mirror of gemm_nt's dispatch) and is part of the test id.
+part of the test id and is asserted against the library's own launch plan (pnp_op_gemm_plan, the function gemm_nt launches from).
 Run on the MI355X box:  python -m pytest tests/test_gemm_ops_gpu.py -m gpu -x -q
 """
 import pytest
@@ -48,18 +48,16 @@ def E(bias=None, resid=False, mode=0, aux=False, out="f32", row_div=0, col=None,
     return dict(bias=bias, resid=resid, mode=mode, aux=aux, out=out, row_div=row_div, col=col, role=role)
 
 
-def _wide_ok(form, e, N):
-    """wide_epilogue_kind of csrc/gemm.hip for the bf16 form."""
-    if form != "bf16" or e["aux"] or e["mode"] == 2 or e["row_div"]:
-        return False
-    div = e["col"][0] if e["col"] else 0
-    if e["mode"] == 0 and not e["resid"] and e["out"] == "t" and e["bias"] != "col" and (div > 0 or e["bias"] == "row"):
-        return bool(div & 1) or N % 2 == 0
-    if div or e["bias"] == "row" or N % 4:
-        return False
-    if e["out"] == "t" and not e["resid"]:
-        return e["mode"] in (0, 1)
-    return e["mode"] == 0 and e["resid"] and e["out"] == "f32"
+def _plan(form, M, N, K, e, **kw):
+    """The library's launch plan (pnp_ovss.hip.gemm_plan) of run_case's launch of epilogue `e`: the operands and outputs
+    run_case hands the entry point, as presence bits."""
+    from pnp_ovss import hip
+    has = {"bias": bool(e["bias"]), "bias_on_rows": e["bias"] == "row", "resid": e["resid"],
+           "out_f32": form == "x3a" or e["out"] in ("f32", "both"), "out_t": form != "x3a" and e["out"] in ("t", "both", "split"),
+           "out_lo": e["out"] == "split", "aux": (e["mode"] == 1 and e["aux"]) or e["mode"] == 2}
+    div, pad = e["col"] or (0, 0)
+    return hip.gemm_plan(form, M, N, K, has=[h for h, on in has.items() if on], mode=e["mode"], row_div=e["row_div"], col_div=div,
+                         col_pad=pad, lda=K + 16, ldb=K + 16, **kw)
 
 
 def _accepts(form, e, N):
@@ -80,7 +78,7 @@ def run_case(lib, acc, form, M, N, K, e, family, seed, branch=None):
     compare launches with each other."""
     case = f"{form} {family} M={M} N={N} K={K} " + " ".join(f"{k}={v}" for k, v in e.items() if v not in (None, False, 0))
     if branch is not None:
-        assert R.gemm_branch(form, M, N, K, _wide_ok(form, e, N)) == branch, (case, "lands on another kernel than the id says")
+        assert _plan(form, M, N, K, e).name == branch, (case, "lands on another kernel than the id says")
     split = form in ("x3", "x3a")
     bf16 = form == "bf16"
     exact = family == "exact"
@@ -272,7 +270,7 @@ def _sweep(lib, acc, form, branch, shapes, linear, nonlin, random_every=2):
     epilogue and the non-linear ones at every `random_every`-th shape (a deliberate subsample: on a linear epilogue the exact
     family is the stronger check, the random one adds the rounding of non-integer data)."""
     n = 0
-    lands = lambda e, M, N, K: _accepts(form, e, N) and R.gemm_branch(form, M, N, K, _wide_ok(form, e, N)) == branch
+    lands = lambda e, M, N, K: _accepts(form, e, N) and _plan(form, M, N, K, e).name == branch
     for i, (M, N, K) in enumerate(shapes):
         for e in linear:
             if lands(e, M, N, K):
@@ -289,7 +287,7 @@ def _sweep(lib, acc, form, branch, shapes, linear, nonlin, random_every=2):
 
 @pytest.mark.parametrize("form", ["f32", "bf16"])
 def test_branch_generic_64x64(lib, form):
-    """launch_big<T, 64, 64, 32, 32, 3> (fewer than 192 tiles of 128): M in {63, 64, 65, 1}, N on and off the 64-column tile with
+    """gemm_nt_big_kernel<T, 64, 64, 32, 32, 3> (fewer than 192 tiles of 128): M in {63, 64, 65, 1}, N on and off the 64-column tile with
     N % 4 in {0, 1, 2, 3}, K = one slab (the smallest the type accepts), two and sixteen."""
     bk = 64 if form == "bf16" else 32
     acc = Acc(f"gpu/gemm/g64/{form}")
@@ -302,7 +300,7 @@ def test_branch_generic_64x64(lib, form):
 
 @pytest.mark.parametrize("form", ["f32", "bf16"])
 def test_branch_generic_128x128(lib, form):
-    """launch_big<T, 128, 128, 64, 64, 2> (192 tiles of 128 or more, bf16: K < 2048): ragged row tile, ragged column tile and
+    """gemm_nt_big_kernel<T, 128, 128, 64, 64, 2> (192 tiles of 128 or more, bf16: K < 2048): ragged row tile, ragged column tile and
     the partial-fragment store (n + 3 >= N) against the reference."""
     bk = 64 if form == "bf16" else 32
     acc = Acc(f"gpu/gemm/g128/{form}")
@@ -314,7 +312,7 @@ def test_branch_generic_128x128(lib, form):
 
 
 def test_branch_generic_256x256_bf16(lib):
-    """launch_big<bf16, 256, 256, 128, 64, 2, false> (K >= 2048, N >= 512, 192 tiles of 128 or more and fewer than 128 tiles of
+    """gemm_nt_big_kernel<bf16, 256, 256, 128, 64, 2, false> (K >= 2048, N >= 512, 192 tiles of 128 or more and fewer than 128 tiles of
     256, or an epilogue the wide kernel does not have): ViT-L fc2 in bf16 mode at 7..17 images.  Also on a large problem (136
     tiles of 256) through the dual output and the GELU stash."""
     acc = Acc("gpu/gemm/g256/bf16")
@@ -549,20 +547,20 @@ def test_gemm_stamps_time_the_shipped_kernels(lib):
         M, N, K = 96, 128, 64
         A, B, bias = rnd(M, K), rnd(N, K), rnd(N)
         run = lambda out: lib.pnp_op_gemm(0, _ptr(A), K, _ptr(B), K, M, N, K, _ptr(bias), None, 0, _ptr(out), N, 0, None)
-        return run, (M, N, torch.float32), 4, R.gemm_branch("f32", M, N, K, False) == "g64"
+        return run, (M, N, torch.float32), 4, ("g64", _plan("f32", M, N, K, E(bias="col"), n_cu=cus, streamk=0))
 
     def split_wide():
         M, N, K = 300, 512, 128
         (Ah, Al), (Bh, Bl), bias = R.split_pair(rnd(M, K)), R.split_pair(rnd(N, K) * 0.25), rnd(N)
         run = lambda out: lib.pnp_op_gemm_x3(_ptr(Ah), _ptr(Al), K, _ptr(Bh), _ptr(Bl), K, M, N, K, _ptr(bias), 0, None, 0, _ptr(out), N,
                                              None, None, 0, 0, 0, 0, None)
-        return run, (M, N, torch.float32), 4, R.gemm_branch("x3", M, N, K, False) == "x3_wide"
+        return run, (M, N, torch.float32), 4, ("x3_wide", _plan("x3", M, N, K, E(bias="col"), n_cu=cus, streamk=0))
 
     def bf16_wide():
         M, N, K = 4096, 2048, 64
         A, B, bias = rnd(M, K).bfloat16(), rnd(N, K).bfloat16(), rnd(N)
         run = lambda out: lib.pnp_op_gemm_ex(1, _ptr(A), K, _ptr(B), K, M, N, K, _ptr(bias), None, 0, None, 0, _ptr(out), N, 0, None)
-        return run, (M, N, torch.bfloat16), 128, R.gemm_branch("bf16", M, N, K, True) == "wide"
+        return run, (M, N, torch.bfloat16), 128, ("wide", _plan("bf16", M, N, K, E(bias="col", out="t"), n_cu=cus, streamk=0))
 
     def launch(run, shape):
         out = torch.zeros(shape[0], shape[1], dtype=shape[2], device=DEV)
@@ -579,9 +577,10 @@ def test_gemm_stamps_time_the_shipped_kernels(lib):
         assert lib.pnp_set_tuning(b"streamk", 0) == 0
         for case in (fp32_generic, split_wide, bf16_wide):
             name = case.__name__
-            run, shape, tiles, lands = case()
-            assert lands, (name, "lands on another kernel")
+            run, shape, tiles, (branch, plan) = case()
+            assert plan.name == branch, (name, "lands on another kernel")
             grid = min(tiles, cus)
+            assert plan.grid == grid and plan.keeps_stamps == 1, (name, plan.grid, grid)
             off = launch(run, shape)
             assert bool(off.ne(0).any()), name
             assert lib.pnp_set_tuning(b"gemm_stamps", 1) == 0
@@ -596,6 +595,7 @@ def test_gemm_stamps_time_the_shipped_kernels(lib):
                 assert (st[:grid, a] <= st[:grid, b]).all(), (name, a, b)
             assert (st[:grid] != before[:grid]).any(axis=1).all(), (name, "a launched workgroup left no stamps")
             assert (st[grid:] == before[grid:]).all(), (name, "rows past the grid were written")
+            assert int((st != before).any(axis=1).sum()) == plan.grid, (name, "stamp rows written != the plan's grid")
             assert lib.pnp_set_tuning(b"gemm_stamps", 0) == 0
             assert torch.equal(off, launch(run, shape)), name
             assert (stamps(grid + 8) == st).all(), (name, "a launch with stamps off wrote stamps")
@@ -616,7 +616,8 @@ def test_gemm_stamps_skip_launches_with_more_workgroups_than_rows(lib):
 
     def launch(tiles):
         N = tiles * 128
-        assert R.gemm_branch("bf16", 1, N, K, False) == "g128"
+        plan = _plan("bf16", 1, N, K, E())
+        assert plan.name == "g128" and plan.grid == tiles and plan.keeps_stamps == int(tiles <= rows)
         out = torch.zeros(1, N, device=DEV)
         assert lib.pnp_op_gemm(1, _ptr(A), K, _ptr(B), K, 1, N, K, None, None, 0, _ptr(out), N, 0, None) == 0
         torch.cuda.synchronize()
