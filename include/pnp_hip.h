@@ -328,6 +328,45 @@ int pnp_crf_step_terms(pnp_crf* c, int32_t n, const float* weights, void* stream
 /* Lattice points of one term over the whole batch, as the last successful set_batch built it: term < T of a terms batch; 0
  * (Gaussian) or 1 (bilateral) of a two-term batch.  -1 for a null solver, no batch, or no such term. */
 int64_t pnp_crf_lattice_points(const pnp_crf* c, int32_t term);
+/* ---- a term's lattice, stage by stage (for tests: what a lattice build left, and parts of one filter pass) ----
+ * pnp_crf_lattice_view_get: the arrays of one term's lattice as the last successful set_batch left them -- device pointers into the
+ * solver's workspace, valid until the next set_batch or pnp_crf_destroy, to be read only -- and their sizes.  term as
+ * pnp_crf_lattice_points takes it.  Returns pointers and sizes: it allocates nothing, does not synchronise (set_batch did) and
+ * writes no device memory.  Lattice ids are internal: points are numbered image by image (idbase) along a Z-order curve of
+ * their first contributor pixel; every id below is global to the batch except those of nbr8, which are local to the image.
+ * PNP_ERR_ARG: null solver or view, no such term; PNP_ERR_STATE: no batch is set. */
+typedef struct pnp_crf_lattice_view {
+    int32_t D1;                  /* d + 1: lattice points per pixel, and blur axes */
+    int32_t images;              /* B */
+    int64_t cap;                 /* stride, in points, of the axis tables n1 / n2 / nbr8 */
+    int64_t points;              /* M = idbase[B] */
+    int64_t entries;             /* (pixels of the batch) * D1 */
+    const float* bary;           /* [entries] barycentric weight of (pixel, vertex) = pixel * D1 + vertex */
+    const int32_t* offset;       /* [entries] lattice id of (pixel, vertex) */
+    const uint32_t* vals;        /* [entries] contributor lists: (pixel, vertex) indices, point by point in id order */
+    const void* ent;             /* [entries] the same lists as 16-byte records {uint32 pixel, float w, float nr, uint32 pad} */
+    const int32_t* seg_lo;       /* [M] a point's contributors are vals[seg_lo .. seg_hi) */
+    const int32_t* seg_hi;
+    const int32_t* idbase;       /* [B + 1] first lattice id of every image */
+    const int32_t* n1;           /* [D1][cap] blur neighbours along every axis, -1 = absent */
+    const int32_t* n2;
+    const void* nbr8;            /* [D1 / 2][cap] 32-byte records {ia, id, pa, pd, aa, ad, da, dd} (int32) of the two-axis blur */
+    const float* norm;           /* [pixels of the batch] the term's normaliser */
+} pnp_crf_lattice_view;
+int pnp_crf_lattice_view_get(pnp_crf* c, int32_t term, pnp_crf_lattice_view* out);
+/* pnp_crf_probe_filter: part of one filter pass of `term` on rows the caller brings, through the kernels and the dispatch of the
+ * mean-field itself.  d_in: (K_b, H_b * W_b) float32 planes laid out as d_unary; they take the place of the marginals.  stage:
+ *   PNP_CRF_PROBE_SPLAT    the splat alone
+ *   PNP_CRF_PROBE_FORWARD  splat and the D1 blur axes as an update runs them (axes in pairs, a single last axis)
+ *   PNP_CRF_PROBE_REVERSE  splat and the axes D1 - 1 .. 0 one by one, as the backward pass runs them
+ *   PNP_CRF_PROBE_SLICE    the message of the forward result: norm * alpha * slice
+ * d_out, SPLAT / FORWARD / REVERSE: the value rows of the lattice without their padding, K_b floats per lattice point in id
+ * order, image after image: sum_b (idbase[b + 1] - idbase[b]) * K_b floats.  SLICE: planes laid out as d_in.  The solver's
+ * marginals are overwritten and its stepwise state is dropped (pnp_crf_start begins anew).  A two-term solver allocates B
+ * descriptors on its first probe of term 1 (counted in pnp_crf_allocated_bytes).  Errors as pnp_crf_lattice_view_get; a stage
+ * out of range or a null pointer is PNP_ERR_ARG. */
+enum { PNP_CRF_PROBE_SPLAT = 0, PNP_CRF_PROBE_FORWARD = 1, PNP_CRF_PROBE_REVERSE = 2, PNP_CRF_PROBE_SLICE = 3 };
+int pnp_crf_probe_filter(pnp_crf* c, int32_t term, int32_t stage, const float* d_in, float* d_out, void* stream);
 /* ---- gradients of the feature-term mean-field (reverse mode; densecrf's DenseCRF::gradient) ----
  * The mean-field of pnp_crf_infer_terms as a differentiable function of the unary energies and of the terms' compatibilities
  * (scalar weight, vector, matrix).  Features, lattices and normalisers are constants of the batch.  Term t's operator A_t =

@@ -1020,11 +1020,15 @@ static void crf_splat(const CrfLattice& L, const PostDesc* d_imgs, int img0, int
 
 // lattice(norm * Q) for images [img0, img0+nimg): splat + (d+1) blurs (the normaliser rides in the contributor records).
 // reverse: lattice^T(norm * Q), the blur axes d, d - 1, .. 0 one crf_blur4_kernel pass each (the adjoint of the forward
-// product of symmetric axis blurs).  Returns the buffer holding the result.
+// product of symmetric axis blurs).  Returns the buffer holding the result.  splat_only: the splatted rows, no axis.
 int crf_filter(const CrfLattice& L, const PostDesc* d_imgs, int img0, int nimg, const float* Q,
-               float* va, float* vb, const float** result, int max_kp, hipStream_t s, bool reverse) {
+               float* va, float* vb, const float** result, int max_kp, hipStream_t s, bool reverse, bool splat_only) {
     const int D = L.D1 - 1;
     crf_splat(L, d_imgs, img0, nimg, Q, va, max_kp, s);
+    if (splat_only) {
+        *result = va;
+        return ok();
+    }
     static PerDeviceInt gb2, gb1;                            // per device ordinal (common.h)
     const int nb2 = gb2.get([] { return resident_grid(crf_blur4x2_kernel, 256, 0); });
     const int nb1 = gb1.get([] { return resident_grid(crf_blur4_kernel, 256, 0); });

@@ -202,6 +202,22 @@ __global__ void crf_kl_final_kernel(const PostDesc* __restrict__ desc, const dou
     out[b] = s;
 }
 
+// pnp_crf_probe_filter: the value rows of a lattice (Kp floats per point at voff[which] of every image) without their pad, K
+// floats per point in id order, image after image
+__global__ __launch_bounds__(256) void crf_probe_rows_kernel(const int* __restrict__ idbase, const PostDesc* __restrict__ desc, int which,
+                                                             const float* __restrict__ val, float* __restrict__ out) {
+    const int b = blockIdx.y;
+    size_t base = 0;
+    for (int i = 0; i < b; i++) base += (size_t)(idbase[i + 1] - idbase[i]) * desc[i].K;
+    const int K = desc[b].K, Kp = desc[b].Kp;
+    const size_t n = (size_t)(idbase[b + 1] - idbase[b]) * K;
+    const float* const v = val + desc[b].voff[which];
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        const size_t p = i / K;
+        out[base + i] = v[p * Kp + (i - p * K)];
+    }
+}
+
 }  // namespace pnp
 
 // ------------------------------------------------------------------------------------------ the solver
@@ -251,6 +267,10 @@ struct pnp_crf {
     CrfGradWorkspace gw;
     size_t q_floats = 0;
     std::vector<int> h_tile0;
+    // -- pnp_crf_probe_filter on the bilateral term of a two-term batch: the batch's descriptors with voff[0] = voff[1], as
+    // crf_slice_add reads a term's value rows (allocated by the first such call)
+    PostDesc* d_pdesc = nullptr;
+    std::vector<PostDesc> pdesc;
     char err[512] = {0};
 };
 
@@ -927,5 +947,85 @@ extern "C" int pnp_crf_kl(pnp_crf* c, float pos_w, float bi_w, double* h_out_per
     CHIP(c, hipGetLastError());
     CHIP(c, hipMemcpyAsync(h_out_per_image, c->kl_out, sizeof(double) * c->B, hipMemcpyDeviceToHost, s));
     CHIP(c, hipStreamSynchronize(s));
+    return PNP_OK;
+}
+
+// ------------------------------------------------------------------------------------------ a term's lattice, stage by stage
+namespace {
+
+// term of the batch that is set -> its lattice and normaliser; errors as pnp_crf_lattice_points' callers expect them
+int crf_term_lattice(pnp_crf* c, int32_t term, const CrfLattice** L, const float** norm) {
+    if (int r = crf_need_batch(c)) return r;
+    const int T = c->terms_batch ? c->T : 2;
+    if (term < 0 || term >= T) return cfail(c, PNP_ERR_ARG, "term = %d: the batch has terms 0..%d", term, T - 1);
+    *L = c->terms_batch ? &c->ws.tlat[term] : &c->ws.lat[term];
+    *norm = c->terms_batch ? c->ws.tnorm[term] : c->ws.norm[term];
+    return PNP_OK;
+}
+
+}  // namespace
+
+extern "C" int pnp_crf_lattice_view_get(pnp_crf* c, int32_t term, pnp_crf_lattice_view* out) {
+    if (!c) return PNP_ERR_ARG;
+    if (!out) return cfail(c, PNP_ERR_ARG, "the view is null");
+    const CrfLattice* L = nullptr;
+    const float* norm = nullptr;
+    if (int r = crf_term_lattice(c, term, &L, &norm)) return r;
+    out->D1 = L->D1;
+    out->images = c->B;
+    out->cap = (int64_t)L->cap;
+    out->points = c->terms_batch ? c->ws.tlat_points[term] : c->ws.lat_points[term];
+    out->entries = (int64_t)c->h_label_off[c->B] * L->D1;
+    out->bary = L->bary;
+    out->offset = L->offset;
+    out->vals = L->vals;
+    out->ent = L->ent;
+    out->seg_lo = L->seg_lo;
+    out->seg_hi = L->seg_hi;
+    out->idbase = L->idbase;
+    out->n1 = L->n1;
+    out->n2 = L->n2;
+    out->nbr8 = L->nbr8;
+    out->norm = norm;
+    return PNP_OK;
+}
+
+extern "C" int pnp_crf_probe_filter(pnp_crf* c, int32_t term, int32_t stage, const float* d_in, float* d_out, void* stream) {
+    if (!c) return PNP_ERR_ARG;
+    if (stage < PNP_CRF_PROBE_SPLAT || stage > PNP_CRF_PROBE_SLICE)
+        return cfail(c, PNP_ERR_ARG, "stage = %d: splat (0), forward (1), reverse (2) or slice (3)", stage);
+    if (!d_in || !d_out) return cfail(c, PNP_ERR_ARG, "null pointers (d_in, d_out)");
+    const CrfLattice* L = nullptr;
+    const float* norm = nullptr;
+    if (int r = crf_term_lattice(c, term, &L, &norm)) return r;
+    hipStream_t s = (hipStream_t)stream;
+    CHIP(c, hipSetDevice(c->device));
+    const int B = c->B;
+    // the term's descriptors: PostDesc::voff[L->which] = its value rows for the filter, voff[0] for crf_slice_add
+    const PostDesc* desc = c->d_desc;
+    if (c->terms_batch) {
+        desc = c->d_tdesc + (size_t)term * c->maxB;
+    } else if (term == 1) {
+        if (!c->d_pdesc)
+            if (int r = calloc_dev(c, &c->d_pdesc, (size_t)c->maxB)) return r;
+        c->pdesc = c->desc;
+        for (PostDesc& d : c->pdesc) d.voff[0] = d.voff[1];
+        // (pageable host memory is staged at enqueue time: pdesc may be rewritten by the next call)
+        CHIP(c, hipMemcpyAsync(c->d_pdesc, c->pdesc.data(), sizeof(PostDesc) * B, hipMemcpyHostToDevice, s));
+        desc = c->d_pdesc;
+    }
+    const bool gauss = !c->terms_batch && term == 0;
+    float* const va = gauss ? c->ws.vga : c->ws.va;
+    float* const vb = gauss ? c->ws.vgb : c->ws.vb;
+    c->started = false;                           // Q holds the caller's rows from here on
+    CK(c, crf_planes_rows(true, c->d_desc, const_cast<float*>(d_in), c->ws.Q, B, c->maxHW, c->kp_max, s));
+    const float* val = nullptr;
+    CK(c, crf_filter(*L, desc, 0, B, c->ws.Q, va, vb, &val, c->kp_max, s, stage == PNP_CRF_PROBE_REVERSE, stage == PNP_CRF_PROBE_SPLAT));
+    if (stage == PNP_CRF_PROBE_SLICE) {
+        CK(c, crf_slice_add(*L, desc, 0, B, val, norm, c->ws.Q, true, s));
+        return crf_emit_q(c, d_out, s);
+    }
+    hipLaunchKernelGGL(crf_probe_rows_kernel, dim3(64, B), dim3(256), 0, s, L->idbase, desc, L->which, val, d_out);
+    CHIP(c, hipGetLastError());
     return PNP_OK;
 }

@@ -187,9 +187,10 @@ int crf_lattice_norm(const CrfLattice& L, const PostDesc* d_imgs, int B, int max
                      float* norm_out, hipStream_t s);
 // crf_meanfield.hip: the forward mean-field
 // lattice(norm * Q): splat and the d + 1 blur axes; *result = the buffer that holds the filtered values (va or vb).  reverse:
-// lattice^T(norm * Q), the blur axes in reverse order (the adjoint of the filter: the reverse mode's)
+// lattice^T(norm * Q), the blur axes in reverse order (the adjoint of the filter: the reverse mode's).  splat_only: no blur axes,
+// *result = the splatted rows (pnp_crf_probe_filter)
 int crf_filter(const CrfLattice& L, const PostDesc* d_imgs, int img0, int nimg, const float* Q,
-               float* va, float* vb, const float** result, int max_kp, hipStream_t s, bool reverse = false);
+               float* va, float* vb, const float** result, int max_kp, hipStream_t s, bool reverse = false, bool splat_only = false);
 // label output of the LAST mean-field update (argmax over the marginals it has just normalised, np.argmax semantics, remapped
 // through the per-image LUT): lab[g] = label map of channel group g, null = no labels from this launch
 struct CrfLabelOut {

@@ -231,6 +231,76 @@ class _Solver:
             _raise(self.lib, self.h, r, "pnp_crf_read")
         return self._split(d_q, d_lab)
 
+    # ---- a term's lattice stage by stage (pnp_crf_lattice_view_get / pnp_crf_probe_filter): for tests
+    def _view(self, term):
+        self._outputs("lattice_arrays", False, False)
+        v = hip.PnpCrfLatticeView()
+        r = self.lib.pnp_crf_lattice_view_get(self.h, int(term), C.byref(v))
+        if r != 0:
+            _raise(self.lib, self.h, r, "pnp_crf_lattice_view_get")
+        return v
+
+    def lattice_arrays(self, term):
+        """The lattice of `term` (0 .. T - 1 of a terms batch; 0 Gaussian / 1 bilateral) as the last set_batch built it: a dict
+        of numpy arrays trimmed to their live sizes -- M = idbase[B] points, E = pixels * D1 entries.  bary (E,) float32; offset,
+        vals (E,); ent (E,) records (pixel, w, nr, pad); seg_lo, seg_hi (M,); idbase (B + 1,); n1, n2 (D1, M); nbr8 (D1 // 2, M, 8)
+        image-local ids in the order ia, id, pa, pd, aa, ad, da, dd; norm (pixels,); and the numbers D1, cap, points."""
+        v = self._view(term)
+        D1, M, E, B, cap = int(v.D1), int(v.points), int(v.entries), int(v.images), int(v.cap)
+
+        def arr(ptr, count, dtype):
+            # count 4-byte words at ptr as a host array of dtype (read as int32 bits, whatever they hold)
+            t = torch.as_tensor(hip._DevView(ptr, (count,), "<i4"), device=self.device)
+            return t.cpu().numpy().view(dtype)
+        i4, u4, f4 = np.int32, np.uint32, np.float32
+        with torch.cuda.device(self.device):
+            torch.cuda.synchronize()
+            out = dict(D1=D1, cap=cap, points=M, bary=arr(v.bary, E, f4), offset=arr(v.offset, E, i4), vals=arr(v.vals, E, u4),
+                       seg_lo=arr(v.seg_lo, M, i4), seg_hi=arr(v.seg_hi, M, i4), idbase=arr(v.idbase, B + 1, i4),
+                       norm=arr(v.norm, E // D1, f4))
+            out["ent"] = arr(v.ent, 4 * E, i4).view(np.dtype([("pixel", "<u4"), ("w", "<f4"), ("nr", "<f4"), ("pad", "<u4")]))
+            # the axis tables have rows of `cap` points: the live part of every row
+            out["n1"] = np.stack([arr(v.n1 + 4 * j * cap, M, i4) for j in range(D1)])
+            out["n2"] = np.stack([arr(v.n2 + 4 * j * cap, M, i4) for j in range(D1)])
+            out["nbr8"] = np.stack([arr(v.nbr8 + 32 * p * cap, 8 * M, i4).reshape(M, 8) for p in range(D1 // 2)])
+        return out
+
+    PROBE_STAGES = {"splat": 0, "forward": 1, "reverse": 2, "slice": 3}        # PNP_CRF_PROBE_*
+
+    def probe_filter(self, term, stage, planes, out=None):
+        """pnp_crf_probe_filter: part of one filter pass of `term` on `planes` -- a device float32 tensor laid out as the unary
+        energies of the batch, (K_b, H_b * W_b) blocks back to back -- through the mean-field's own kernels.  stage: "splat",
+        "forward", "reverse" -> per image a (M_b, K_b) device tensor of lattice value rows in id order; "slice" -> per image the
+        (K_b, H_b, W_b) message.  out: a device float32 buffer to write into (default: a new one).  Overwrites the solver's
+        marginals (start() anew)."""
+        self._outputs("probe_filter", False, False)
+        plan, sizes, labels = self._plan
+        if stage not in self.PROBE_STAGES:
+            raise ValueError(f"stage is one of {sorted(self.PROBE_STAGES)}, not {stage!r}")
+        if planes.dtype != torch.float32 or planes.numel() != plan["total_unary"]:
+            raise ValueError("planes do not match the sizes and label counts of the batch")
+        v = self._view(term)
+        with torch.cuda.device(self.device):
+            torch.cuda.synchronize()
+            idbase = torch.as_tensor(hip._DevView(v.idbase, (int(v.images) + 1,), "<i4"), device=self.device).cpu().numpy()
+        counts = [int(idbase[b + 1] - idbase[b]) for b in range(len(sizes))]
+        need = plan["total_unary"] if stage == "slice" else sum(m * k for m, k in zip(counts, labels))
+        if out is None:
+            out = torch.empty(need, dtype=torch.float32, device=self.device)
+        if out.dtype != torch.float32 or out.numel() < need:
+            raise ValueError(f"out holds {out.numel()} floats, the stage writes {need}")
+        with torch.cuda.device(self.device):
+            r = self.lib.pnp_crf_probe_filter(self.h, int(term), self.PROBE_STAGES[stage], hip._ptr(planes), hip._ptr(out), hip._stream())
+        if r != 0:
+            _raise(self.lib, self.h, r, "pnp_crf_probe_filter")
+        if stage == "slice":
+            return self._split(out, None)[1]
+        res, at = [], 0
+        for m, k in zip(counts, labels):
+            res.append(out[at:at + m * k].view(m, k))
+            at += m * k
+        return res
+
     def _split(self, d_q, d_lab):
         plan, sizes, labels = self._plan
         want_q, want_labels = d_q is not None, d_lab is not None

@@ -44,6 +44,11 @@ class PnpCrfTerm(C.Structure):
     _fields_ = [("dims", C.c_int32), ("d_features", C.c_void_p)]
 
 
+class PnpCrfLatticeView(C.Structure):
+    _fields_ = [("D1", C.c_int32), ("images", C.c_int32), ("cap", C.c_int64), ("points", C.c_int64), ("entries", C.c_int64)] + \
+               [(n, C.c_void_p) for n in ("bary", "offset", "vals", "ent", "seg_lo", "seg_hi", "idbase", "n1", "n2", "nbr8", "norm")]
+
+
 class PnpGemmPlan(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("status", "family", "variant", "dtype_bf16", "n_pad", "grid", "block", "smem",
                                          "keeps_stamps", "profiled", "sk_full", "sk_upw")]
@@ -151,6 +156,8 @@ def load_library():
         "pnp_crf_reserve_grad": (i32, [vp]),
         "pnp_crf_infer_terms_saved": (i32, [vp, i32, C.POINTER(f32), vp, vp, vp, vp]),
         "pnp_crf_backward_terms": (i32, [vp, i32, C.POINTER(f32), vp, vp, vp, C.POINTER(vp), vp]),
+        "pnp_crf_lattice_view_get": (i32, [vp, i32, C.POINTER(PnpCrfLatticeView)]),
+        "pnp_crf_probe_filter": (i32, [vp, i32, i32, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)          # AttributeError here = ABI drift, fail loudly
@@ -176,7 +183,7 @@ EXPORTED = ["pnp_create", "pnp_create_shared", "pnp_destroy", "pnp_last_error", 
             "pnp_crf_infer", "pnp_crf_set_batch_aniso", "pnp_crf_set_compat", "pnp_crf_start", "pnp_crf_step", "pnp_crf_read",
             "pnp_crf_kl", "pnp_crf_create_terms", "pnp_crf_set_batch_terms", "pnp_crf_set_term_compat", "pnp_crf_infer_terms",
             "pnp_crf_step_terms", "pnp_crf_lattice_points", "pnp_crf_reserve_grad", "pnp_crf_infer_terms_saved",
-            "pnp_crf_backward_terms"]
+            "pnp_crf_backward_terms", "pnp_crf_lattice_view_get", "pnp_crf_probe_filter"]
 
 
 PROJ_NAMES = ("vision_proj.weight", "vision_proj.bias", "text_proj.weight", "text_proj.bias")      # the optional ITC projections

@@ -73,6 +73,7 @@ class Lattice:
         self.n1 = np.zeros((d + 1, M), np.int64)
         self.n2 = np.zeros((d + 1, M), np.int64)
         wide = ukeys.astype(np.int32)
+        self.keys = wide                                     # (M, d) the lattice points' keys, in id order
         for j in range(d + 1):
             a, b = wide - 1, wide + 1
             if j < d:
@@ -91,23 +92,37 @@ class Lattice:
         ids[inv[:M]] = np.arange(M)
         return ids[inv[M:]]
 
-    def compute(self, x):
-        """lattice_compute: x (N, vs) float32 -> (N, vs) float32."""
+    def splat(self, x):
+        """The sequential splat, contributors in (pixel, vertex) order: x (N, vs) float32 -> values (M + 1, vs) float32, row 0
+        the absent neighbour (zeros), row id + 1 the lattice point id."""
         x = np.ascontiguousarray(x, dtype=F32)
-        N, d, M, vs = self.N, self.d, self.M, x.shape[1]
-        values = np.zeros((M + 1, vs), F32)                  # row 0: the absent neighbour
+        values = np.zeros((self.M + 1, x.shape[1]), F32)
         o = (self.offset + 1).reshape(-1)
-        np.add.at(values, o, self.bary.reshape(-1, 1) * np.repeat(x, d + 1, axis=0))
-        for j in range(d + 1):
+        np.add.at(values, o, self.bary.reshape(-1, 1) * np.repeat(x, self.d + 1, axis=0))
+        return values
+
+    def blur(self, values, axes=None):
+        """The axis blurs `old + 0.5 * (n1 + n2)` through double along `axes` in turn (default 0 .. d: lattice_compute's order;
+        d .. 0 is its reverse = true); values as splat() leaves them."""
+        for j in range(self.d + 1) if axes is None else axes:
             t = values[self.n1[j] + 1] + values[self.n2[j] + 1]
             new = np.zeros_like(values)
             new[1:] = (values[1:].astype(np.float64) + 0.5 * t.astype(np.float64)).astype(F32)
             values = new
+        return values
+
+    def slice(self, values):
+        """values (M + 1, vs) -> (N, vs): sum over the vertices, in order, of (bary * value) * alpha."""
+        d = self.d
         alpha = F32(1.0) / (F32(1.0) + F32(2.0 ** -d))
-        out = np.zeros((N, vs), F32)
+        out = np.zeros((self.N, values.shape[1]), F32)
         for j in range(d + 1):
             out = out + self.bary[:, j, None] * values[self.offset[:, j] + 1] * alpha
         return out
+
+    def compute(self, x):
+        """lattice_compute: x (N, vs) float32 -> (N, vs) float32."""
+        return self.slice(self.blur(self.splat(x)))
 
     def norm(self):
         ones = self.compute(np.ones((self.N, 1), F32))
