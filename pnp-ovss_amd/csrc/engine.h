@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <map>
 #include <memory>
+#include <set>
 #include <string>
 #include <utility>
 #include <vector>
@@ -18,11 +19,6 @@
 #include "kernels.h"
 
 namespace pnp {
-
-struct Buf {
-    void* p = nullptr;
-    size_t bytes = 0;
-};
 
 // A GEMM weight [rows, cols] in the engine's compute mode.  bf16x3 keeps the wide Linears' weights as a (hi | lo) bf16 pair in the
 // bytes of the fp32 copy: the hi array, then the lo array.  Only this type and new_weight / fill_weight know it.
@@ -66,18 +62,50 @@ struct TextLayerA {
 };
 
 struct VitLayerW {
-    float *n1w, *n1b, *n2w, *n2b, *qkv_b, *proj_b, *fc1_b, *fc2_b;
+    float *n1w = nullptr, *n1b = nullptr, *n2w = nullptr, *n2b = nullptr, *qkv_b = nullptr, *proj_b = nullptr, *fc1_b = nullptr,
+          *fc2_b = nullptr;
     Weight qkv_w, proj_w, fc1_w, fc2_w;
 };
 
-// Device allocations that hold WEIGHTS (converted GEMM weights, biases, LayerNorm parameters, embeddings): read-only once
-// finalized, so several engines of a process may use one copy (pnp_create_shared); freed with the last engine that holds it.
-struct WeightStore {
-    int device = 0;
+// A list of device allocations and what they add up to: the engine's own (activations, workspace) or a Weights'
+struct Allocs {
     std::vector<void*> allocs;
     size_t bytes = 0;
-    ~WeightStore() {
+};
+
+// Everything pnp_load_weight / pnp_finalize_weights produce (converted GEMM weights, biases, LayerNorm parameters, embeddings)
+// and the device memory behind it: read-only once finalized, so several engines of a process may use one copy
+// (pnp_create_shared); freed with the last engine that holds it.
+struct Weights : Allocs {
+    int device = 0;
+    bool finalized = false;
+    // the loader's state, empty once finalized: fp32 device staging of the GEMM weights by tensor name, names that arrived
+    std::map<std::string, float*> staged;
+    std::set<std::string> loaded;
+
+    float *cls = nullptr, *pos = nullptr, *patch_b = nullptr, *vnorm_w = nullptr, *vnorm_b = nullptr;
+    Weight patch_w;
+    std::vector<VitLayerW> vit;
+    float *word = nullptr, *tpos = nullptr, *eln_w = nullptr, *eln_b = nullptr, *itm_w = nullptr, *itm_b = nullptr;
+    std::vector<TextLayerW> txt;
+    // optional ITC projections, [0] vision_proj (D -> E), [1] text_proj (H -> E) (B/blip_image_text_matching.py:54-55): present when
+    // the state dict carried weight and bias; E is read from the weight's first dimension
+    Weight proj_w[2];
+    float* proj_b[2] = {nullptr, nullptr};
+    int proj_E[2] = {0, 0};
+    Weight ck_w, cv_w;                         // cross K / V weights of all layers: [TL*H, D]
+    float *ck_b = nullptr, *cv_b = nullptr;    // [TL*H]
+
+    void drop_staging() {
+        for (auto& s : staged) (void)hipFree(s.second);
+        staged.clear();
+        loaded.clear();
+    }
+    Weights() = default;
+    Weights(const Weights&) = delete;
+    ~Weights() {
         (void)hipSetDevice(device);
+        drop_staging();
         for (void* p : allocs) (void)hipFree(p);
     }
 };
@@ -86,34 +114,14 @@ struct WeightStore {
 
 struct pnp_engine {
     pnp_config c{};
-    std::shared_ptr<pnp::WeightStore> wstore;  // owner(s) of every weight allocation below
-    bool to_store = false;                     // dalloc target: the weight store (true) or this engine's own list
-    bool shares_weights = false;               // created by pnp_create_shared: the weights belong to a donor's store
+    std::shared_ptr<pnp::Weights> w;           // never null; with shares_weights, a donor's (pnp_create_shared)
+    bool shares_weights = false;
     int bf = 0;                // 1: bf16 storage / bf16 MFMA everywhere
     int x3 = 0;                // 1: split-bf16 ("bf16x3") ViT Linears + cross K/V projections, everything else as fp32 mode
     size_t esz = 4;
     int P = 0, PP = 0, N = 0, Npad = 0, D = 0, H = 0, I = 0, TL = 0, nh = 0, Nst = 0, SL = 0;
     char err[512] = {0};
-    std::vector<void*> allocs;
-    size_t alloc_bytes = 0;
-    std::map<std::string, pnp::Buf> named;     // raw fp32 device copies of small params + test buffers
-    std::map<std::string, bool> loaded;
-    bool finalized = false;
-
-    // ---- weights
-    float *cls = nullptr, *pos = nullptr, *patch_b = nullptr, *vnorm_w = nullptr, *vnorm_b = nullptr;
-    pnp::Weight patch_w;
-    std::vector<pnp::VitLayerW> vit;
-    float *word = nullptr, *tpos = nullptr, *eln_w = nullptr, *eln_b = nullptr, *itm_w = nullptr, *itm_b = nullptr;
-    std::vector<pnp::TextLayerW> txt;
-    // optional ITC projections, [0] vision_proj (D -> E), [1] text_proj (H -> E) (B/blip_image_text_matching.py:54-55): present when
-    // the state dict carried weight and bias; E is read from the weight's first dimension
-    pnp::Weight proj_w[2];
-    float* proj_b[2] = {nullptr, nullptr};
-    int proj_E[2] = {0, 0};
-    pnp::Weight ck_w, cv_w;                    // cross K / V weights of all layers: [TL*H, D]
-    float *ck_b = nullptr, *cv_b = nullptr;    // [TL*H]
-    std::vector<pnp::Buf> staging;             // fp32 staging of GEMM weights until finalize
+    pnp::Allocs own;           // what this engine alone holds: activations and workspace
 
     // ---- activations
     int ldq = 0;               // row stride (elements) of the fused q|k|v buffer
@@ -202,32 +210,30 @@ inline int fail(pnp_engine* e, int code, const char* fmt, ...) {
         if (_r != PNP_OK) return fail(e, _r, "%s failed (%d): %s", #call, _r, hipGetErrorString(hipGetLastError())); \
     } while (0)
 
+// the one allocation routine: `count` elements of T that `owner` frees (e->own, or *e->w for a weight); errors go to e
 template <typename T>
-inline int dalloc(pnp_engine* e, T** out, size_t count, bool zero = false) {
+inline int dalloc(pnp_engine* e, Allocs& owner, T** out, size_t count, bool zero = false) {
     void* p = nullptr;
     const size_t bytes = (count * sizeof(T) + 255) / 256 * 256;
     if (hipMalloc(&p, bytes ? bytes : 256) != hipSuccess) return fail(e, PNP_ERR_NOMEM, "hipMalloc(%zu) failed", bytes);
+    owner.allocs.push_back(p);
+    owner.bytes += bytes;
     if (zero && hipMemset(p, 0, bytes ? bytes : 256) != hipSuccess) return fail(e, PNP_ERR_HIP, "hipMemset failed");
-    if (e->to_store && e->wstore) {
-        e->wstore->allocs.push_back(p);
-        e->wstore->bytes += bytes;
-    } else {
-        e->allocs.push_back(p);
-    }
-    e->alloc_bytes += bytes;
     *out = reinterpret_cast<T*>(p);
     return PNP_OK;
 }
+template <typename T>
+inline int dalloc(pnp_engine* e, T** out, size_t count, bool zero = false) { return dalloc(e, e->own, out, count, zero); }
 inline int dalloc_t(pnp_engine* e, void** out, size_t count, bool zero = false) {   // `count` elements of the compute type
     char* p = nullptr;
-    int r = dalloc<char>(e, &p, count * e->esz, zero);
+    int r = dalloc(e, &p, count * e->esz, zero);
     *out = p;
     return r;
 }
 // a raw kernel launch: KCHK(e, launched()) right behind it
 inline int launched() { return hipPeekAtLastError() == hipSuccess ? PNP_OK : PNP_ERR_HIP; }   // (KCHK reads and clears the error)
 
-// state-dict names of the optional ITC projections, [0] / [1] as in pnp_engine::proj_w
+// state-dict names of the optional ITC projections, [0] / [1] as in Weights::proj_w
 inline const char* const kProj[2] = {"vision_proj", "text_proj"};
 
 inline GemmArgs G_(const void* A, int lda, const void* B, int ldb, int M, int N, int K) {

@@ -37,7 +37,8 @@ __global__ void transpose_cast_kernel_f32(const float* __restrict__ in, float* _
 
 int new_weight(pnp_engine* e, int rows, int cols, bool pair, Weight* w) {
     *w = Weight{nullptr, rows, cols, pair ? 2 : (int)e->esz, pair};
-    return dalloc_t(e, &w->p, (size_t)rows * cols);      // a pair belongs to bf16x3, whose compute type is fp32
+    // a pair belongs to bf16x3, whose compute type is fp32
+    return dalloc(e, *e->w, reinterpret_cast<char**>(&w->p), (size_t)rows * cols * e->esz);
 }
 // fp32 [n, w.cols] staging -> rows r0 .. r0 + n of the device weight
 int fill_weight(pnp_engine* e, const float* src32, const Weight& w, int r0, int n) {
@@ -62,6 +63,80 @@ int make_weight(pnp_engine* e, const float* src32, int rows, int cols, bool tran
     if (tmp) (void)hipFree(tmp);
     if (r != PNP_OK || st != hipSuccess) return fail(e, PNP_ERR_HIP, "weight conversion failed");
     return PNP_OK;
+}
+
+// One tensor of the reference state dict and where it goes.  The three lists below (top level, ViT block, text layer) are the
+// only place that names the keys and their sizes: pnp_create allocates the fp32 arrays from them, pnp_load_weight resolves a
+// name through them, pnp_finalize_weights walks them to see that everything arrived.
+struct Key {
+    const char* name = "";
+    float** slot = nullptr;    // the fp32 array it is copied into (biases, LN, embeddings); null: a GEMM weight, staged fp32 until finalize
+    size_t total = 0;          // elements of that array: several keys may share one (the fused qkv_b, the layer-major ck_b / cv_b)
+    size_t off = 0;            // this key's first element in it
+    int rows = 1, cols = 0;
+    int id = 0;                // GEMM weight: its index in finalize's array of staged pointers (the enums below)
+};
+Key small(const char* name, float** slot, int count, size_t off = 0, size_t total = 0) {
+    return {name, slot, total ? total : (size_t)count, off, 1, count, 0};
+}
+Key gemm(const char* name, int id, int rows, int cols) { return {name, nullptr, 0, 0, rows, cols, id}; }
+
+enum { W_PATCH };
+enum { W_QKV, W_PROJ, W_FC1, W_FC2 };
+enum { W_Q, W_K, W_V, W_SO, W_CQ, W_CK, W_CV, W_CO, W_I, W_O, W_MAX };
+
+std::vector<Key> top_keys(Weights& w, const pnp_config& c) {
+    const int D = c.vit_dim, H = c.txt_hidden, N = (c.img_size / 16) * (c.img_size / 16) + 1;
+    return {small("visual_encoder.cls_token", &w.cls, D),
+            small("visual_encoder.pos_embed", &w.pos, N * D),
+            gemm("visual_encoder.patch_embed.proj.weight", W_PATCH, D, 768),
+            small("visual_encoder.patch_embed.proj.bias", &w.patch_b, D),
+            small("visual_encoder.norm.weight", &w.vnorm_w, D),
+            small("visual_encoder.norm.bias", &w.vnorm_b, D),
+            small("text_encoder.embeddings.word_embeddings.weight", &w.word, c.vocab * H),
+            small("text_encoder.embeddings.position_embeddings.weight", &w.tpos, c.max_pos * H),
+            small("text_encoder.embeddings.LayerNorm.weight", &w.eln_w, H),
+            small("text_encoder.embeddings.LayerNorm.bias", &w.eln_b, H),
+            small("itm_head.weight", &w.itm_w, 2 * H),
+            small("itm_head.bias", &w.itm_b, 2)};
+}
+const char* const kVitPrefix = "visual_encoder.blocks.";
+std::vector<Key> vit_keys(Weights& w, const pnp_config& c, int li) {
+    VitLayerW& v = w.vit[li];
+    const int D = c.vit_dim, F = D * c.vit_mlp_ratio;
+    return {small("norm1.weight", &v.n1w, D),      small("norm1.bias", &v.n1b, D),
+            gemm("attn.qkv.weight", W_QKV, 3 * D, D),   small("attn.qkv.bias", &v.qkv_b, 3 * D),
+            gemm("attn.proj.weight", W_PROJ, D, D),     small("attn.proj.bias", &v.proj_b, D),
+            small("norm2.weight", &v.n2w, D),      small("norm2.bias", &v.n2b, D),
+            gemm("mlp.fc1.weight", W_FC1, F, D),        small("mlp.fc1.bias", &v.fc1_b, F),
+            gemm("mlp.fc2.weight", W_FC2, D, F),        small("mlp.fc2.bias", &v.fc2_b, D)};
+}
+const char* const kTextPrefix = "text_encoder.encoder.layer.";
+std::vector<Key> text_keys(Weights& w, const pnp_config& c, int li) {
+    TextLayerW& t = w.txt[li];
+    const int D = c.vit_dim, H = c.txt_hidden, I = c.txt_inter;
+    const size_t l = (size_t)li * H, all = (size_t)c.txt_layers * H;   // this layer's part of the layer-major cross K / V biases, of all
+    return {gemm("attention.self.query.weight", W_Q, H, H),            small("attention.self.query.bias", &t.qkv_b, H, 0, 3 * H),
+            gemm("attention.self.key.weight", W_K, H, H),              small("attention.self.key.bias", &t.qkv_b, H, H, 3 * H),
+            gemm("attention.self.value.weight", W_V, H, H),            small("attention.self.value.bias", &t.qkv_b, H, 2 * H, 3 * H),
+            gemm("attention.output.dense.weight", W_SO, H, H),         small("attention.output.dense.bias", &t.so_b, H),
+            small("attention.output.LayerNorm.weight", &t.sln_w, H),   small("attention.output.LayerNorm.bias", &t.sln_b, H),
+            gemm("crossattention.self.query.weight", W_CQ, H, H),      small("crossattention.self.query.bias", &t.cq_b, H),
+            gemm("crossattention.self.key.weight", W_CK, H, D),        small("crossattention.self.key.bias", &w.ck_b, H, l, all),
+            gemm("crossattention.self.value.weight", W_CV, H, D),      small("crossattention.self.value.bias", &w.cv_b, H, l, all),
+            gemm("crossattention.output.dense.weight", W_CO, H, H),    small("crossattention.output.dense.bias", &t.co_b, H),
+            small("crossattention.output.LayerNorm.weight", &t.cln_w, H), small("crossattention.output.LayerNorm.bias", &t.cln_b, H),
+            gemm("intermediate.dense.weight", W_I, I, H),              small("intermediate.dense.bias", &t.i_b, I),
+            gemm("output.dense.weight", W_O, H, I),                    small("output.dense.bias", &t.o_b, H),
+            small("output.LayerNorm.weight", &t.oln_w, H),             small("output.LayerNorm.bias", &t.oln_b, H)};
+}
+
+// pnp_create_shared: everything but the per-engine capacities (batch, text length), the stash layer (it has a rule of its own)
+// and the [ENC] token id has to be the donor's.  pnp_config is int32 / float fields throughout, so it has no padding bytes.
+static_assert(sizeof(pnp_config) == 20 * 4, "pnp_config: 20 four-byte fields");
+bool same_model(pnp_config a, const pnp_config& b) {
+    a.max_batch = b.max_batch; a.max_text_len = b.max_text_len; a.stash_layer = b.stash_layer; a.enc_token_id = b.enc_token_id;
+    return memcmp(&a, &b, sizeof a) == 0;
 }
 
 }  // namespace
@@ -89,8 +164,7 @@ extern "C" void pnp_destroy(pnp_engine* e) {
     if (!e) return;
     (void)hipSetDevice(e->c.device);
     (void)hipDeviceSynchronize();
-    for (void* p : e->allocs) (void)hipFree(p);
-    for (auto& b : e->staging) if (b.p) (void)hipFree(b.p);
+    for (void* p : e->own.allocs) (void)hipFree(p);
     if (e->gemm_prof) {
         for (int i = 0; i < e->gemm_prof->created; i++) {
             (void)hipEventDestroy(e->gemm_prof->ev0[i]);
@@ -109,18 +183,15 @@ static int create_impl(const pnp_config* cfg, pnp_engine* donor, pnp_engine** ou
     pnp_engine* e = new pnp_engine();
     *out = e;
     e->c = *cfg;
+    e->w = std::make_shared<Weights>();        // empty and unfinalized: what an engine refused below is left with
+    e->w->device = cfg->device;
     if (donor) {
-        const pnp_config& d = donor->c;
-        if (!donor->finalized) return fail(e, PNP_ERR_STATE, "pnp_create_shared: the donor's weights are not finalized");
-        if (d.device != cfg->device || d.compute_bf16 != cfg->compute_bf16 || d.img_size != cfg->img_size || d.patch != cfg->patch ||
-            d.vit_dim != cfg->vit_dim || d.vit_depth != cfg->vit_depth || d.vit_heads != cfg->vit_heads ||
-            d.vit_mlp_ratio != cfg->vit_mlp_ratio || d.txt_hidden != cfg->txt_hidden || d.txt_layers != cfg->txt_layers ||
-            d.txt_heads != cfg->txt_heads || d.txt_inter != cfg->txt_inter || d.vocab != cfg->vocab || d.max_pos != cfg->max_pos ||
-            d.vit_ln_eps != cfg->vit_ln_eps || d.txt_ln_eps != cfg->txt_ln_eps)
+        if (!donor->w->finalized) return fail(e, PNP_ERR_STATE, "pnp_create_shared: the donor's weights are not finalized");
+        if (!same_model(donor->c, *cfg))
             return fail(e, PNP_ERR_ARG, "pnp_create_shared: device, compute mode and model geometry must equal the donor's");
-        if (cfg->stash_layer < d.stash_layer)
+        if (cfg->stash_layer < donor->c.stash_layer)
             return fail(e, PNP_ERR_ARG, "pnp_create_shared: stash_layer %d below the donor's %d (its transposed backward weights "
-                        "exist for layers >= %d only)", cfg->stash_layer, d.stash_layer, d.stash_layer);
+                        "exist for layers >= %d only)", cfg->stash_layer, donor->c.stash_layer, donor->c.stash_layer);
     }
     const pnp_config& c = e->c;
     if (c.compute_bf16 < 0 || c.compute_bf16 > 2) return fail(e, PNP_ERR_ARG, "compute_bf16 must be 0 (fp32), 1 (bf16) or 2 (split-bf16)");
@@ -154,13 +225,11 @@ static int create_impl(const pnp_config* cfg, pnp_engine* donor, pnp_engine** ou
     if ((e->N + 15) / 16 > 160) return fail(e, PNP_ERR_ARG, "too many image tokens (%d) for the cross-attention kernel", e->N);
     const size_t B = c.max_batch, M = B * e->N, D = e->D, H = e->H, I = e->I, L = c.max_text_len, R = B * L, TL = e->TL;
     const size_t ldv = B * e->Npad;
-    e->vit.resize(c.vit_depth);
-    e->txt.resize(TL);
     e->ta.resize(TL);
     if (e->x3) {                               // one 256 KB partial-tile slot + one flag per CU (64 MB): not shared between engines
         const int n_cu = device_cu_count();
         if (!n_cu || streamk_ws_create(&e->sk_ws, n_cu) != PNP_OK) return fail(e, PNP_ERR_HIP, "stream-K workspace allocation failed");
-        e->alloc_bytes += (size_t)n_cu * 256 * 256 * 4;
+        e->own.bytes += (size_t)n_cu * 256 * 256 * 4;
     }
     // activations
     KCHK(e, dalloc_t(e, &e->patches, B * e->PP * 768));
@@ -232,46 +301,23 @@ static int create_impl(const pnp_config* cfg, pnp_engine* donor, pnp_engine** ou
     KCHK(e, dalloc(e, &e->logits_scratch, B * 2));
     if (donor) {
         // weights: the donor's device copies (read-only after finalize); this engine owns activations and workspace only
-        e->wstore = donor->wstore;
+        e->w = donor->w;
         e->shares_weights = true;
-        e->cls = donor->cls; e->pos = donor->pos; e->patch_b = donor->patch_b; e->vnorm_w = donor->vnorm_w; e->vnorm_b = donor->vnorm_b;
-        e->word = donor->word; e->tpos = donor->tpos; e->eln_w = donor->eln_w; e->eln_b = donor->eln_b;
-        e->itm_w = donor->itm_w; e->itm_b = donor->itm_b; e->ck_b = donor->ck_b; e->cv_b = donor->cv_b;
-        e->patch_w = donor->patch_w; e->ck_w = donor->ck_w; e->cv_w = donor->cv_w;
-        e->vit = donor->vit;
-        e->txt = donor->txt;
-        for (int i = 0; i < 2; i++) { e->proj_w[i] = donor->proj_w[i]; e->proj_b[i] = donor->proj_b[i]; e->proj_E[i] = donor->proj_E[i]; }
-        e->finalized = true;
         return PNP_OK;
     }
-    e->wstore = std::make_shared<WeightStore>();
-    e->wstore->device = c.device;
-    e->to_store = true;
-    // small fp32 params
-    KCHK(e, dalloc(e, &e->cls, D));
-    KCHK(e, dalloc(e, &e->pos, (size_t)e->N * D));
-    KCHK(e, dalloc(e, &e->patch_b, D));
-    KCHK(e, dalloc(e, &e->vnorm_w, D));
-    KCHK(e, dalloc(e, &e->vnorm_b, D));
-    KCHK(e, dalloc(e, &e->word, (size_t)c.vocab * H));
-    KCHK(e, dalloc(e, &e->tpos, (size_t)c.max_pos * H));
-    KCHK(e, dalloc(e, &e->eln_w, H));
-    KCHK(e, dalloc(e, &e->eln_b, H));
-    KCHK(e, dalloc(e, &e->itm_w, 2 * H));
-    KCHK(e, dalloc(e, &e->itm_b, 2));
-    KCHK(e, dalloc(e, &e->ck_b, TL * H));
-    KCHK(e, dalloc(e, &e->cv_b, TL * H));
-    for (auto& v : e->vit) {
-        KCHK(e, dalloc(e, &v.n1w, D)); KCHK(e, dalloc(e, &v.n1b, D)); KCHK(e, dalloc(e, &v.n2w, D)); KCHK(e, dalloc(e, &v.n2b, D));
-        KCHK(e, dalloc(e, &v.qkv_b, 3 * D)); KCHK(e, dalloc(e, &v.proj_b, D));
-        KCHK(e, dalloc(e, &v.fc1_b, D * c.vit_mlp_ratio)); KCHK(e, dalloc(e, &v.fc2_b, D));
-    }
-    for (auto& t : e->txt) {
-        KCHK(e, dalloc(e, &t.qkv_b, 3 * H)); KCHK(e, dalloc(e, &t.so_b, H)); KCHK(e, dalloc(e, &t.sln_w, H)); KCHK(e, dalloc(e, &t.sln_b, H));
-        KCHK(e, dalloc(e, &t.cq_b, H)); KCHK(e, dalloc(e, &t.co_b, H)); KCHK(e, dalloc(e, &t.cln_w, H)); KCHK(e, dalloc(e, &t.cln_b, H));
-        KCHK(e, dalloc(e, &t.i_b, I)); KCHK(e, dalloc(e, &t.o_b, H)); KCHK(e, dalloc(e, &t.oln_w, H)); KCHK(e, dalloc(e, &t.oln_b, H));
-    }
-    e->to_store = false;
+    // the fp32 arrays the loader copies into (biases, LayerNorm, embeddings): one allocation per distinct array of the key lists
+    e->w->vit.resize(c.vit_depth);
+    e->w->txt.resize(TL);
+    auto alloc_small = [e](const std::vector<Key>& keys) {
+        for (const Key& k : keys)
+            if (k.slot && !*k.slot) KCHK(e, dalloc(e, *e->w, k.slot, k.total));
+        return (int)PNP_OK;
+    };
+    if (int r = alloc_small(top_keys(*e->w, c))) return r;
+    for (int i = 0; i < c.vit_depth; i++)
+        if (int r = alloc_small(vit_keys(*e->w, c, i))) return r;
+    for (int i = 0; i < c.txt_layers; i++)
+        if (int r = alloc_small(text_keys(*e->w, c, i))) return r;
     return PNP_OK;
 }
 extern "C" int pnp_create(const pnp_config* cfg, pnp_engine** out) { return create_impl(cfg, nullptr, out); }
@@ -283,69 +329,6 @@ extern "C" int pnp_create_shared(const pnp_config* cfg, pnp_engine* donor, pnp_e
 // =========================================================================================== weights
 
 namespace {
-
-// One tensor of the reference state dict and where it goes.  The three lists below (top level, ViT block, text layer) are the
-// only place that names the keys: pnp_load_weight resolves a name through them, pnp_finalize_weights walks them to see that
-// everything arrived.
-struct Key {
-    const char* name = "";
-    float* small = nullptr;    // direct fp32 destination (biases, LN, embeddings); null: a GEMM weight, staged fp32 until finalize
-    size_t small_off = 0;      // element offset inside `small`
-    int rows = 1, cols = 0;
-    int id = 0;                // GEMM weight: its index in finalize's array of staged pointers (the enums below)
-};
-Key small(const char* name, float* p, int count, size_t off = 0) { return {name, p, off, 1, count, 0}; }
-Key gemm(const char* name, int id, int rows, int cols) { return {name, nullptr, 0, rows, cols, id}; }
-
-enum { W_PATCH };
-enum { W_QKV, W_PROJ, W_FC1, W_FC2 };
-enum { W_Q, W_K, W_V, W_SO, W_CQ, W_CK, W_CV, W_CO, W_I, W_O, W_MAX };
-
-std::vector<Key> top_keys(pnp_engine* e) {
-    const int D = e->D, H = e->H;
-    return {small("visual_encoder.cls_token", e->cls, D),
-            small("visual_encoder.pos_embed", e->pos, e->N * D),
-            gemm("visual_encoder.patch_embed.proj.weight", W_PATCH, D, 768),
-            small("visual_encoder.patch_embed.proj.bias", e->patch_b, D),
-            small("visual_encoder.norm.weight", e->vnorm_w, D),
-            small("visual_encoder.norm.bias", e->vnorm_b, D),
-            small("text_encoder.embeddings.word_embeddings.weight", e->word, e->c.vocab * H),
-            small("text_encoder.embeddings.position_embeddings.weight", e->tpos, e->c.max_pos * H),
-            small("text_encoder.embeddings.LayerNorm.weight", e->eln_w, H),
-            small("text_encoder.embeddings.LayerNorm.bias", e->eln_b, H),
-            small("itm_head.weight", e->itm_w, 2 * H),
-            small("itm_head.bias", e->itm_b, 2)};
-}
-const char* const kVitPrefix = "visual_encoder.blocks.";
-std::vector<Key> vit_keys(pnp_engine* e, int li) {
-    VitLayerW& v = e->vit[li];
-    const int D = e->D, F = D * e->c.vit_mlp_ratio;
-    return {small("norm1.weight", v.n1w, D),       small("norm1.bias", v.n1b, D),
-            gemm("attn.qkv.weight", W_QKV, 3 * D, D),   small("attn.qkv.bias", v.qkv_b, 3 * D),
-            gemm("attn.proj.weight", W_PROJ, D, D),     small("attn.proj.bias", v.proj_b, D),
-            small("norm2.weight", v.n2w, D),       small("norm2.bias", v.n2b, D),
-            gemm("mlp.fc1.weight", W_FC1, F, D),        small("mlp.fc1.bias", v.fc1_b, F),
-            gemm("mlp.fc2.weight", W_FC2, D, F),        small("mlp.fc2.bias", v.fc2_b, D)};
-}
-const char* const kTextPrefix = "text_encoder.encoder.layer.";
-std::vector<Key> text_keys(pnp_engine* e, int li) {
-    TextLayerW& t = e->txt[li];
-    const int D = e->D, H = e->H, I = e->I;
-    const size_t l = (size_t)li * H;               // this layer's part of the layer-major cross K / V biases
-    return {gemm("attention.self.query.weight", W_Q, H, H),            small("attention.self.query.bias", t.qkv_b, H, 0),
-            gemm("attention.self.key.weight", W_K, H, H),              small("attention.self.key.bias", t.qkv_b, H, H),
-            gemm("attention.self.value.weight", W_V, H, H),            small("attention.self.value.bias", t.qkv_b, H, 2 * H),
-            gemm("attention.output.dense.weight", W_SO, H, H),         small("attention.output.dense.bias", t.so_b, H),
-            small("attention.output.LayerNorm.weight", t.sln_w, H),    small("attention.output.LayerNorm.bias", t.sln_b, H),
-            gemm("crossattention.self.query.weight", W_CQ, H, H),      small("crossattention.self.query.bias", t.cq_b, H),
-            gemm("crossattention.self.key.weight", W_CK, H, D),        small("crossattention.self.key.bias", e->ck_b, H, l),
-            gemm("crossattention.self.value.weight", W_CV, H, D),      small("crossattention.self.value.bias", e->cv_b, H, l),
-            gemm("crossattention.output.dense.weight", W_CO, H, H),    small("crossattention.output.dense.bias", t.co_b, H),
-            small("crossattention.output.LayerNorm.weight", t.cln_w, H), small("crossattention.output.LayerNorm.bias", t.cln_b, H),
-            gemm("intermediate.dense.weight", W_I, I, H),              small("intermediate.dense.bias", t.i_b, I),
-            gemm("output.dense.weight", W_O, H, I),                    small("output.dense.bias", t.o_b, H),
-            small("output.LayerNorm.weight", t.oln_w, H),              small("output.LayerNorm.bias", t.oln_b, H)};
-}
 
 bool find_key(const std::vector<Key>& keys, const char* name, Key& out) {
     for (const Key& k : keys)
@@ -364,9 +347,9 @@ bool resolve(pnp_engine* e, const std::string& n, Key& s) {
         const size_t len = strlen(prefix);
         return n.compare(0, len, prefix) == 0 && sscanf(n.c_str() + len, "%d.%127s", &li, rest) == 2 && li >= 0 && li < depth;
     };
-    if (layer_of(kVitPrefix, e->c.vit_depth)) return find_key(vit_keys(e, li), rest, s);
-    if (layer_of(kTextPrefix, e->TL)) return find_key(text_keys(e, li), rest, s);
-    return find_key(top_keys(e), n.c_str(), s);
+    if (layer_of(kVitPrefix, e->c.vit_depth)) return find_key(vit_keys(*e->w, e->c, li), rest, s);
+    if (layer_of(kTextPrefix, e->TL)) return find_key(text_keys(*e->w, e->c, li), rest, s);
+    return find_key(top_keys(*e->w, e->c), n.c_str(), s);
 }
 
 // the optional ITC projections: 1 = `name` is one of the four tensors (staged like a GEMM weight until finalize), 0 = it is
@@ -384,24 +367,25 @@ int resolve_proj(pnp_engine* e, const std::string& n, const int64_t* shape, int 
         return fail(e, PNP_ERR_ARG, "%s: expected %s, second dimension %d", n.c_str(), bias ? "a vector" : "a matrix", K);
     const int64_t E = shape[0];
     if (E <= 0 || E > 1024 || E % 64) return fail(e, PNP_ERR_ARG, "%s: embedding width %lld must be a multiple of 64 up to 1024", n.c_str(), (long long)E);
-    if (e->proj_E[which] && e->proj_E[which] != (int)E)
-        return fail(e, PNP_ERR_ARG, "%s: %lld rows, but the other tensor of this projection has %d", n.c_str(), (long long)E, e->proj_E[which]);
-    e->proj_E[which] = (int)E;
+    int& have = e->w->proj_E[which];
+    if (have && have != (int)E)
+        return fail(e, PNP_ERR_ARG, "%s: %lld rows, but the other tensor of this projection has %d", n.c_str(), (long long)E, have);
+    have = (int)E;
     s.rows = (int)E;
     s.cols = bias ? 1 : K;
     return 1;
 }
 
-const float* staged(pnp_engine* e, const std::string& n) {
-    auto it = e->named.find("stage:" + n);
-    return it == e->named.end() ? nullptr : (const float*)it->second.p;
+const float* staged(const Weights& w, const std::string& n) {   // null until a copy into the buffer has succeeded
+    auto it = w.staged.find(n);
+    return it == w.staged.end() || !w.loaded.count(n) ? nullptr : it->second;
 }
 
 // every tensor of a family must have arrived; st[id] <- the fp32 staging of its GEMM weights
 int collect(pnp_engine* e, const std::string& prefix, const std::vector<Key>& keys, const float** st) {
     for (const Key& k : keys) {
         const std::string n = prefix + k.name;
-        if (k.small ? !e->loaded.count(n) : !(st[k.id] = staged(e, n))) return fail(e, PNP_ERR_STATE, "missing weight %s", n.c_str());
+        if (k.slot ? !e->w->loaded.count(n) : !(st[k.id] = staged(*e->w, n))) return fail(e, PNP_ERR_STATE, "missing weight %s", n.c_str());
     }
     return PNP_OK;
 }
@@ -412,7 +396,8 @@ extern "C" int pnp_load_weight(pnp_engine* e, const char* name, const float* dat
                                int32_t on_device) {
     if (!e || !name || !data || !shape) return PNP_ERR_ARG;
     if (e->shares_weights) return fail(e, PNP_ERR_STATE, "this engine uses a donor's weights (pnp_create_shared)");
-    if (e->finalized) return fail(e, PNP_ERR_STATE, "weights already finalized");
+    Weights& w = *e->w;
+    if (w.finalized) return fail(e, PNP_ERR_STATE, "weights already finalized");
     HIPCHK(e, hipSetDevice(e->c.device));
     Key s;
     const int pj = resolve_proj(e, name, shape, ndim, s);
@@ -422,44 +407,40 @@ extern "C" int pnp_load_weight(pnp_engine* e, const char* name, const float* dat
     for (int i = 0; i < ndim; i++) count *= (size_t)shape[i];
     if (count != (size_t)s.rows * s.cols) return fail(e, PNP_ERR_ARG, "%s: expected %d elements, got %zu", name, s.rows * s.cols, count);
     const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    if (s.small) {
-        HIPCHK(e, hipMemcpy(s.small + s.small_off, data, count * 4, kind));
-    } else {
-        Buf b;
-        b.bytes = count * 4;
-        HIPCHK(e, hipMalloc(&b.p, b.bytes));
-        HIPCHK(e, hipMemcpy(b.p, data, b.bytes, kind));
-        e->staging.push_back(b);
-        e->named[std::string("stage:") + name] = b;
+    float* dst = s.slot ? *s.slot + s.off : nullptr;
+    if (!s.slot) {                             // staged in a buffer that w owns from its allocation on; a second load of the name
+        float*& b = w.staged[name];            // has the same count (the key's, or the projection's E) and overwrites it
+        if (!b) HIPCHK(e, hipMalloc((void**)&b, count * 4));
+        dst = b;
     }
-    e->loaded[name] = true;
+    HIPCHK(e, hipMemcpy(dst, data, count * 4, kind));
+    w.loaded.insert(name);
     return PNP_OK;
 }
 
 extern "C" int pnp_finalize_weights(pnp_engine* e) {
     if (!e) return PNP_ERR_ARG;
-    if (e->finalized) return PNP_OK;
+    Weights& w = *e->w;
+    if (w.finalized) return PNP_OK;
     HIPCHK(e, hipSetDevice(e->c.device));
-    e->to_store = true;                        // everything allocated from here to the end of the call is a weight
-    struct StoreOff { pnp_engine* e; ~StoreOff() { e->to_store = false; } } store_off{e};
     const int D = e->D, H = e->H, I = e->I, TL = e->TL, F = D * e->c.vit_mlp_ratio;
     const float* st[W_MAX];
-    if (int r = collect(e, "", top_keys(e), st)) return r;
-    KCHK(e, make_weight(e, st[W_PATCH], D, 768, false, &e->patch_w));
+    if (int r = collect(e, "", top_keys(w, e->c), st)) return r;
+    KCHK(e, make_weight(e, st[W_PATCH], D, 768, false, &w.patch_w));
     for (int i = 0; i < e->c.vit_depth; i++) {
-        VitLayerW& v = e->vit[i];
-        if (int r = collect(e, kVitPrefix + std::to_string(i) + ".", vit_keys(e, i), st)) return r;
+        VitLayerW& v = w.vit[i];
+        if (int r = collect(e, kVitPrefix + std::to_string(i) + ".", vit_keys(w, e->c, i), st)) return r;
         KCHK(e, make_weight(e, st[W_QKV], 3 * D, D, false, &v.qkv_w, e->x3));
         KCHK(e, make_weight(e, st[W_PROJ], D, D, false, &v.proj_w, e->x3));
         KCHK(e, make_weight(e, st[W_FC1], F, D, false, &v.fc1_w, e->x3));
         KCHK(e, make_weight(e, st[W_FC2], D, F, false, &v.fc2_w, e->x3));
     }
     // cross-attention K / V weights of all layers, layer-major, so one GEMM projects every layer
-    KCHK(e, new_weight(e, TL * H, D, e->x3, &e->ck_w));
-    KCHK(e, new_weight(e, TL * H, D, e->x3, &e->cv_w));
+    KCHK(e, new_weight(e, TL * H, D, e->x3, &w.ck_w));
+    KCHK(e, new_weight(e, TL * H, D, e->x3, &w.cv_w));
     for (int i = 0; i < TL; i++) {
-        TextLayerW& t = e->txt[i];
-        if (int r = collect(e, kTextPrefix + std::to_string(i) + ".", text_keys(e, i), st)) return r;
+        TextLayerW& t = w.txt[i];
+        if (int r = collect(e, kTextPrefix + std::to_string(i) + ".", text_keys(w, e->c, i), st)) return r;
         // fused self q|k|v [3H, H]
         float* fused = nullptr;
         HIPCHK(e, hipMalloc((void**)&fused, (size_t)3 * H * H * 4));
@@ -475,8 +456,8 @@ extern "C" int pnp_finalize_weights(pnp_engine* e) {
         KCHK(e, make_weight(e, st[W_CO], H, H, false, &t.co_w, e->x3));
         KCHK(e, make_weight(e, st[W_I], I, H, false, &t.i_w, e->x3));
         KCHK(e, make_weight(e, st[W_O], H, I, false, &t.o_w, e->x3));
-        KCHK(e, fill_weight(e, st[W_CK], e->ck_w, i * H, H));
-        KCHK(e, fill_weight(e, st[W_CV], e->cv_w, i * H, H));
+        KCHK(e, fill_weight(e, st[W_CK], w.ck_w, i * H, H));
+        KCHK(e, fill_weight(e, st[W_CV], w.cv_w, i * H, H));
         if (i >= e->SL) {
             KCHK(e, make_weight(e, st[W_O], H, I, true, &t.o_wT, e->x3));      // [I][H]
             KCHK(e, make_weight(e, st[W_I], I, H, true, &t.i_wT, e->x3));      // [H][I]
@@ -489,23 +470,18 @@ extern "C" int pnp_finalize_weights(pnp_engine* e) {
     }
     // the optional ITC projections: converted like every other Linear weight when weight and bias both arrived
     for (int i = 0; i < 2; i++) {
-        const float *w = staged(e, std::string(kProj[i]) + ".weight"), *bs = staged(e, std::string(kProj[i]) + ".bias");
-        if (!w || !bs) {
-            e->proj_E[i] = 0;
+        const float *pw = staged(w, std::string(kProj[i]) + ".weight"), *bs = staged(w, std::string(kProj[i]) + ".bias");
+        if (!pw || !bs) {
+            w.proj_E[i] = 0;
             continue;
         }
-        KCHK(e, make_weight(e, w, e->proj_E[i], i == 0 ? D : H, false, &e->proj_w[i], e->x3));
-        KCHK(e, dalloc(e, &e->proj_b[i], (size_t)e->proj_E[i]));
-        HIPCHK(e, hipMemcpy(e->proj_b[i], bs, (size_t)e->proj_E[i] * 4, hipMemcpyDeviceToDevice));
+        KCHK(e, make_weight(e, pw, w.proj_E[i], i == 0 ? D : H, false, &w.proj_w[i], e->x3));
+        KCHK(e, dalloc(e, w, &w.proj_b[i], (size_t)w.proj_E[i]));
+        HIPCHK(e, hipMemcpy(w.proj_b[i], bs, (size_t)w.proj_E[i] * 4, hipMemcpyDeviceToDevice));
     }
     HIPCHK(e, hipDeviceSynchronize());
-    for (auto& b : e->staging) if (b.p) (void)hipFree(b.p);
-    e->staging.clear();
-    for (auto it = e->named.begin(); it != e->named.end();) {
-        if (it->first.rfind("stage:", 0) == 0) it = e->named.erase(it);
-        else ++it;
-    }
-    e->finalized = true;
+    w.drop_staging();
+    w.finalized = true;
     return PNP_OK;
 }
 
@@ -533,7 +509,8 @@ extern "C" int pnp_get_buffer(pnp_engine* e, const char* name, void** d_ptr, siz
     return fail(e, PNP_ERR_ARG, "unknown buffer %s", name);
 }
 
-extern "C" size_t pnp_allocated_bytes(const pnp_engine* e) { return e ? e->alloc_bytes : 0; }
+// (a sharing engine holds no weight bytes of its own: they are counted once, by the engine that loaded them)
+extern "C" size_t pnp_allocated_bytes(const pnp_engine* e) { return e ? e->own.bytes + (e->shares_weights ? 0 : e->w->bytes) : 0; }
 
 extern "C" int pnp_profile_enable(pnp_engine* e, int32_t on) {
     if (!e) return PNP_ERR_ARG;

@@ -75,21 +75,21 @@ enum class Embed { fresh, keep, reuse };
 
 static int vit_forward_impl(pnp_engine* e, const float* d_images, const uint8_t* d_dropped, int32_t B, void* stream, Embed embed) {
     if (!e || !d_images) return PNP_ERR_ARG;
-    if (!e->finalized) return fail(e, PNP_ERR_STATE, "weights not finalized");
+    if (!e->w->finalized) return fail(e, PNP_ERR_STATE, "weights not finalized");
     if (B <= 0 || B > e->c.max_batch) return fail(e, PNP_ERR_ARG, "batch %d out of range (max %d)", B, e->c.max_batch);
     hipStream_t s = (hipStream_t)stream;
     const int D = e->D, N = e->N, M = B * N, F = D * e->c.vit_mlp_ratio, bf = e->bf;
     const int ldv = e->c.max_batch * e->Npad;
     if (embed == Embed::reuse && d_dropped) {
-        hipLaunchKernelGGL(embed_reuse_kernel, dim3(2048), dim3(256), 0, s, (const float*)e->x0, d_dropped, (const float*)e->patch_b,
-                           (const float*)e->pos, e->x, M, N, D / 4);
+        hipLaunchKernelGGL(embed_reuse_kernel, dim3(2048), dim3(256), 0, s, (const float*)e->x0, d_dropped, (const float*)e->w->patch_b,
+                           (const float*)e->w->pos, e->x, M, N, D / 4);
         KCHK(e, launched());
     } else {
         KCHK(e, patchify(bf, d_images, d_dropped, e->patches, B, e->c.img_size, e->P, s));
-        KCHK(e, cls_rows(e->cls, e->pos, e->x, B, N, D, s));
+        KCHK(e, cls_rows(e->w->cls, e->w->pos, e->x, B, N, D, s));
         {
-            GemmArgs g = linear(e->patches, 768, e->patch_w, B * e->PP);
-            g.bias = e->patch_b; g.resid = e->pos; g.ldr = D; g.out_f32 = e->x; g.ldo = D; g.row_div = e->PP;
+            GemmArgs g = linear(e->patches, 768, e->w->patch_w, B * e->PP);
+            g.bias = e->w->patch_b; g.resid = e->w->pos; g.ldr = D; g.out_f32 = e->x; g.ldo = D; g.row_div = e->PP;
             KCHK(e, egemm(e, g, s));
         }
         if (embed == Embed::keep)
@@ -101,7 +101,7 @@ static int vit_forward_impl(pnp_engine* e, const float* d_images, const uint8_t*
     // operand already split (the handles' lo halves, null in the other modes)
     const int ln = bf | e->x3;                   // LayerNorm writes bf16 for the pair too
     for (int l = 0; l < e->c.vit_depth; l++) {
-        const VitLayerW& w = e->vit[l];
+        const VitLayerW& w = e->w->vit[l];
         KCHK(e, layernorm(ln, e->x, w.n1w, w.n1b, e->c.vit_ln_eps, M, D, nullptr, e->xn.hi, nullptr, nullptr, s, e->xn.lo));
         if (bf || e->x3) {   // q | k | v natural in one launch: [M, 3D] at the padded stride; the attention kernel transposes V on its LDS reads
             GemmArgs g = linear(e->xn, D, w.qkv_w, M);
@@ -142,7 +142,7 @@ static int vit_forward_impl(pnp_engine* e, const float* d_images, const uint8_t*
             KCHK(e, egemm(e, g, s));
         }
     }
-    KCHK(e, layernorm(ln, e->x, e->vnorm_w, e->vnorm_b, e->c.vit_ln_eps, M, D, e->emb32, e->embT.hi, nullptr, nullptr, s, e->embT.lo));
+    KCHK(e, layernorm(ln, e->x, e->w->vnorm_w, e->w->vnorm_b, e->c.vit_ln_eps, M, D, e->emb32, e->embT.hi, nullptr, nullptr, s, e->embT.lo));
     return pnp_cross_kv(e, B, stream);
 }
 extern "C" int pnp_vit_forward(pnp_engine* e, const float* d_images, const uint8_t* d_dropped, int32_t B, void* stream) {
@@ -154,7 +154,7 @@ extern "C" int pnp_vit_forward(pnp_engine* e, const float* d_images, const uint8
 // launches (natural + transposed layouts) right after the ViT, from the compute-type copy of image_embeds.
 extern "C" int pnp_cross_kv(pnp_engine* e, int32_t B, void* stream) {
     if (!e) return PNP_ERR_ARG;
-    if (!e->finalized) return fail(e, PNP_ERR_STATE, "weights not finalized");
+    if (!e->w->finalized) return fail(e, PNP_ERR_STATE, "weights not finalized");
     if (B <= 0 || B > e->c.max_batch) return fail(e, PNP_ERR_ARG, "batch %d out of range (max %d)", B, e->c.max_batch);
     hipStream_t s = (hipStream_t)stream;
     const int D = e->D, N = e->N, M = B * N;
@@ -166,13 +166,13 @@ extern "C" int pnp_cross_kv(pnp_engine* e, int32_t B, void* stream) {
         else { g.out_t = p; g.ldo_t = ld; }
     };
     {
-        GemmArgs g = linear(e->embT, D, e->ck_w, M);
-        g.bias = e->ck_b; out(g, e->Knat, TL * H);
+        GemmArgs g = linear(e->embT, D, e->w->ck_w, M);
+        g.bias = e->w->ck_b; out(g, e->Knat, TL * H);
         KCHK(e, egemm(e, g, s));
     }
     {
-        GemmArgs g = linear_t(e->embT, D, e->cv_w, M);
-        g.bias = e->cv_b; g.bias_on_rows = 1; out(g, e->Vt, ldv); g.col_div = N; g.col_pad = e->Npad;
+        GemmArgs g = linear_t(e->embT, D, e->w->cv_w, M);
+        g.bias = e->w->cv_b; g.bias_on_rows = 1; out(g, e->Vt, ldv); g.col_div = N; g.col_pad = e->Npad;
         KCHK(e, egemm(e, g, s));
     }
     // V token-major of layers >= SL, K^T of layers > SL
@@ -188,13 +188,13 @@ extern "C" int pnp_cross_kv(pnp_engine* e, int32_t B, void* stream) {
         return PNP_OK;
     }
     {
-        GemmArgs g = linear(e->embT, D, e->cv_w, M, SL * H, nVn * H);
-        g.bias = e->cv_b + (size_t)SL * H; g.out_t = e->Vnat; g.ldo_t = nVn * H;
+        GemmArgs g = linear(e->embT, D, e->w->cv_w, M, SL * H, nVn * H);
+        g.bias = e->w->cv_b + (size_t)SL * H; g.out_t = e->Vnat; g.ldo_t = nVn * H;
         KCHK(e, egemm(e, g, s));
     }
     if (nKt > 0) {
-        GemmArgs g = linear_t(e->embT, D, e->ck_w, M, (SL + 1) * H, nKt * H);
-        g.bias = e->ck_b + (size_t)(SL + 1) * H; g.bias_on_rows = 1; g.out_t = e->Kt; g.ldo_t = ldv; g.col_div = N; g.col_pad = e->Npad;
+        GemmArgs g = linear_t(e->embT, D, e->w->ck_w, M, (SL + 1) * H, nKt * H);
+        g.bias = e->w->ck_b + (size_t)(SL + 1) * H; g.bias_on_rows = 1; g.out_t = e->Kt; g.ldo_t = ldv; g.col_div = N; g.col_pad = e->Npad;
         KCHK(e, egemm(e, g, s));
     }
     return PNP_OK;
@@ -208,7 +208,7 @@ static int text_layer(pnp_engine* e, int i, const int64_t* d_mask, int32_t ld, i
                       hipStream_t s) {
     const int H = e->H, I = e->I, TL = e->TL, R = B * L, bf = e->bf, N = e->N;
     const int ldv = e->c.max_batch * e->Npad;
-    const TextLayerW& w = e->txt[i];
+    const TextLayerW& w = e->w->txt[i];
     TextLayerA& a = e->ta[i];
     const float* h = i ? e->ta[i - 1].h_out : e->h0;
     const void* hT = i ? e->ta[i - 1].h_outT : e->h0T;
@@ -268,21 +268,21 @@ static int text_layer(pnp_engine* e, int i, const int64_t* d_mask, int32_t ld, i
 static int text_forward_impl(pnp_engine* e, const int64_t* d_ids, const int64_t* d_mask, int32_t ld, int32_t B, int32_t L,
                              float* d_logits, void* stream, bool reuse_prefix) {
     if (!e || !d_ids || !d_mask) return PNP_ERR_ARG;
-    if (!e->finalized) return fail(e, PNP_ERR_STATE, "weights not finalized");
+    if (!e->w->finalized) return fail(e, PNP_ERR_STATE, "weights not finalized");
     if (B <= 0 || B > e->c.max_batch || L < 5 || L > e->c.max_text_len || ld < L)
         return fail(e, PNP_ERR_ARG, "text batch %d x %d (ld %d) out of range (max %d x %d)", B, L, ld, e->c.max_batch, e->c.max_text_len);
     hipStream_t s = (hipStream_t)stream;
     const int H = e->H, TL = e->TL, R = B * L;
     e->acts_text_only = false;
     if (!reuse_prefix) {
-        KCHK(e, text_embed(d_ids, ld, e->word, e->tpos, e->temb, B, L, H, e->c.enc_token_id, e->c.vocab, s));
-        KCHK(e, layernorm(e->bf, e->temb, e->eln_w, e->eln_b, e->c.txt_ln_eps, R, H, e->h0, e->h0T, nullptr, nullptr, s));
+        KCHK(e, text_embed(d_ids, ld, e->w->word, e->w->tpos, e->temb, B, L, H, e->c.enc_token_id, e->c.vocab, s));
+        KCHK(e, layernorm(e->bf, e->temb, e->w->eln_w, e->w->eln_b, e->c.txt_ln_eps, R, H, e->h0, e->h0T, nullptr, nullptr, s));
     }
     for (int i = 0; i < TL; i++) {
         int r = text_layer(e, i, d_mask, ld, B, L, true, reuse_prefix && i == 0, s);
         if (r) return r;
     }
-    KCHK(e, itm_head(e->ta[TL - 1].h_out, e->itm_w, e->itm_b, d_logits ? d_logits : e->logits_scratch, B, L, H, s));
+    KCHK(e, itm_head(e->ta[TL - 1].h_out, e->w->itm_w, e->w->itm_b, d_logits ? d_logits : e->logits_scratch, B, L, H, s));
     return PNP_OK;
 }
 extern "C" int pnp_text_forward_xattn(pnp_engine* e, const int64_t* d_ids, const int64_t* d_mask, int32_t ld, int32_t B,
@@ -300,7 +300,7 @@ extern "C" int pnp_text_forward_text(pnp_engine* e, const int64_t* d_ids, const 
     if (!e || !d_ids || !d_mask) return PNP_ERR_ARG;
     if (T <= 0 || L < 2 || L > e->c.max_text_len || ld < L)
         return fail(e, PNP_ERR_ARG, "text batch %d x %d (ld %d) out of range (2 <= L <= %d, T > 0)", T, L, ld, e->c.max_text_len);
-    if (!e->finalized) return fail(e, PNP_ERR_STATE, "weights not finalized");
+    if (!e->w->finalized) return fail(e, PNP_ERR_STATE, "weights not finalized");
     hipStream_t s = (hipStream_t)stream;
     const int H = e->H, TL = e->TL;
     e->grad_layer = -1;
@@ -309,8 +309,8 @@ extern "C" int pnp_text_forward_text(pnp_engine* e, const int64_t* d_ids, const 
         const int B = T - t0 < e->c.max_batch ? T - t0 : e->c.max_batch, R = B * L;
         const int64_t* ids = d_ids + (size_t)t0 * ld;
         const int64_t* mask = d_mask + (size_t)t0 * ld;
-        KCHK(e, text_embed(ids, ld, e->word, e->tpos, e->temb, B, L, H, -1, e->c.vocab, s));
-        KCHK(e, layernorm(e->bf, e->temb, e->eln_w, e->eln_b, e->c.txt_ln_eps, R, H, e->h0, e->h0T, nullptr, nullptr, s));
+        KCHK(e, text_embed(ids, ld, e->w->word, e->w->tpos, e->temb, B, L, H, -1, e->c.vocab, s));
+        KCHK(e, layernorm(e->bf, e->temb, e->w->eln_w, e->w->eln_b, e->c.txt_ln_eps, R, H, e->h0, e->h0T, nullptr, nullptr, s));
         for (int i = 0; i < TL; i++) {
             int r = text_layer(e, i, mask, ld, B, L, false, false, s);
             if (r) return r;
@@ -336,12 +336,12 @@ extern "C" int pnp_project_normalize(pnp_engine* e, int32_t which, const float* 
     // the GEMM kernels address an operand by 32-bit byte offsets from its base
     if ((int64_t)rows * row_stride * 4 >= (int64_t)1 << 32)
         return fail(e, PNP_ERR_ARG, "rows %d x row_stride %lld: the input must span less than 4 GiB", rows, (long long)row_stride);
-    if (!e->finalized) return fail(e, PNP_ERR_STATE, "weights not finalized");
-    const Weight& w = e->proj_w[which];
-    if (!w.p || !e->proj_b[which])
+    if (!e->w->finalized) return fail(e, PNP_ERR_STATE, "weights not finalized");
+    const Weight& w = e->w->proj_w[which];
+    if (!w.p || !e->w->proj_b[which])
         return fail(e, PNP_ERR_STATE, "missing weight %s.weight (the state dict held no %s.weight / .bias)", kProj[which], kProj[which]);
     hipStream_t s = (hipStream_t)stream;
-    const int E = e->proj_E[which];
+    const int E = e->w->proj_E[which];
     if (e->bf) {
         // bf16 operands: rows are cast into xn (free between ViT forwards), as many at a time as it holds
         size_t cap = (size_t)e->c.max_batch * e->N * e->D / K;
@@ -350,12 +350,12 @@ extern "C" int pnp_project_normalize(pnp_engine* e, int32_t which, const float* 
             const int n = (int)((size_t)rows - r0 < cap ? (size_t)rows - r0 : cap);
             KCHK(e, cast_rows_bf16(d_x + r0 * row_stride, (int)row_stride, e->xn.hi, n, K, s));
             GemmArgs g = linear(e->xn.hi, K, w, n);
-            g.bias = e->proj_b[which]; g.out_f32 = d_out + r0 * E; g.ldo = E;
+            g.bias = e->w->proj_b[which]; g.out_f32 = d_out + r0 * E; g.ldo = E;
             KCHK(e, egemm(e, g, s));
         }
     } else {
         GemmArgs g = linear(d_x, (int)row_stride, w, rows);
-        g.bias = e->proj_b[which]; g.out_f32 = d_out; g.ldo = E;
+        g.bias = e->w->proj_b[which]; g.out_f32 = d_out; g.ldo = E;
         KCHK(e, egemm(e, g, s));
     }
     KCHK(e, l2_normalize_rows(d_out, rows, E, 1e-12f, s));
@@ -368,7 +368,7 @@ extern "C" int pnp_xattn_grad(pnp_engine* e, int32_t B, int32_t L, void* stream)
 
 extern "C" int pnp_xattn_grad_layer(pnp_engine* e, int32_t B, int32_t L, int32_t layer, void* stream) {
     if (!e) return PNP_ERR_ARG;
-    if (!e->finalized) return fail(e, PNP_ERR_STATE, "weights not finalized");
+    if (!e->w->finalized) return fail(e, PNP_ERR_STATE, "weights not finalized");
     if (B <= 0 || B > e->c.max_batch || L < 5 || L > e->c.max_text_len) return fail(e, PNP_ERR_ARG, "bad B/L");
     if (layer < e->SL || layer >= e->TL)
         return fail(e, PNP_ERR_ARG, "layer %d: cross-attention maps are kept for text layers %d..%d (stash_layer)", layer, e->SL, e->TL - 1);
@@ -378,9 +378,9 @@ extern "C" int pnp_xattn_grad_layer(pnp_engine* e, int32_t B, int32_t L, int32_t
     const int H = e->H, I = e->I, TL = e->TL, R = B * L, bf = e->bf, N = e->N, SL = e->SL;
     const int ldv = e->c.max_batch * e->Npad, nVn = TL - SL;
     e->grad_layer = layer;
-    KCHK(e, itm_grad_seed(e->itm_w, e->dh, B, L, H, s));
+    KCHK(e, itm_grad_seed(e->w->itm_w, e->dh, B, L, H, s));
     for (int i = TL - 1; i >= layer; i--) {
-        const TextLayerW& w = e->txt[i];
+        const TextLayerW& w = e->w->txt[i];
         TextLayerA& a = e->ta[i];
         KCHK(e, layernorm_bwd(bf, e->dh, w.oln_w, a.o_hat, a.o_rstd, R, H, e->d_pre, e->d_preT, s));
         {   // dg = (d_pre . Wo2) * gelu'(u)
