@@ -1,5 +1,7 @@
-// Internal to csrc/, included only by crf_lattice.hip, crf_meanfield.hip and crf_grad.hip: the device helpers and constants the
-// DenseCRF kernels of those units share, and the host-side helpers their launchers share.  The algorithm: crf_lattice.hip.
+// Internal to csrc/, included only by crf_lattice.hip and, through crf_tile.h, by crf_meanfield.hip and crf_grad.hip: the device
+// helpers and constants the DenseCRF kernels of those units share, and the host-side helpers their launchers share.  The pieces
+// of the tiled update / backward kernels (tile geometry, item walk, slice records, slice, label, store loop): crf_tile.h.
+// The algorithm: crf_lattice.hip.
 #pragma once
 #include <map>
 #include <mutex>

@@ -1,7 +1,7 @@
 // The reverse mode of the DenseCRF's feature-term mean-field: its kernels and their launchers.  The lattices are those of
 // crf_lattice.hip (the algorithm: that file's header), the forward kernels and crf_filter are in crf_meanfield.hip, the shared
-// helpers in crf_device.h.
-#include "crf_device.h"
+// helpers in crf_device.h, the pieces of the tiled kernels -- the forward's -- in crf_tile.h.
+#include "crf_tile.h"
 
 namespace pnp {
 
@@ -54,11 +54,12 @@ __global__ __launch_bounds__(256) void crf_softmax_backward_kernel(const PostDes
     }
 }
 
-// One term of the backward update on a TW x TH pixel tile, with crf_term_update_kernel's tiles, XCD-affine image schedule and
-// LDS-staged slice records: h = C^T dl -- w dl (KIND 0), wvec (.) dl (1), h[k] = sum_l M[l][k] dl[l] (2: row k of the transposed
+// One term of the backward update on a TW x TH pixel tile, from the pieces of crf_term_update_kernel (crf_tile.h: tiles, item
+// walk, wave roles, LDS-staged slice records, slice, store loop) in the XCD-affine image schedule: h = C^T dl -- w dl
+// (KIND 0), wvec (.) dl (1), h[k] = sum_l M[l][k] dl[l] (2: row k of the transposed
 // matrix MT is contiguous; lane = pixel, rows through scalar loads as in the forward's phase 2) -- into the rows of `h`.
-// val non-null (the forward-filtered values of Q_{i-1}): the tile also slices msg = A Q_{i-1} with crf_term_update_kernel's
-// sequence and leaves the compatibility gradient of its pixels, in pixel order in fp32, as ONE partial of psz floats at
+// val non-null (the forward-filtered values of Q_{i-1}): the tile also slices msg = A Q_{i-1} (crf_gather_rows / crf_slice_rows,
+// the forward's bits) and leaves the compatibility gradient of its pixels, in pixel order in fp32, as ONE partial of psz floats at
 // part[(tile0[b] - tile0[img0] + tile - t_lo) * psz]: sum_p sum_l dl msg (KIND 0), [l] sum_p dl[l] msg[l] (1), [l * K + k] sum_p dl[l]
 // msg[k] (2: a thread owns entries tid, tid + 256, ..; both tiles stay in LDS, rows of Kp + 1 floats).  Pixels of an edge
 // tile outside the image carry dl = 0.  crf_grad_reduce adds the partials.
@@ -72,24 +73,23 @@ __global__ __launch_bounds__(256) void crf_term_backward_kernel(const CrfLattice
     extern __shared__ __attribute__((aligned(16))) float tile[];        // dl [TP][Kp + 1], msg / h [TP][Kp + 1], the slice records
     __shared__ float red[256];                                          // (KIND 0: the per-label sums of a tile)
     const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, bpx = gridDim.x >> 3;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int tid = threadIdx.x;
     const int TW = crf_tile_w(TP), TH = TP / TW;
     const int tw_shift = __ffs(TW) - 1;
-    const int WPS = TP > 64 ? TP >> 6 : 1, NG = 4 / WPS;
-    const int px2 = (wave % WPS) * 64 + lane, lg = wave / WPS;
-    const bool act = px2 < TP;
-    const int pxc = act ? px2 : TP - 1;
+    const CrfWaveRole wr = crf_wave_role(TP, tid);                      // (KIND 2)
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
     int b, part_i, parts;
     for (int wi = 0; xcd_work(wi, xcd, img0, nimg, b, part_i, parts); wi++) {
         const PostDesc im = imgs[b];
         const int K = im.K, Kp = im.Kp, K4 = Kp >> 2, ldt = Kp + 1;
         const int lo = L.idbase[b];
-        const int tiles_x = (im.W + TW - 1) / TW, tiles_y = (im.H + TH - 1) / TH, ntiles = tiles_x * tiles_y;
-        // the launch takes tiles [t_lo, t_hi) of every image (all of them, or a span of one image whose partials fill the buffer)
+        const CrfTiles tiles = crf_tiles(im, TW, TH);
+        // the launch takes tiles [t_lo, t_hi) of every image (all of them, or a span of one image whose partials fill the
+        // buffer), so the slice's share is taken of that window
+        const int ntiles = tiles.ntiles;
         const int tl0 = t_lo < ntiles ? t_lo : ntiles, nt = (t_hi < ntiles ? t_hi : ntiles) - tl0;
-        const int tfirst = tl0 + (int)((long)nt * part_i / parts), tend = tl0 + (int)((long)nt * (part_i + 1) / parts);
+        const CrfShare sh = crf_share(nt, part_i, parts);
+        const int tfirst = tl0 + sh.first, tend = tl0 + sh.end;
         const char* const Db = reinterpret_cast<const char*>(dl + im.qoff);
         const char* const Vb = reinterpret_cast<const char*>(val ? val + im.voff[0] : nullptr);
         f32x4* const H4 = reinterpret_cast<f32x4*>(h + im.qoff);
@@ -99,67 +99,40 @@ __global__ __launch_bounds__(256) void crf_term_backward_kernel(const CrfLattice
         float* const rec_w = reinterpret_cast<float*>(rec_o + TP * D1);
         float* const rec_n = rec_w + TP * D1;
         const int tbase = val ? tile0[b] - tile0[img0] - tl0 : 0;
-        const int q256 = 256 / K4, r256 = 256 - q256 * K4;
-        const int pl0 = tid / K4, c0 = tid - pl0 * K4;
+        const CrfItemWalk it0(tid, K4);
         for (int tl = tfirst + slot; tl < tend; tl += bpx) {
-            const int ty = tl / tiles_x, tx = tl - ty * tiles_x;
-            const int x0 = tx * TW, y0 = ty * TH;
-            auto pixel_of = [&](int pl) {
-                const int x = x0 + (pl & (TW - 1)), y = y0 + (pl >> tw_shift);
-                return (y < im.H ? y : im.H - 1) * im.W + (x < im.W ? x : im.W - 1);
-            };
-            auto inside = [&](int pl) { return x0 + (pl & (TW - 1)) < im.W && y0 + (pl >> tw_shift) < im.H; };
+            const CrfTileAt at = tiles.at(tl, TW, TH, tw_shift, im);
             if (val) {
-                for (int pl = tid; pl < TP; pl += 256) {
-                    const size_t g = (size_t)im.pix0 + pixel_of(pl);
-#pragma unroll
-                    for (int v = 0; v < D1; v++) {
-                        rec_o[pl * D1 + v] = L.offset[g * D1 + v] - lo;
-                        rec_w[pl * D1 + v] = L.bary[g * D1 + v];
-                    }
+                for (int pl = tid; pl < TP; pl += 256) {                 // slice records, one pixel per thread
+                    const size_t g = (size_t)im.pix0 + at.pixel_of(pl);
+                    crf_stage_record<D1>(L, lo, g, pl, rec_o, rec_w);
                     rec_n[pl] = norm[g];
                 }
                 __syncthreads();
             }
-            {   // phase 1: the dl chunk of every (pixel, chunk) item, its message chunk if asked for, and h without a matrix
-                int pl = pl0, c = c0;
-                for (int item = tid; item < TP * K4; item += 256) {
-                    const int px = pixel_of(pl);
-                    const bool in = inside(pl);
-                    const uint32_t cofs = (uint32_t)c * 16u;
-                    const f32x4 d = in ? *reinterpret_cast<const f32x4*>(Db + (__umul24((uint32_t)px, rowb) + cofs)) : zero;
-                    if (val) {
-                        f32x4 vv[D1];
+            // phase 1: the dl chunk of every (pixel, chunk) item, its message chunk if asked for, and h without a matrix
+            for (CrfItemWalk it = it0; it.item < TP * K4; it.next()) {
+                const int pl = it.pl, c = it.c, px = at.pixel_of(pl);
+                const bool in = at.inside(pl);
+                const uint32_t cofs = (uint32_t)c * 16u;
+                const f32x4 d = in ? *reinterpret_cast<const f32x4*>(Db + (__umul24((uint32_t)px, rowb) + cofs)) : zero;
+                if (val) {
+                    f32x4 vv[D1];
+                    crf_gather_rows<D1>(Vb, rec_o + pl * D1, rowb, cofs, vv);
+                    const f32x4 o = crf_slice_rows<D1>(vv, rec_w + pl * D1, alpha);
+                    const float nr = rec_n[pl];
 #pragma unroll
-                        for (int v = 0; v < D1; v++)
-                            vv[v] = *reinterpret_cast<const f32x4*>(Vb + (__umul24((uint32_t)rec_o[pl * D1 + v], rowb) + cofs));
-                        f32x4 o = zero;
+                    for (int i = 0; i < 4; i++) msg[pl * ldt + 4 * c + i] = __fmul_rn(o[i], nr);
+                }
 #pragma unroll
-                        for (int v = 0; v < D1; v++) {
-                            const float wv = rec_w[pl * D1 + v];
+                for (int i = 0; i < 4; i++) tile[pl * ldt + 4 * c + i] = d[i];
+                if (KIND != 2 && in) {
+                    f32x4 wl = {w, w, w, w};
+                    if (KIND == 1) wl = *reinterpret_cast<const f32x4*>(wvec + 4 * c);
+                    f32x4 hh;
 #pragma unroll
-                            for (int i = 0; i < 4; i++) o[i] = __fadd_rn(o[i], __fmul_rn(__fmul_rn(wv, vv[v][i]), alpha));
-                        }
-                        const float nr = rec_n[pl];
-#pragma unroll
-                        for (int i = 0; i < 4; i++) msg[pl * ldt + 4 * c + i] = __fmul_rn(o[i], nr);
-                    }
-#pragma unroll
-                    for (int i = 0; i < 4; i++) tile[pl * ldt + 4 * c + i] = d[i];
-                    if (KIND != 2 && in) {
-                        f32x4 wl = {w, w, w, w};
-                        if (KIND == 1) wl = *reinterpret_cast<const f32x4*>(wvec + 4 * c);
-                        f32x4 hh;
-#pragma unroll
-                        for (int i = 0; i < 4; i++) hh[i] = wl[i] * d[i];
-                        H4[(size_t)px * K4 + c] = hh;
-                    }
-                    pl += q256;
-                    c += r256;
-                    if (c >= K4) {
-                        c -= K4;
-                        pl++;
-                    }
+                    for (int i = 0; i < 4; i++) hh[i] = wl[i] * d[i];
+                    H4[(size_t)px * K4 + c] = hh;
                 }
             }
             __syncthreads();
@@ -193,8 +166,8 @@ __global__ __launch_bounds__(256) void crf_term_backward_kernel(const CrfLattice
                 __syncthreads();
             }
             if (KIND == 2) {   // h[k] = sum_l M[l][k] dl[l] into the message tile (its last reader is behind the barrier above)
-                const float* const x = tile + pxc * ldt;
-                for (int k0 = lg * CRF_CL; k0 < K; k0 += NG * CRF_CL) {
+                const float* const x = tile + wr.pxc * ldt;
+                for (int k0 = wr.lg * CRF_CL; k0 < K; k0 += wr.NG * CRF_CL) {
                     float a[CRF_CL];
 #pragma unroll
                     for (int i = 0; i < CRF_CL; i++) a[i] = 0.f;
@@ -207,23 +180,10 @@ __global__ __launch_bounds__(256) void crf_term_backward_kernel(const CrfLattice
                     }
 #pragma unroll
                     for (int i = 0; i < CRF_CL; i++)
-                        if (act && k0 + i < Kp) msg[px2 * ldt + k0 + i] = a[i];
+                        if (wr.act && k0 + i < Kp) msg[wr.px2 * ldt + k0 + i] = a[i];
                 }
                 __syncthreads();
-                int pl = pl0, c = c0;
-                for (int item = tid; item < TP * K4; item += 256) {
-                    if (inside(pl)) {
-                        const float* r = msg + pl * ldt + 4 * c;
-                        const f32x4 v = {r[0], r[1], r[2], r[3]};
-                        H4[(size_t)pixel_of(pl) * K4 + c] = v;
-                    }
-                    pl += q256;
-                    c += r256;
-                    if (c >= K4) {
-                        c -= K4;
-                        pl++;
-                    }
-                }
+                crf_store_tile<false>(msg, ldt, at, it0, TP, H4);
                 __syncthreads();
             }
         }
@@ -268,13 +228,14 @@ __global__ __launch_bounds__(256) void crf_grad_emit_kernel(const double* __rest
 }
 
 // g[p] (+)= norm[p] * alpha * sum_v bary_v val_v: the slice of A^T h into the cotangent rows -- a store for the first term of
-// an update, a read-modify-write after it.  (pixel, 16-byte chunk) items over 16 x 16 pixel tiles in the XCD-affine schedule;
-// the D1 vertex ids and weights of a pixel are read by each of its lanes (one cached line per pixel).
+// an update, a read-modify-write after it.  (pixel, 16-byte chunk) items over 16 x 16 pixel tiles in the XCD-affine schedule,
+// sliced with the forward's pieces (crf_tile.h); no LDS: the D1 vertex ids and weights of a pixel are read by each of its lanes
+// (one cached line per pixel), and pixels outside the image are skipped.
 template <int D1>
 __global__ __launch_bounds__(256) void crf_slice_add_kernel(const CrfLattice L, const PostDesc* __restrict__ imgs, const float* __restrict__ val,
                                                             const float* __restrict__ norm, float* __restrict__ g, int first, float alpha,
                                                             int img0, int nimg) {
-    constexpr int TW = 16, TH = 16, TP = TW * TH;
+    constexpr int TW_SHIFT = 4, TW = 1 << TW_SHIFT, TH = 16, TP = TW * TH;
     const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, bpx = gridDim.x >> 3;
     const int tid = threadIdx.x;
     int b, part_i, parts;
@@ -282,22 +243,19 @@ __global__ __launch_bounds__(256) void crf_slice_add_kernel(const CrfLattice L, 
         const PostDesc im = imgs[b];
         const int K4 = im.Kp >> 2;
         const int lo = L.idbase[b];
-        const int tiles_x = (im.W + TW - 1) / TW, tiles_y = (im.H + TH - 1) / TH, ntiles = tiles_x * tiles_y;
-        const int tfirst = (int)((long)ntiles * part_i / parts), tend = (int)((long)ntiles * (part_i + 1) / parts);
+        const CrfTiles tiles = crf_tiles(im, TW, TH);
+        const CrfShare sh = crf_share(tiles.ntiles, part_i, parts);
         const char* const Vb = reinterpret_cast<const char*>(val + im.voff[0]);
         f32x4* const G4 = reinterpret_cast<f32x4*>(g + im.qoff);
         const uint32_t rowb = (uint32_t)K4 * 16u;
-        const int q256 = 256 / K4, r256 = 256 - q256 * K4;
-        const int pl0 = tid / K4, c0 = tid - pl0 * K4;
-        for (int tl = tfirst + slot; tl < tend; tl += bpx) {
-            const int ty = tl / tiles_x, tx = tl - ty * tiles_x;
-            int pl = pl0, c = c0;
-            for (int item = tid; item < TP * K4; item += 256) {
-                const int x = tx * TW + (pl & (TW - 1)), y = ty * TH + (pl >> 4);
-                if (x < im.W && y < im.H) {
-                    const int px = y * im.W + x;
+        const CrfItemWalk it0(tid, K4);
+        for (int tl = sh.first + slot; tl < sh.end; tl += bpx) {
+            const CrfTileAt at = tiles.at(tl, TW, TH, TW_SHIFT, im);
+            for (CrfItemWalk it = it0; it.item < TP * K4; it.next()) {
+                if (at.inside(it.pl)) {
+                    const int px = at.pixel_inside(it.pl);
                     const size_t gi = (size_t)im.pix0 + px;
-                    const uint32_t cofs = (uint32_t)c * 16u;
+                    const uint32_t cofs = (uint32_t)it.c * 16u;
                     int ids[D1];
                     float wv[D1];
 #pragma unroll
@@ -307,25 +265,14 @@ __global__ __launch_bounds__(256) void crf_slice_add_kernel(const CrfLattice L, 
                     }
                     const float nr = norm[gi];
                     f32x4 vv[D1];
-#pragma unroll
-                    for (int v = 0; v < D1; v++) vv[v] = *reinterpret_cast<const f32x4*>(Vb + (__umul24((uint32_t)ids[v], rowb) + cofs));
-                    f32x4 o = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                    for (int v = 0; v < D1; v++)
-#pragma unroll
-                        for (int i = 0; i < 4; i++) o[i] = __fadd_rn(o[i], __fmul_rn(__fmul_rn(wv[v], vv[v][i]), alpha));
-                    f32x4* const at = G4 + (size_t)px * K4 + c;
+                    crf_gather_rows<D1>(Vb, ids, rowb, cofs, vv);
+                    const f32x4 o = crf_slice_rows<D1>(vv, wv, alpha);
+                    f32x4* const to = G4 + (size_t)px * K4 + it.c;
                     f32x4 r = {0.f, 0.f, 0.f, 0.f};
-                    if (!first) r = *at;
+                    if (!first) r = *to;
 #pragma unroll
                     for (int i = 0; i < 4; i++) r[i] = __fadd_rn(r[i], __fmul_rn(o[i], nr));
-                    *at = r;
-                }
-                pl += q256;
-                c += r256;
-                if (c >= K4) {
-                    c -= K4;
-                    pl++;
+                    *to = r;
                 }
             }
         }

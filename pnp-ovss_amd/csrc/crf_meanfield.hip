@@ -1,7 +1,7 @@
 // The forward mean-field of the DenseCRF on the lattices of crf_lattice.hip (the algorithm and its contract: that file's
 // header): splat, lattice blurs and the three update kernels, with their launchers.  Shared helpers and the XCD work
-// distribution of these kernels: crf_device.h.
-#include "crf_device.h"
+// distribution of these kernels: crf_device.h; the pieces the update kernels are put together from: crf_tile.h.
+#include "crf_tile.h"
 
 namespace pnp {
 
@@ -260,7 +260,9 @@ void crf_blur4x2_kernel(const CrfLattice L, const PostDesc* __restrict__ imgs,
 // touches about half the distinct value rows of a strip of the same size and the slice gathers hit L1 / L2 accordingly.
 // WIDE (rows of >= CRF_WAVE_SOFTMAX_K channels per group): the wave-parallel softmax below; such tiles are LDS-bound to three
 // workgroups per CU, so the kernel may use 128 registers (the narrow form is held to 80 for six waves per SIMD: 714 -> 607 us
-// per launch on the headline batch, of which 714 -> 648 at five waves from the leaner record staging and store loop below)
+// per launch on the headline batch, of which 714 -> 648 at five waves from the leaner record staging and store loop below).
+// Tile geometry, item walk, record staging, slice, label and store loop are the pieces of crf_tile.h, shared with the kernels
+// below; the two softmax forms, thread per row and wave per rows, are this kernel's own.
 template <bool WIDE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WIDE ? 4 : 6)))
 void crf_update_kernel(const CrfLattice Lg, const CrfLattice Lb, const PostDesc* __restrict__ imgs,
@@ -285,8 +287,8 @@ void crf_update_kernel(const CrfLattice Lg, const CrfLattice Lb, const PostDesc*
         const int TPe = CRF_TP / im.G < tp_cap ? CRF_TP / im.G : tp_cap; // one softmax thread per (pixel, group)
         const int TW = tile_w > 0 ? tile_w : crf_tile_w(TPe), TH = TPe / TW, TP = TW * TH;   // TW: a power of two
         const int tw_shift = __ffs(TW) - 1;
-        const int tiles_x = (im.W + TW - 1) / TW, tiles_y = (im.H + TH - 1) / TH, ntiles = tiles_x * tiles_y;
-        const int tfirst = (int)((long)ntiles * part / parts), tend = (int)((long)ntiles * (part + 1) / parts);
+        const CrfTiles tiles = crf_tiles(im, TW, TH);
+        const CrfShare sh = crf_share(tiles.ntiles, part, parts);
         // rows of the pixel-major arrays and of the lattice value arrays as base + 32-bit byte offset
         const char* const Ub = reinterpret_cast<const char*>(unary + im.qoff);
         const char* const Gb = reinterpret_cast<const char*>(vg + im.voff[0]);
@@ -298,18 +300,9 @@ void crf_update_kernel(const CrfLattice Lg, const CrfLattice Lb, const PostDesc*
         float* const rec_wg = reinterpret_cast<float*>(rec_og + TP * 3);
         float* const rec_nb = rec_wg + TP * 3;
         float* const rec_ng = rec_nb + TP;
-        const int q256 = 256 / K4, r256 = 256 - q256 * K4;             // item -> (pixel, chunk) advance without a division
-        const int pl0 = tid / K4, c0 = tid - pl0 * K4;
-        for (int tl = tfirst + slot; tl < tend; tl += bpx) {
-            const int ty = tl / tiles_x, tx = tl - ty * tiles_x;
-            const int x0 = tx * TW, y0 = ty * TH;
-            // slots of an edge tile that fall outside the image redo its last column / row (branch-free main loop) and
-            // store nothing
-            auto pixel_of = [&](int pl) {
-                const int x = x0 + (pl & (TW - 1)), y = y0 + (pl >> tw_shift);
-                return (y < im.H ? y : im.H - 1) * im.W + (x < im.W ? x : im.W - 1);
-            };
-            auto inside = [&](int pl) { return x0 + (pl & (TW - 1)) < im.W && y0 + (pl >> tw_shift) < im.H; };
+        const CrfItemWalk it0(tid, K4);
+        for (int tl = sh.first + slot; tl < sh.end; tl += bpx) {
+            const CrfTileAt at = tiles.at(tl, TW, TH, tw_shift, im);
             // the tile's per-pixel slice records -- 6 + 3 image-local lattice ids and barycentric weights, two normalisers --
             // are staged once through LDS instead of being fetched by every channel-chunk lane of the pixel: 10 vector-memory
             // instructions per (pixel, chunk) item instead of 30 (the kernel is issue-bound there).  One thread per pixel: its
@@ -317,73 +310,34 @@ void crf_update_kernel(const CrfLattice Lg, const CrfLattice Lb, const PostDesc*
             // loop in registers
             if (pairwise) {
                 for (int pl = tid; pl < TP; pl += 256) {                 // (TP <= 256: one pixel per thread)
-                    const size_t g = (size_t)im.pix0 + pixel_of(pl);
-#pragma unroll
-                    for (int v = 0; v < 6; v++) {
-                        rec_ob[pl * 6 + v] = Lb.offset[g * 6 + v] - lo_b;
-                        rec_wb[pl * 6 + v] = Lb.bary[g * 6 + v];
-                    }
-#pragma unroll
-                    for (int v = 0; v < 3; v++) {
-                        rec_og[pl * 3 + v] = Lg.offset[g * 3 + v] - lo_g;
-                        rec_wg[pl * 3 + v] = Lg.bary[g * 3 + v];
-                    }
+                    const size_t g = (size_t)im.pix0 + at.pixel_of(pl);
+                    crf_stage_record<6>(Lb, lo_b, g, pl, rec_ob, rec_wb);
+                    crf_stage_record<3>(Lg, lo_g, g, pl, rec_og, rec_wg);
                     rec_nb[pl] = norm_b[g];
                     rec_ng[pl] = norm_g[g];
                 }
                 __syncthreads();
             }
-            {
-                int pl = pl0, c = c0;
-                for (int item = tid; item < TP * K4; item += 256) {
-                    const int px = pixel_of(pl);
-                    {
-                        const uint32_t cofs = (uint32_t)c * 16u;
-                        const f32x4 u = ld_stream(reinterpret_cast<const f32x4*>(Ub + (__umul24((uint32_t)px, rowb) + cofs)));
-                        f32x4 t = {-u[0], -u[1], -u[2], -u[3]};
-                        if (pairwise) {
-                            f32x4 vg3[3], vb6[6];
+            for (CrfItemWalk it = it0; it.item < TP * K4; it.next()) {
+                const int pl = it.pl, c = it.c, px = at.pixel_of(pl);
+                const uint32_t cofs = (uint32_t)c * 16u;
+                const f32x4 u = ld_stream(reinterpret_cast<const f32x4*>(Ub + (__umul24((uint32_t)px, rowb) + cofs)));
+                f32x4 t = {-u[0], -u[1], -u[2], -u[3]};
+                if (pairwise) {
+                    f32x4 vg3[3], vb6[6];
+                    crf_gather_rows<3>(Gb, rec_og + pl * 3, rowb, cofs, vg3);
+                    crf_gather_rows<6>(Bb, rec_ob + pl * 6, rowb, cofs, vb6);
+                    const f32x4 og = crf_slice_rows<3>(vg3, rec_wg + pl * 3, alpha_g);
+                    const float nrg = rec_ng[pl];
 #pragma unroll
-                            for (int v = 0; v < 3; v++)
-                                vg3[v] = *reinterpret_cast<const f32x4*>(Gb + (__umul24((uint32_t)rec_og[pl * 3 + v], rowb) + cofs));
+                    for (int i = 0; i < 4; i++) t[i] = __fsub_rn(t[i], __fmul_rn(-w_g, __fmul_rn(og[i], nrg)));
+                    const f32x4 ob = crf_slice_rows<6>(vb6, rec_wb + pl * 6, alpha_b);
+                    const float nrb = rec_nb[pl];
 #pragma unroll
-                            for (int v = 0; v < 6; v++)
-                                vb6[v] = *reinterpret_cast<const f32x4*>(Bb + (__umul24((uint32_t)rec_ob[pl * 6 + v], rowb) + cofs));
-                            {
-                                f32x4 out = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                                for (int v = 0; v < 3; v++) {
-                                    const float wv = rec_wg[pl * 3 + v];
-#pragma unroll
-                                    for (int i = 0; i < 4; i++) out[i] = __fadd_rn(out[i], __fmul_rn(__fmul_rn(wv, vg3[v][i]), alpha_g));
-                                }
-                                const float nr = rec_ng[pl];
-#pragma unroll
-                                for (int i = 0; i < 4; i++) t[i] = __fsub_rn(t[i], __fmul_rn(-w_g, __fmul_rn(out[i], nr)));
-                            }
-                            {
-                                f32x4 out = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                                for (int v = 0; v < 6; v++) {
-                                    const float wv = rec_wb[pl * 6 + v];
-#pragma unroll
-                                    for (int i = 0; i < 4; i++) out[i] = __fadd_rn(out[i], __fmul_rn(__fmul_rn(wv, vb6[v][i]), alpha_b));
-                                }
-                                const float nr = rec_nb[pl];
-#pragma unroll
-                                for (int i = 0; i < 4; i++) t[i] = __fsub_rn(t[i], __fmul_rn(-w_b, __fmul_rn(out[i], nr)));
-                            }
-                        }
-#pragma unroll
-                        for (int i = 0; i < 4; i++) tile[pl * ldt + 4 * c + i] = t[i];
-                    }
-                    pl += q256;
-                    c += r256;
-                    if (c >= K4) {
-                        c -= K4;
-                        pl++;
-                    }
+                    for (int i = 0; i < 4; i++) t[i] = __fsub_rn(t[i], __fmul_rn(-w_b, __fmul_rn(ob[i], nrb)));
                 }
+#pragma unroll
+                for (int i = 0; i < 4; i++) tile[pl * ldt + 4 * c + i] = t[i];
             }
             __syncthreads();
             if (WIDE && K >= CRF_WAVE_SOFTMAX_K) {                       // (per image: the rows of a batch differ in width)
@@ -450,24 +404,12 @@ void crf_update_kernel(const CrfLattice Lg, const CrfLattice Lb, const PostDesc*
                 if (lane < RW) {
                     const int rr = rbase + lane, grp = rr / TP, px = rr - grp * TP;
                     float* row = tile + px * ldt + grp * im.Kg;
-                    if (lout.lab[grp]) {                                // last iteration: first maximum, NaN counts as maximum
-                        int best = 0;
-                        float bv = row[0];
-                        for (int k = 1; k < K; k++) {
-                            const float v = row[k];
-                            if (bv == bv && (v > bv || v != v)) {
-                                best = k;
-                                bv = v;
-                            }
-                        }
-                        if (inside(px)) lout.lab[grp][lout.label_off[b] + pixel_of(px)] = (uint8_t)lout.lut[b * lout.lut_stride + best];
-                    }
+                    crf_store_label(lout, grp, b, at, px, row, K);         // (last iteration)
                     if (grp == im.G - 1)                                // pad floats behind the last group stay zero
                         for (int k = im.G * im.Kg; k < Kp; k++) tile[px * ldt + k] = 0.f;
                 }
             } else if (tid < TP * im.G) {                               // one softmax per (pixel, channel group)
                 const int grp = tid / TP, px = tid - grp * TP;
-                const int p = pixel_of(px);
                 {
                     float* row = tile + px * ldt + grp * im.Kg;
                     float m = row[0];
@@ -482,40 +424,13 @@ void crf_update_kernel(const CrfLattice Lg, const CrfLattice Lb, const PostDesc*
                         s = __fadd_rn(s, e);
                     }
                     for (int k = 0; k < K; k++) row[k] = __fdiv_rn(row[k], s);
-                    if (lout.lab[grp]) {
-                        // last iteration: the label of this (pixel, group) straight from the marginals in LDS -- first maximum,
-                        // NaN counts as maximum (np.argmax, as argmax_kernel reads them back from memory) -- through the LUT
-                        int best = 0;
-                        float bv = row[0];
-                        for (int k = 1; k < K; k++) {
-                            const float v = row[k];
-                            if (bv == bv && (v > bv || v != v)) {
-                                best = k;
-                                bv = v;
-                            }
-                        }
-                        if (inside(px)) lout.lab[grp][lout.label_off[b] + p] = (uint8_t)lout.lut[b * lout.lut_stride + best];
-                    }
+                    crf_store_label(lout, grp, b, at, px, row, K);         // (last iteration)
                     if (grp == im.G - 1)                                // pad floats behind the last group stay zero
                         for (int k = im.G * im.Kg; k < Kp; k++) tile[px * ldt + k] = 0.f;
                 }
             }
             __syncthreads();
-            {
-                int pl = pl0, c = c0;
-                for (int item = tid; item < TP * K4; item += 256) {
-                    if (inside(pl)) {
-                        const float* r = tile + pl * ldt + 4 * c;
-                        st_stream(Q4 + (size_t)pixel_of(pl) * K4 + c, f32x4{r[0], r[1], r[2], r[3]});
-                    }
-                    pl += q256;
-                    c += r256;
-                    if (c >= K4) {
-                        c -= K4;
-                        pl++;
-                    }
-                }
-            }
+            crf_store_tile<true>(tile, ldt, at, it0, TP, Q4);
             __syncthreads();
         }
     }
@@ -526,11 +441,15 @@ void crf_update_kernel(const CrfLattice Lg, const CrfLattice Lb, const PostDesc*
 //   acc_t[l] = sum_k M_t[l][k] * msg_t[k]   (one fp32 accumulator per output, k ascending, multiply and add rounded
 //                                            separately: no FMA, no MFMA -- the order of the sum is part of the contract)
 //   logit[l] = (-U[l] + acc_g[l]) + acc_b[l],   Q = softmax(logit)
-// msg_t[k] is what crf_update_kernel forms per term -- (sum_v (bary_v * val_v[k]) * alpha_t) * norm_t, same instruction
-// sequence and vertex order -- so M_t = w * I gives the Potts kernel's logits value for value (the other products are exact
-// zeros).  Same TW x TH block tiles, LDS-staged slice records, XCD-affine sweep and 16-byte global I/O as crf_update_kernel.
-// Phase 1 (lanes over (pixel, 16-byte chunk) items, as there) puts -U into the logit tile and the two message rows of every
-// pixel into LDS (row stride Kp + 1: odd, so the per-pixel reads of phase 2 hit 32 distinct banks per half wave).  Phase 2 does
+// msg_t[k] is what crf_update_kernel forms per term -- (sum_v (bary_v * val_v[k]) * alpha_t) * norm_t, the statements of
+// crf_gather_rows / crf_slice_rows in their order -- so M_t = w * I gives the Potts kernel's logits value for value (the other
+// products are exact zeros).  Same TW x TH block tiles, LDS-staged slice records, XCD-affine sweep and 16-byte global I/O as
+// crf_update_kernel, but WRITTEN OUT here, not called from crf_tile.h: with the pieces the compiler scheduled the scalar loads
+// of phase 2's inner loop differently and the K = 150 update ran 3.7 - 4.5 % slower (profiles/crf_update_pieces.txt; no single
+// piece does it).  A change to a piece is repeated here by hand; tests/test_crf_general_gpu.py and test_crf_terms_gpu.py hold
+// this kernel to the others bit for bit.  Phase 1 (lanes over (pixel, 16-byte chunk) items) puts -U into the logit tile and
+// the two message rows of every pixel into LDS (row stride Kp + 1: odd, so the per-pixel reads of phase 2 hit 32 distinct
+// banks per half wave).  Phase 2 does
 // the two K x K products with lane = pixel: a wave owns 64 pixels (32 where a tile has only 32: half the lanes idle) and a
 // block of CRF_CL labels l at a time, so every M_t[l][k] is the same in all lanes and is read with scalar loads from global
 // memory (two 150 x 150 matrices are 180 KB: not LDS material), and one LDS read of msg_t[k] feeds CRF_CL accumulators.  The
@@ -538,7 +457,7 @@ void crf_update_kernel(const CrfLattice Lg, const CrfLattice Lb, const PostDesc*
 // block needs for one k are 32 consecutive bytes -- one scalar load and one pointer per term -- and a block that reaches past K
 // multiplies by the pad's zeros into accumulators nobody reads.  The
 // blocks of l are dealt round the 4 / (TP / 64) waves that share a pixel set.  Then softmax, labels and the zeroing of the pad
-// floats with crf_update_kernel's thread-per-row arithmetic, and the same store loop.
+// floats with crf_update_kernel's thread-per-row arithmetic, and its store loop.
 // Tile size (crf_update_compat): 256 / 128 pixels while the three LDS rows per pixel stay under 64 KB (Kp <= 12 / <= 32), 64
 // up to Kp = 200, 32 beyond (three rows of 257 floats x 64 pixels would pass the CU's 160 KB).
 // KL = true: no update.  The tile holds Q instead of -U and a fourth row per pixel holds U; phase 2 ends in the pixel's term of
@@ -790,17 +709,19 @@ __global__ __launch_bounds__(256) void crf_update_compat_kernel(const CrfLattice
 // One pairwise term of a T-term update over caller-supplied features (pnp_crf_set_batch_terms; the two-term runs above never come
 // here): slice the term's blurred lattice (D1 = d + 1 = 2 .. 7 vertices per pixel), weigh the message, add it into the
 // pixel-major logit row, and after the last term take the softmax:
-//   msg[k]   = (sum_v (bary_v * val_v[k]) * alpha) * norm        v ascending: crf_update_kernel's sequence per term
+//   msg[k]   = (sum_v (bary_v * val_v[k]) * alpha) * norm        crf_gather_rows / crf_slice_rows<D1>
 //   acc[l]   = w * msg[l] | wvec[l] * msg[l] | sum_k M[l][k] * msg[k]      (one fp32 accumulator, k ascending, no FMA)
 //   row[l]   = (first ? -U[l] : row[l]) + acc[l]
 //   last:  Q = softmax(row), labels, zero pad -- crf_update_compat_kernel's arithmetic element by element
-// so T = 2 with xy and xy+rgb features leaves the bits of crf_update_kernel (scalars) / crf_update_compat_kernel (matrices).
-// Built like crf_update_compat_kernel: TW x TH pixel tiles, XCD-affine image schedule, slice records (2 D1 + 1 words per pixel)
-// staged in LDS by one thread per pixel, 16-byte row gathers with lanes over (pixel, chunk) items.  `base` and `out` may be the
+// so T = 2 with xy and xy+rgb features leaves the bits of crf_update_kernel (scalars: the same functions for 3 and 6 vertices)
+// / crf_update_compat_kernel (matrices: the same statements, written out there).  The other pieces of crf_tile.h: TW x TH
+// pixel tiles, slice records (2 D1 + 1 words per pixel) staged in LDS by one thread per pixel, 16-byte row gathers with lanes
+// over (pixel, chunk) items, wave roles of phase 2, store loop; XCD-affine image schedule.  `base` and `out` may be the
 // same array (the logit rows, updated in place: an item reads its chunk before it writes it, and a tile's rows are only its
 // own).  What a launch keeps in LDS besides the records: nothing (scalar / vector weights, not last: rows go from registers
 // straight to memory), the logit tile (last: the softmax needs whole rows), or tile + message rows (MATRIX: phase 2 with
-// lane = pixel and the transposed matrix through scalar loads, as there).  imgs: the TERM's descriptors (voff[0] = its value rows).
+// lane = pixel and the transposed matrix through scalar loads: crf_update_compat_kernel's, written out for one term).
+// imgs: the TERM's descriptors (voff[0] = its value rows).
 // Per-thread arrays are indexed by unrolled loops over the template's D1 only.
 template <int D1, bool MATRIX>
 __global__ __launch_bounds__(256) void crf_term_update_kernel(const CrfLattice L, const PostDesc* __restrict__ imgs, const float* __restrict__ val,
@@ -809,23 +730,18 @@ __global__ __launch_bounds__(256) void crf_term_update_kernel(const CrfLattice L
                                                               float alpha, int img0, int nimg, int TP, const CrfLabelOut lout) {
     extern __shared__ __attribute__((aligned(16))) float tile[];        // [TP][Kp + 1] x (0 | 1 | 2), then the slice records
     const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, bpx = gridDim.x >> 3;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int tid = threadIdx.x;
     const bool tiled = MATRIX || last;
     const int TW = crf_tile_w(TP), TH = TP / TW;                        // TP = 32 .. 256, a power of two
     const int tw_shift = __ffs(TW) - 1;
-    // phase 2 and the softmax: WPS waves cover the pixels of a tile, NG = 4 / WPS waves share a pixel set
-    const int WPS = TP > 64 ? TP >> 6 : 1, NG = 4 / WPS;
-    const int px2 = (wave % WPS) * 64 + lane, lg = wave / WPS;
-    const bool act = px2 < TP;
-    const int pxc = act ? px2 : TP - 1;
+    const CrfWaveRole wr = crf_wave_role(TP, tid);                      // phase 2 and the softmax
     int b, part, parts;
     for (int wi = 0; xcd_work(wi, xcd, img0, nimg, b, part, parts); wi++) {
         const PostDesc im = imgs[b];
         const int K = im.K, Kp = im.Kp, K4 = Kp >> 2, ldt = Kp + 1;
         const int lo = L.idbase[b];
-        const int tiles_x = (im.W + TW - 1) / TW, tiles_y = (im.H + TH - 1) / TH, ntiles = tiles_x * tiles_y;
-        const int tfirst = (int)((long)ntiles * part / parts), tend = (int)((long)ntiles * (part + 1) / parts);
+        const CrfTiles tiles = crf_tiles(im, TW, TH);
+        const CrfShare sh = crf_share(tiles.ntiles, part, parts);
         const char* const Bb = reinterpret_cast<const char*>(base + im.qoff);
         const char* const Vb = reinterpret_cast<const char*>(val + im.voff[0]);
         f32x4* const O4 = reinterpret_cast<f32x4*>(out + im.qoff);
@@ -834,77 +750,49 @@ __global__ __launch_bounds__(256) void crf_term_update_kernel(const CrfLattice L
         int* const rec_o = reinterpret_cast<int*>(tile + ((tiled ? 1 : 0) + (MATRIX ? 1 : 0)) * TP * ldt);   // [TP][D1] lattice ids
         float* const rec_w = reinterpret_cast<float*>(rec_o + TP * D1);                // [TP][D1] barycentric weights
         float* const rec_n = rec_w + TP * D1;                                          // [TP] normaliser; then row maximum / sum
-        const int q256 = 256 / K4, r256 = 256 - q256 * K4;
-        const int pl0 = tid / K4, c0 = tid - pl0 * K4;
-        for (int tl = tfirst + slot; tl < tend; tl += bpx) {
-            const int ty = tl / tiles_x, tx = tl - ty * tiles_x;
-            const int x0 = tx * TW, y0 = ty * TH;
-            // slots of an edge tile that fall outside the image redo its last column / row and store nothing
-            auto pixel_of = [&](int pl) {
-                const int x = x0 + (pl & (TW - 1)), y = y0 + (pl >> tw_shift);
-                return (y < im.H ? y : im.H - 1) * im.W + (x < im.W ? x : im.W - 1);
-            };
-            auto inside = [&](int pl) { return x0 + (pl & (TW - 1)) < im.W && y0 + (pl >> tw_shift) < im.H; };
+        const CrfItemWalk it0(tid, K4);
+        for (int tl = sh.first + slot; tl < sh.end; tl += bpx) {
+            const CrfTileAt at = tiles.at(tl, TW, TH, tw_shift, im);
             for (int pl = tid; pl < TP; pl += 256) {                     // slice records, one pixel per thread
-                const size_t g = (size_t)im.pix0 + pixel_of(pl);
-#pragma unroll
-                for (int v = 0; v < D1; v++) {
-                    rec_o[pl * D1 + v] = L.offset[g * D1 + v] - lo;
-                    rec_w[pl * D1 + v] = L.bary[g * D1 + v];
-                }
+                const size_t g = (size_t)im.pix0 + at.pixel_of(pl);
+                crf_stage_record<D1>(L, lo, g, pl, rec_o, rec_w);
                 rec_n[pl] = norm[g];
             }
             __syncthreads();
-            {   // phase 1: the message chunk of every (pixel, chunk) item; without a matrix also its weight and the row's sum
-                int pl = pl0, c = c0;
-                for (int item = tid; item < TP * K4; item += 256) {
-                    const int px = pixel_of(pl);
-                    const uint32_t cofs = (uint32_t)c * 16u;
-                    f32x4 t = *reinterpret_cast<const f32x4*>(Bb + (__umul24((uint32_t)px, rowb) + cofs));
-                    if (first) t = f32x4{-t[0], -t[1], -t[2], -t[3]};
-                    f32x4 vv[D1];
+            // phase 1: the message chunk of every (pixel, chunk) item; without a matrix also its weight and the row's sum
+            for (CrfItemWalk it = it0; it.item < TP * K4; it.next()) {
+                const int pl = it.pl, c = it.c, px = at.pixel_of(pl);
+                const uint32_t cofs = (uint32_t)c * 16u;
+                f32x4 t = *reinterpret_cast<const f32x4*>(Bb + (__umul24((uint32_t)px, rowb) + cofs));
+                if (first) t = f32x4{-t[0], -t[1], -t[2], -t[3]};
+                f32x4 vv[D1];
+                crf_gather_rows<D1>(Vb, rec_o + pl * D1, rowb, cofs, vv);
+                const f32x4 o = crf_slice_rows<D1>(vv, rec_w + pl * D1, alpha);
+                const float nr = rec_n[pl];
+                f32x4 m;
 #pragma unroll
-                    for (int v = 0; v < D1; v++)
-                        vv[v] = *reinterpret_cast<const f32x4*>(Vb + (__umul24((uint32_t)rec_o[pl * D1 + v], rowb) + cofs));
-                    f32x4 o = {0.f, 0.f, 0.f, 0.f};
+                for (int i = 0; i < 4; i++) m[i] = __fmul_rn(o[i], nr);
+                if (!MATRIX) {
+                    f32x4 wl = {w, w, w, w};
+                    if (wvec) wl = *reinterpret_cast<const f32x4*>(wvec + 4 * c);
 #pragma unroll
-                    for (int v = 0; v < D1; v++) {
-                        const float wv = rec_w[pl * D1 + v];
+                    for (int i = 0; i < 4; i++) t[i] = __fadd_rn(t[i], __fmul_rn(wl[i], m[i]));
+                }
+                if (tiled) {
 #pragma unroll
-                        for (int i = 0; i < 4; i++) o[i] = __fadd_rn(o[i], __fmul_rn(__fmul_rn(wv, vv[v][i]), alpha));
+                    for (int i = 0; i < 4; i++) {
+                        tile[pl * ldt + 4 * c + i] = t[i];
+                        if (MATRIX) msg[pl * ldt + 4 * c + i] = m[i];
                     }
-                    const float nr = rec_n[pl];
-                    f32x4 m;
-#pragma unroll
-                    for (int i = 0; i < 4; i++) m[i] = __fmul_rn(o[i], nr);
-                    if (!MATRIX) {
-                        f32x4 wl = {w, w, w, w};
-                        if (wvec) wl = *reinterpret_cast<const f32x4*>(wvec + 4 * c);
-#pragma unroll
-                        for (int i = 0; i < 4; i++) t[i] = __fadd_rn(t[i], __fmul_rn(wl[i], m[i]));
-                    }
-                    if (tiled) {
-#pragma unroll
-                        for (int i = 0; i < 4; i++) {
-                            tile[pl * ldt + 4 * c + i] = t[i];
-                            if (MATRIX) msg[pl * ldt + 4 * c + i] = m[i];
-                        }
-                    } else if (inside(pl)) {
-                        O4[(size_t)px * K4 + c] = t;
-                    }
-                    pl += q256;
-                    c += r256;
-                    if (c >= K4) {
-                        c -= K4;
-                        pl++;
-                    }
+                } else if (at.inside(pl)) {
+                    O4[(size_t)px * K4 + c] = t;
                 }
             }
             __syncthreads();
             if (!tiled) continue;
             if (MATRIX) {   // phase 2: lane = pixel, CRF_CL labels per pass over k; M rows through scalar loads (wave-uniform)
-                const float* const x = msg + pxc * ldt;
-                for (int l0 = lg * CRF_CL; l0 < K; l0 += NG * CRF_CL) {
+                const float* const x = msg + wr.pxc * ldt;
+                for (int l0 = wr.lg * CRF_CL; l0 < K; l0 += wr.NG * CRF_CL) {
                     float a[CRF_CL];
 #pragma unroll
                     for (int i = 0; i < CRF_CL; i++) a[i] = 0.f;
@@ -918,8 +806,8 @@ __global__ __launch_bounds__(256) void crf_term_update_kernel(const CrfLattice L
                     }
 #pragma unroll
                     for (int i = 0; i < CRF_CL; i++) {
-                        if (act && l0 + i < K) {
-                            float* const t = tile + px2 * ldt + l0 + i;
+                        if (wr.act && l0 + i < K) {
+                            float* const t = tile + wr.px2 * ldt + l0 + i;
                             *t = __fadd_rn(*t, a[i]);
                         }
                     }
@@ -927,8 +815,9 @@ __global__ __launch_bounds__(256) void crf_term_update_kernel(const CrfLattice L
                 __syncthreads();
             }
             if (last) {
-                // softmax, label, pad: crf_update_compat_kernel's steps -- maximum (a NaN wins) and sum (k ascending) by one
-                // thread per row, exponentials and divisions by the lanes of phase 2
+                // softmax, label, pad: crf_update_compat_kernel's steps, element by element -- maximum (a NaN wins) and sum
+                // (k ascending) by one thread per row, exponentials and divisions by the lanes of phase 2; row maximum and sum
+                // pass through the spent normaliser slots
                 if (tid < TP) {
                     const float* row = tile + tid * ldt;
                     float mx = row[0];
@@ -939,10 +828,10 @@ __global__ __launch_bounds__(256) void crf_term_update_kernel(const CrfLattice L
                     rec_n[tid] = mx;
                 }
                 __syncthreads();
-                if (act) {
-                    float* row = tile + px2 * ldt;
-                    const float mx = rec_n[px2];
-                    for (int k = lg; k < K; k += NG) row[k] = pnp_expf(__fsub_rn(row[k], mx));
+                if (wr.act) {
+                    float* row = tile + wr.px2 * ldt;
+                    const float mx = rec_n[wr.px2];
+                    for (int k = wr.lg; k < K; k += wr.NG) row[k] = pnp_expf(__fsub_rn(row[k], mx));
                 }
                 __syncthreads();
                 if (tid < TP) {
@@ -952,48 +841,21 @@ __global__ __launch_bounds__(256) void crf_term_update_kernel(const CrfLattice L
                     rec_n[tid] = sm;
                 }
                 __syncthreads();
-                if (act) {
-                    float* row = tile + px2 * ldt;
-                    const float sm = rec_n[px2];
-                    for (int k = lg; k < K; k += NG) row[k] = __fdiv_rn(row[k], sm);
+                if (wr.act) {
+                    float* row = tile + wr.px2 * ldt;
+                    const float sm = rec_n[wr.px2];
+                    for (int k = wr.lg; k < K; k += wr.NG) row[k] = __fdiv_rn(row[k], sm);
                 }
                 __syncthreads();
                 if (tid < TP) {
-                    const int px = tid;
-                    float* row = tile + px * ldt;
-                    if (lout.lab[0]) {                                   // first maximum, NaN counts as maximum (np.argmax)
-                        int best = 0;
-                        float bv = row[0];
-                        for (int k = 1; k < K; k++) {
-                            const float v = row[k];
-                            if (bv == bv && (v > bv || v != v)) {
-                                best = k;
-                                bv = v;
-                            }
-                        }
-                        if (inside(px)) lout.lab[0][lout.label_off[b] + pixel_of(px)] = (uint8_t)lout.lut[b * lout.lut_stride + best];
-                    }
+                    float* row = tile + tid * ldt;
+                    crf_store_label(lout, 0, b, at, tid, row, K);
                     for (int k = K; k < Kp; k++) row[k] = 0.f;           // pad floats stay zero
                 }
                 __syncthreads();
             }
-            {
-                int pl = pl0, c = c0;
-                for (int item = tid; item < TP * K4; item += 256) {
-                    if (inside(pl)) {
-                        const float* r = tile + pl * ldt + 4 * c;
-                        const f32x4 v = {r[0], r[1], r[2], r[3]};
-                        if (last) st_stream(O4 + (size_t)pixel_of(pl) * K4 + c, v);
-                        else O4[(size_t)pixel_of(pl) * K4 + c] = v;
-                    }
-                    pl += q256;
-                    c += r256;
-                    if (c >= K4) {
-                        c -= K4;
-                        pl++;
-                    }
-                }
-            }
+            if (last) crf_store_tile<true>(tile, ldt, at, it0, TP, O4);
+            else crf_store_tile<false>(tile, ldt, at, it0, TP, O4);
             __syncthreads();
         }
     }
