@@ -448,12 +448,48 @@ typedef struct pnp_jpeg_segment {
     int32_t raw_len;            /* entropy-coded bytes of the interval, markers excluded */
     int32_t clean_cap;          /* bytes reserved at clean_off, >= raw_len + 32 */
     int32_t sub_bits;           /* sub-sequence length in bits: a multiple of 32, >= 8 * raw_len / 1024 */
-    int32_t pad[2];
+    int32_t scan;               /* pnp_jpeg_decode_scans only: index of the segment's scan in d_scans */
+    int32_t pad;
 } pnp_jpeg_segment;
 int pnp_jpeg_decode(const uint8_t* d_data, const pnp_jpeg_image* d_images, const pnp_jpeg_tables* d_tables,
                     const pnp_jpeg_segment* d_segments, int32_t n_images, int32_t n_segments, uint8_t* d_clean, int32_t* d_seg_bits,
                     int16_t* d_coef, int64_t coef_elems, uint8_t* d_planes, uint8_t* d_rgb, int32_t max_blocks_per_image,
                     int32_t max_pixels_per_image, int32_t* d_err, void* stream);
+
+/* The same decode for any mix of baseline and PROGRESSIVE (SOF2, Huffman, 8-bit, same colour spaces) files, scan by scan.
+ * The host (pnp_ovss/jpeg.py pack_scans) records every scan of every file -- a baseline file is one scan of kind 0 -- and has
+ * checked the progression (T.81 G.1.1.1.1: every coefficient of every component ends at Al = 0).  One restart interval of one
+ * scan is one segment; `scan` names its pnp_jpeg_scan, mcu0 / nmcu count that scan's units: MCUs of the frame in an
+ * interleaved scan, blocks of the component's own ceil(Xc / 8) x ceil(Yc / 8) grid (bw x bh) in a one-component scan.
+ * d_segments holds the n_base_segments segments of baseline files first, then the progressive ones ordered by (scan ordinal,
+ * kind): h_groups, a HOST array of n_groups x 4 int32 (first segment, segments, kind, ordinal) in that order, names the
+ * contiguous ranges, one launch each, so every file's scans run in file order.  Order of work: zero the coefficients, un-stuff
+ * all segments, baseline entropy decode, the groups, inverse DCT + colour over all images.  The four progressive kinds restate
+ * T.81 G.1.2 (csrc/jpeg_prog.hip); the Huffman ones use the sub-sequence scheme above.  An image's `tab` entry holds its
+ * quantisation tables (tq indexes it), a scan's `tab` entry the Huffman tables in force at its SOS.
+ * Workspaces as pnp_jpeg_decode, plus d_hist: coef_elems / 64 uint64, one history mask per coefficient block (AC refinement).
+ * d_rounds (device, n_segments ints, may be NULL): synchronisation rounds each progressive segment took.  h_group_ms (host,
+ * n_groups floats, may be NULL): profiling -- every group's launch is timed between two events and the call synchronises.
+ * *d_err is set to 1 on an undefined code, a size above 1 in a refinement symbol, an index past Se, an end-of-band run past
+ * the scan's blocks or a stream that ends early.  Stateless; PNP_ERR_ARG for inconsistent arguments before any HIP call. */
+typedef struct pnp_jpeg_scan {
+    int32_t image;
+    int32_t kind;               /* 0 sequential, 1 DC first, 2 DC refinement, 3 AC first, 4 AC refinement */
+    int32_t ordinal;            /* position of the scan in its file */
+    int32_t ncomp, comp[3];     /* the scan's components, indices into the frame, in frame order */
+    int32_t td[3], ta[3];       /* per scan component: slot (0 / 1) of its DC / AC Huffman table in d_tables[tab] */
+    int32_t ss, se, ah, al;     /* spectral selection and successive approximation of the SOS header */
+    int32_t tab;
+    int32_t bw, bh;             /* the grid the scan's units are counted on */
+    int32_t nunits;             /* bw * bh */
+    int32_t pad[3];
+} pnp_jpeg_scan;
+int pnp_jpeg_decode_scans(const uint8_t* d_data, const pnp_jpeg_image* d_images, const pnp_jpeg_tables* d_tables,
+                          const pnp_jpeg_scan* d_scans, const pnp_jpeg_segment* d_segments, int32_t n_images, int32_t n_scans,
+                          int32_t n_segments, int32_t n_base_segments, const int32_t* h_groups, int32_t n_groups, uint8_t* d_clean,
+                          int32_t* d_seg_bits, int16_t* d_coef, int64_t coef_elems, uint64_t* d_hist, uint8_t* d_planes,
+                          uint8_t* d_rgb, int32_t max_blocks_per_image, int32_t max_pixels_per_image, int32_t* d_rounds,
+                          float* h_group_ms, int32_t* d_err, void* stream);
 
 /* ---- output side: what the reference's Draw_Segmentation_map writes (PnP_OVSS_0514_updated_segmentation_coco.py:966-983) ----
  * Colour overlay of label maps on their images: skimage.color.label2rgb(kind="overlay", alpha, bg_label=0, image_alpha=1,

@@ -79,7 +79,9 @@ def get_args_parser():
     p.add_argument("--crf_chunk", default=0, type=int, help="images per DenseCRF launch group (0 = the whole batch)")
     p.add_argument("--checkpoint", default=None, help="BLIP ITM-large checkpoint (.pth); default: seeded synthetic weights")
     p.add_argument("--vocab", default=None, help="bert-base-uncased vocab.txt")
-    p.add_argument("--device_jpeg", default=1, type=int, help="1: decode JPEG files on the GPU (baseline files; others fall back to Pillow)")
+    p.add_argument("--device_jpeg", default=1, type=int, help="1: decode JPEG files on the GPU (baseline files, progressive ones with --device_progressive 1; others fall back to Pillow)")
+    p.add_argument("--device_progressive", default=None, type=int,
+                   help="progressive JPEG files: 1 on the GPU scan by scan, 0 with Pillow on the host (default: datasets.DEVICE_PROGRESSIVE)")
     p.add_argument("--pipelines", default=1, type=int,
                    help="batches in flight on this GPU: P model replicas, each with its own HIP stream and host thread, take the "
                         "batches as they come (the text side and kernel tails of one batch run beside another batch's dense "

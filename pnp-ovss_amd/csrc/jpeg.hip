@@ -455,4 +455,24 @@ int jpeg_decode(const uint8_t* d_data, const JpegImage* d_imgs, const JpegTables
     return hipGetLastError() == hipSuccess ? PNP_OK : PNP_ERR_HIP;
 }
 
+// The launches above one by one, for the scan-by-scan decoder (jpeg_prog.hip), which runs its own entropy kernels between them.
+void jpeg_launch_unstuff(const uint8_t* d_data, const JpegImage* d_imgs, const JpegSegment* d_segs, int n_segments, uint8_t* d_clean,
+                         int* d_seg_bits, hipStream_t s) {
+    hipLaunchKernelGGL(jpeg_unstuff_kernel, dim3(n_segments), dim3(256), 0, s, d_data, d_imgs, d_segs, d_clean, d_seg_bits);
+}
+
+void jpeg_launch_huffman(const uint8_t* d_clean, const JpegImage* d_imgs, const JpegTables* d_tabs, const JpegSegment* d_segs,
+                         int n_segments, const int* d_seg_bits, int16_t* d_coef, int* d_err, hipStream_t s) {
+    hipLaunchKernelGGL(jpeg_huffman_kernel, dim3(n_segments), dim3(JPEG_T), 0, s, d_clean, d_imgs, d_tabs, d_segs, d_seg_bits, d_coef, d_err);
+}
+
+void jpeg_launch_pixels(const JpegImage* d_imgs, const JpegTables* d_tabs, int n_images, const int16_t* d_coef, uint8_t* d_planes,
+                        uint8_t* d_rgb, int max_blocks, int max_pixels, hipStream_t s) {
+    const int nb = (max_blocks + 255) / 256;
+    hipLaunchKernelGGL(jpeg_idct_kernel, dim3(nb < 1 ? 1 : nb, n_images), dim3(256), 0, s, d_imgs, d_tabs, d_coef, d_planes);
+    int np = (max_pixels + 255) / 256;
+    np = np > 1024 ? 1024 : (np < 1 ? 1 : np);
+    hipLaunchKernelGGL(jpeg_color_kernel, dim3(np, n_images), dim3(256), 0, s, d_imgs, d_planes, d_rgb);
+}
+
 }  // namespace pnp

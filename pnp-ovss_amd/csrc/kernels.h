@@ -139,11 +139,37 @@ struct JpegSegment {
     int32_t raw_len;        // entropy-coded bytes of the interval (markers excluded)
     int32_t clean_cap;      // bytes reserved at clean_off: >= raw_len + 32
     int32_t sub_bits;       // sub-sequence length of the parallel decode: a multiple of 32, >= 8 * raw_len / 1024
-    int32_t pad[2];
+    int32_t scan;           // jpeg_decode_scans: index of the segment's JpegScan; mcu0 / nmcu then count that scan's units
+    int32_t pad;
 };
 int jpeg_decode(const uint8_t* d_data, const JpegImage* d_imgs, const JpegTables* d_tabs, const JpegSegment* d_segs, int n_images,
                 int n_segments, uint8_t* d_clean, int* d_seg_bits, int16_t* d_coef, size_t coef_elems, uint8_t* d_planes, uint8_t* d_rgb,
                 int max_blocks, int max_pixels, int* d_err, hipStream_t s);
+// the launches of jpeg_decode one stage at a time (un-stuff; baseline entropy decode; inverse DCT + colour)
+void jpeg_launch_unstuff(const uint8_t* d_data, const JpegImage* d_imgs, const JpegSegment* d_segs, int n_segments, uint8_t* d_clean,
+                         int* d_seg_bits, hipStream_t s);
+void jpeg_launch_huffman(const uint8_t* d_clean, const JpegImage* d_imgs, const JpegTables* d_tabs, const JpegSegment* d_segs,
+                         int n_segments, const int* d_seg_bits, int16_t* d_coef, int* d_err, hipStream_t s);
+void jpeg_launch_pixels(const JpegImage* d_imgs, const JpegTables* d_tabs, int n_images, const int16_t* d_coef, uint8_t* d_planes,
+                        uint8_t* d_rgb, int max_blocks, int max_pixels, hipStream_t s);
+
+// jpeg_prog.hip -- progressive files scan by scan (pnp_ovss/jpeg.py pack_scans; see include/pnp_hip.h)
+struct JpegScan {
+    int32_t image;
+    int32_t kind;           // 0 sequential (a baseline file's one scan), 1 DC first, 2 DC refinement, 3 AC first, 4 AC refinement
+    int32_t ordinal;        // position of the scan in its file
+    int32_t ncomp, comp[3]; // the scan's components: indices into the frame
+    int32_t td[3], ta[3];   // per scan component: slot (0 / 1) of its DC / AC table in JpegTables `tab`
+    int32_t ss, se, ah, al;
+    int32_t tab;            // the Huffman tables in force at this SOS
+    int32_t bw, bh;         // grid of the scan's units: MCUs when interleaved, the component's own blocks for one component
+    int32_t nunits;
+    int32_t pad[3];
+};
+int jpeg_decode_scans(const uint8_t* d_data, const JpegImage* d_imgs, const JpegTables* d_tabs, const JpegScan* d_scans,
+                      const JpegSegment* d_segs, int n_images, int n_segments, int n_base_segments, const int32_t* h_groups, int n_groups,
+                      uint8_t* d_clean, int* d_seg_bits, int16_t* d_coef, size_t coef_elems, uint64_t* d_hist, uint8_t* d_planes,
+                      uint8_t* d_rgb, int max_blocks, int max_pixels, int* d_rounds, float* h_group_ms, int* d_err, hipStream_t s);
 
 // sort.hip: stable LSD radix sort of (u64 key, u32 value) pairs and int32 prefix sum (the lattice build's device-wide primitives)
 size_t sort_temp_bytes(size_t n);

@@ -238,6 +238,36 @@ extern "C" int pnp_jpeg_decode(const uint8_t* d_data, const pnp_jpeg_image* d_im
                        (size_t)coef_elems, d_planes, d_rgb, max_blocks_per_image, max_pixels_per_image, d_err, (hipStream_t)stream);
 }
 
+extern "C" int pnp_jpeg_decode_scans(const uint8_t* d_data, const pnp_jpeg_image* d_images, const pnp_jpeg_tables* d_tables,
+                                     const pnp_jpeg_scan* d_scans, const pnp_jpeg_segment* d_segments, int32_t n_images,
+                                     int32_t n_scans, int32_t n_segments, int32_t n_base_segments, const int32_t* h_groups,
+                                     int32_t n_groups, uint8_t* d_clean, int32_t* d_seg_bits, int16_t* d_coef, int64_t coef_elems,
+                                     uint64_t* d_hist, uint8_t* d_planes, uint8_t* d_rgb, int32_t max_blocks_per_image,
+                                     int32_t max_pixels_per_image, int32_t* d_rounds, float* h_group_ms, int32_t* d_err, void* stream) {
+    if (!d_data || !d_images || !d_tables || !d_scans || !d_segments || !d_clean || !d_seg_bits || !d_coef || !d_planes || !d_rgb ||
+        !d_err || coef_elems <= 0 || coef_elems % 64)
+        return PNP_ERR_ARG;
+    if (n_images <= 0 || n_scans < n_images || n_segments < n_scans || n_base_segments < 0 || n_base_segments > n_segments ||
+        n_groups < 0 || (n_groups > 0 && !h_groups))
+        return PNP_ERR_ARG;
+    int next = n_base_segments;                           // the groups tile the progressive segments, in order
+    bool refine = false;
+    for (int g = 0; g < n_groups; g++) {
+        const int32_t* q = h_groups + 4 * g;
+        if (q[0] != next || q[1] <= 0 || q[1] > n_segments - next || q[2] < 1 || q[2] > 4 || q[3] < 0) return PNP_ERR_ARG;
+        if (g > 0 && (q[3] < q[-1] || (q[3] == q[-1] && q[2] <= q[-2]))) return PNP_ERR_ARG;
+        refine = refine || q[2] == 4;
+        next += q[1];
+    }
+    if (next != n_segments || (refine && !d_hist)) return PNP_ERR_ARG;
+    static_assert(sizeof(pnp_jpeg_scan) == sizeof(JpegScan) && sizeof(pnp_jpeg_segment) == sizeof(JpegSegment),
+                  "JPEG descriptor layouts are part of the ABI");
+    return jpeg_decode_scans(d_data, reinterpret_cast<const JpegImage*>(d_images), reinterpret_cast<const JpegTables*>(d_tables),
+                             reinterpret_cast<const JpegScan*>(d_scans), reinterpret_cast<const JpegSegment*>(d_segments), n_images,
+                             n_segments, n_base_segments, h_groups, n_groups, d_clean, d_seg_bits, d_coef, (size_t)coef_elems, d_hist,
+                             d_planes, d_rgb, max_blocks_per_image, max_pixels_per_image, d_rounds, h_group_ms, d_err, (hipStream_t)stream);
+}
+
 // operator forms of the lattice build's sort / scan (tests); the scratch is allocated per call
 extern "C" int pnp_op_sort_pairs(uint64_t* d_keys_in, uint64_t* d_keys_out, uint32_t* d_vals_in, uint32_t* d_vals_out, int64_t n,
                                  int32_t begin_bit, int32_t end_bit, const size_t* h_seg_off, int32_t n_seg, void* stream) {

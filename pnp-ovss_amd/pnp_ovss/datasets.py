@@ -2,8 +2,8 @@
 deliver to the driver (`img0`, `img_id`, original RGB for the CRF, ground-truth label map), sharded
 across ranks like `DataLoader(..., sampler=DistributedSampler(dataset))` (Load_datasets.py:15-26).
 
-JPEG files are decoded on the device per batch (hip.jpeg_decode_batch -> csrc/jpeg.hip: Pillow-exact baseline decoder;
-`--device_jpeg 0` or a file the decoder does not cover -> Pillow on the host); PNG ground truth stays on the host.
+JPEG files are decoded on the device per batch (hip.jpeg_decode_batch -> csrc/jpeg.hip, csrc/jpeg_prog.hip: Pillow-exact
+baseline and progressive decoders; `--device_jpeg 0` or a file the decoder does not cover -> Pillow on the host); PNG ground truth stays on the host.
   synthetic  seeded images + one-word-piece-per-class captions (no files needed; bench / CI)
   voc        Dataset.py:349-445 (bicubic resize to img_size, CLIP mean/std: on device, bit-identical to the
              Pillow / torchvision host path -- pnp_preprocess_images), PnP.py:901-955 (GT / RGB)
@@ -59,9 +59,12 @@ class _Base:
 
     resample = ("bicubic", synth.CLIP_MEAN, synth.CLIP_STD)      # Dataset.py:434-443
 
-    def _decode_on_device(self, items):
+    def _decode_on_device(self, items, device_progressive=None):
         """Items whose image is still a JPEG byte string are decoded together on the GPU; a file the device decoder does
-        not cover (progressive, arithmetic, CMYK) is decoded by Pillow on the host, loudly."""
+        not cover (arithmetic coding, CMYK, 12-bit, an incomplete progressive file or one of more than jpeg.MAX_SCANS scans)
+        is decoded by Pillow on the host, loudly.  Progressive files go to the device (scan by scan, hip.jpeg_decode_batch)
+        when device_progressive -- default: args.device_progressive, else DEVICE_PROGRESSIVE -- is set, else to Pillow, loudly
+        as well."""
         todo = [k for k, it in enumerate(items) if isinstance(it[2], (bytes, bytearray))]
         if not todo:
             return items
@@ -76,10 +79,17 @@ class _Base:
             warnings.warn(f"image {items[k][1]}: {why}: decoded on the host")
             items[k][2] = np.asarray(Image.open(io.BytesIO(items[k][2])).convert("RGB"))
 
+        if device_progressive is None:
+            device_progressive = getattr(getattr(self, "args", None), "device_progressive", None)
+        if device_progressive is None:
+            device_progressive = DEVICE_PROGRESSIVE
         for k in todo:
             try:
                 from . import jpeg as J
-                J.parse(items[k][2])
+                if device_progressive and J.is_progressive(items[k][2]):
+                    J.parse_progressive(items[k][2])
+                else:
+                    J.parse(items[k][2])
                 good.append(k)
             except UnsupportedJpeg as exc:
                 on_host(k, exc)
@@ -135,6 +145,13 @@ class _Base:
                 batch["ready"] = torch.cuda.Event()
                 batch["ready"].record()
             yield batch
+
+
+# Where progressive JPEG files are decoded when neither the caller nor args.device_progressive says: with Pillow on the host.
+# Measured (profiles/jpeg_progressive.json, tools/jpeg_bench.py --progressive): a batch of 35 progressive 375 x 500 files takes
+# the device 109 ms end to end against 47 ms for Pillow on one host thread -- 101 ms of it in the AC refinement scans, whose
+# sub-sequences become exact one per round -- so the device path is opt-in (--device_progressive 1) until that kernel is tuned.
+DEVICE_PROGRESSIVE = False
 
 
 def wait_ready(batch):

@@ -115,6 +115,7 @@ def load_library():
         "pnp_op_layernorm": (i32, [vp, vp, vp, f32, i32, i32, vp, vp]),
         "pnp_op_cast": (i32, [i32, vp, vp, i64, vp]),
         "pnp_jpeg_decode": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, vp, i64, vp, vp, i32, i32, vp, vp]),
+        "pnp_jpeg_decode_scans": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, i64, vp, vp, vp, i32, i32, vp, vp, vp, vp]),
         "pnp_overlay_labels": (i32, [vp, vp, vp, i32, vp, C.c_double, vp, vp]),
         "pnp_jpeg_encode": (i32, [vp, vp, i32, vp, vp, vp, vp, vp, i64, C.POINTER(i64), vp]),
         "pnp_op_split": (i32, [vp, vp, vp, i64, vp]),
@@ -178,7 +179,7 @@ EXPORTED = ["pnp_create", "pnp_create_shared", "pnp_destroy", "pnp_last_error", 
             "pnp_streamk_status", "pnp_text_forward_text", "pnp_project_normalize", "pnp_itc_similarity",
             "pnp_op_text_self_attn", "pnp_op_text_self_attn_bwd", "pnp_op_layernorm_ex", "pnp_op_layernorm_bwd",
             "pnp_op_text_embed", "pnp_op_itm_head", "pnp_op_itm_grad_seed", "pnp_op_patchify", "pnp_op_cls_rows",
-            "pnp_op_gemm_args", "pnp_op_gemm_plan", "pnp_overlay_labels", "pnp_jpeg_encode",
+            "pnp_op_gemm_args", "pnp_op_gemm_plan", "pnp_overlay_labels", "pnp_jpeg_encode", "pnp_jpeg_decode_scans",
             "pnp_crf_create", "pnp_crf_destroy", "pnp_crf_allocated_bytes", "pnp_crf_last_error", "pnp_crf_set_batch",
             "pnp_crf_infer", "pnp_crf_set_batch_aniso", "pnp_crf_set_compat", "pnp_crf_start", "pnp_crf_step", "pnp_crf_read",
             "pnp_crf_kl", "pnp_crf_create_terms", "pnp_crf_set_batch_terms", "pnp_crf_set_term_compat", "pnp_crf_infer_terms",
@@ -300,14 +301,72 @@ def preprocess_images(images, S, mean=(0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0), devi
     return out
 
 
+def jpeg_scans_upload(files, device=None, profile=False):
+    """jpeg.pack_scans(files) with its arrays and the workspaces of pnp_jpeg_decode_scans on the device -> the context
+    jpeg_scans_run takes.  profile=True adds what the measurements read: the synchronisation rounds per segment and the kernel
+    time per launch group (at the price of one synchronisation per group)."""
+    if not torch.cuda.is_available():
+        raise RuntimeError("pnp_ovss.hip.jpeg_scans_upload needs a HIP device (no CPU fallback)")
+    from . import jpeg as J
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    data, imgs, tabs, scans, segs, groups, sizes, tot = J.pack_scans(files)
+
+    def up(buf):
+        return torch.frombuffer(bytearray(bytes(buf)), dtype=torch.uint8).to(dev)
+    ctx = dict(n=len(files), scans=scans, segs=segs, groups=np.ascontiguousarray(groups, dtype=np.int32), sizes=sizes, tot=tot, dev=dev,
+               d_data=torch.from_numpy(data).to(dev), d_imgs=up(imgs), d_tabs=up(tabs), d_scans=up(scans), d_segs=up(segs),
+               d_clean=torch.empty(tot["clean_bytes"], dtype=torch.uint8, device=dev),
+               d_bits=torch.empty(len(segs), dtype=torch.int32, device=dev),
+               d_coef=torch.empty(tot["coef_elems"], dtype=torch.int16, device=dev),
+               d_hist=torch.empty(tot["coef_elems"] // 64, dtype=torch.int64, device=dev),
+               d_planes=torch.empty(tot["plane_bytes"], dtype=torch.uint8, device=dev),
+               d_rgb=torch.empty(tot["rgb_bytes"], dtype=torch.uint8, device=dev),
+               d_err=torch.zeros(1, dtype=torch.int32, device=dev))
+    if profile:
+        ctx.update(d_rounds=torch.zeros(len(segs), dtype=torch.int32, device=dev), group_ms=np.zeros(len(groups), dtype=np.float32))
+    return ctx
+
+
+def jpeg_scans_run(ctx):
+    """One pnp_jpeg_decode_scans call on an uploaded batch, on the current stream; d_err is left for the caller to read."""
+    lib = load_library()
+    tot, prof = ctx["tot"], "d_rounds" in ctx
+    r = lib.pnp_jpeg_decode_scans(ctx["d_data"].data_ptr(), ctx["d_imgs"].data_ptr(), ctx["d_tabs"].data_ptr(), ctx["d_scans"].data_ptr(),
+                                  ctx["d_segs"].data_ptr(), ctx["n"], len(ctx["scans"]), len(ctx["segs"]), tot["base_segments"],
+                                  ctx["groups"].ctypes.data, len(ctx["groups"]), ctx["d_clean"].data_ptr(), ctx["d_bits"].data_ptr(),
+                                  ctx["d_coef"].data_ptr(), tot["coef_elems"], ctx["d_hist"].data_ptr(), ctx["d_planes"].data_ptr(),
+                                  ctx["d_rgb"].data_ptr(), tot["max_blocks"], tot["max_pixels"],
+                                  ctx["d_rounds"].data_ptr() if prof else None, ctx["group_ms"].ctypes.data if prof else None,
+                                  ctx["d_err"].data_ptr(), torch.cuda.current_stream().cuda_stream)
+    if r != 0:
+        raise RuntimeError(f"pnp_jpeg_decode_scans failed ({r})")
+
+
+def jpeg_decode_scans(files, device=None):
+    """pnp_jpeg_decode_scans for any mix of baseline and progressive files -> list of (H, W, 3) uint8 views of one concatenated
+    device buffer in batch order."""
+    ctx = jpeg_scans_upload(files, device)
+    jpeg_scans_run(ctx)
+    if int(ctx["d_err"].item()):
+        raise RuntimeError("pnp_jpeg_decode_scans: corrupt entropy-coded data")
+    out, o = [], 0
+    for h, w in ctx["sizes"]:
+        out.append(ctx["d_rgb"][o:o + h * w * 3].view(h, w, 3))
+        o += h * w * 3
+    return out
+
+
 def jpeg_decode_batch(files, device=None):
-    """`Image.open(f).convert('RGB')` for a batch of baseline JPEG byte strings, on the device (pnp_jpeg_decode): returns a
-    list of uint8 device tensors (H, W, 3), views of one concatenated buffer in batch order -- the layout the resize
-    kernel and the CRF read.  Raises pnp_ovss.jpeg.UnsupportedJpeg for progressive / arithmetic / CMYK files (the caller
-    decodes those with Pillow) and RuntimeError for a corrupt stream."""
+    """`Image.open(f).convert('RGB')` for a batch of JPEG byte strings, on the device: returns a list of uint8 device tensors
+    (H, W, 3), views of one concatenated buffer in batch order -- the layout the resize kernel and the CRF read.  A batch of
+    baseline files goes through pnp_jpeg_decode; as soon as one file is progressive the whole batch goes scan by scan through
+    pnp_jpeg_decode_scans.  Raises pnp_ovss.jpeg.UnsupportedJpeg for what neither parser covers (arithmetic coding, CMYK,
+    12-bit, incomplete progressive files: the caller decodes those with Pillow) and RuntimeError for a corrupt stream."""
     if not torch.cuda.is_available():
         raise RuntimeError("pnp_ovss.hip.jpeg_decode_batch needs a HIP device (no CPU fallback)")
     from . import jpeg as J
+    if any(J.is_progressive(f) for f in files):
+        return jpeg_decode_scans(files, device)
     lib = load_library()
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     data, imgs, tabs, segs, sizes, tot = J.pack_batch(files)

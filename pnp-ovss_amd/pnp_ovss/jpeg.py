@@ -2,9 +2,11 @@
 `Image.open(path).convert('RGB')` (Dataset.py:349-445, PnP_OVSS_0514_updated_segmentation.py:929-955); here the host only
 walks the JPEG markers (byte work: frame geometry, quantisation and Huffman tables, restart intervals) and hands the
 entropy-coded bytes plus descriptors to the GPU, which does the Huffman decode, inverse DCT, chroma upsampling and colour
-conversion for the whole batch.  Baseline sequential files (grayscale / YCbCr 4:4:4, 4:2:2, 4:2:0) are supported --
-what VOC / COCO / ADE20K ship; anything else (progressive, arithmetic, CMYK) raises `UnsupportedJpeg` and the dataset
-decodes that one file with Pillow.
+conversion for the whole batch.  Baseline sequential files (grayscale / YCbCr 4:4:4, 4:2:2, 4:2:0) -- what VOC / COCO /
+ADE20K ship -- go through `parse` / `pack_batch`; progressive files of the same colour spaces -- what web exporters and
+many phones write -- through `parse_progressive` / `pack_scans` (csrc/jpeg_prog.hip, `pnp_jpeg_decode_scans`).  Anything
+else (arithmetic coding, CMYK, 12-bit, an incomplete progressive file) raises `UnsupportedJpeg` and the dataset decodes
+that one file with Pillow.
 
 Below it, the host half of the device ENCODER (csrc/jpeg_enc.hip, `pnp_jpeg_encode`): libjpeg's quality-scaled quantisation
 tables and the markers around the entropy-coded scan the GPU writes, byte for byte those of Pillow's `save(..., "JPEG")`.
@@ -34,8 +36,20 @@ class JpegTables(C.Structure):
 
 class JpegSegment(C.Structure):
     _fields_ = [("byte_off", C.c_int64), ("clean_off", C.c_int64)] + \
-               [(n, C.c_int32) for n in ("image", "mcu0", "nmcu", "raw_len", "clean_cap", "sub_bits")] + [("pad", C.c_int32 * 2)]
+               [(n, C.c_int32) for n in ("image", "mcu0", "nmcu", "raw_len", "clean_cap", "sub_bits", "scan", "pad")]
 
+
+class JpegScan(C.Structure):
+    """One scan of one image (csrc/kernels.h JpegScan).  kind: one of SCAN_KINDS.  comp / td / ta: the scan's components
+    (indices into the frame) and the slot (0 / 1) of each one's DC / AC table in the JpegTables entry `tab`, the snapshot of
+    the Huffman tables in force at this SOS.  bw x bh: the grid the scan's units are counted on -- MCUs of the frame for an
+    interleaved scan, the component's own ceil(Xc / 8) x ceil(Yc / 8) blocks for a one-component scan."""
+    _fields_ = [(n, C.c_int32) for n in ("image", "kind", "ordinal", "ncomp")] + [(n, C.c_int32 * 3) for n in ("comp", "td", "ta")] + \
+               [(n, C.c_int32) for n in ("ss", "se", "ah", "al", "tab", "bw", "bh", "nunits")] + [("pad", C.c_int32 * 3)]
+
+
+SCAN_KINDS = ("sequential", "dc_first", "dc_refine", "ac_first", "ac_refine")
+MAX_SCANS = 64          # scans per progressive file; a file with more goes to Pillow
 
 SUBSEQUENCES = 1024     # threads per restart segment of the device decoder (csrc/jpeg.hip JPEG_T)
 
@@ -237,6 +251,328 @@ def pack_batch(files):
     data = np.concatenate(chunks) if chunks else np.zeros(16, dtype=np.uint8)
     return data, imgs, tabs, sg, sizes, dict(coef_elems=coef, plane_bytes=plane, rgb_bytes=rgb, clean_bytes=clean, max_blocks=max_blocks,
                                              max_pixels=max_pixels)
+
+
+# ---------------------------------------------------------------------------------------------------------- progressive files
+# SOF2 (csrc/jpeg_prog.hip, `pnp_jpeg_decode_scans`): the coefficients arrive in several scans (T.81 Annex G), each a band
+# Ss..Se of the zig-zag sequence of some components at some bit precision.  The host records every scan and checks the
+# progression (T.81 G.1.1.1.1); the device decodes them in file order into the same coefficient buffers as a baseline file.
+def parse_progressive(data: bytes):
+    """Marker walk of one SOF2 file (8-bit, Huffman, greyscale or YCbCr 4:4:4 / 4:2:2 / 4:2:0) -> dict(H, W, comps[{id, h,
+    v, tq, q}], scans[{comps, td, ta, Ss, Se, Ah, Al, kind, start, end, dri, ht}]): per scan the component indices, the
+    table SLOTS (0 / 1) of each component, the entropy-coded byte range, the restart interval and the snapshot
+    {(class, slot): (counts, symbols)} of the Huffman tables in force at that SOS.  comps[c]['q'] is the quantisation table
+    in force at the component's first scan.  Raises UnsupportedJpeg for what the device does not decode: other processes and
+    colour spaces (as `parse`), a scan that breaks the progression rules, an incomplete file (some coefficient never reaches
+    Al = 0: libjpeg would smooth it), more than MAX_SCANS scans, more than two tables of one class in one scan."""
+    try:
+        return _parse_progressive(data)
+    except UnsupportedJpeg:
+        raise
+    except (IndexError, ValueError, KeyError) as exc:
+        raise UnsupportedJpeg(f"malformed marker segment ({type(exc).__name__}: {exc})") from None
+
+
+def _scan_end(marks, start, n):
+    """First byte behind the entropy-coded data that starts at `start`: the next FF that neither a stuffed 00 nor RSTn follows."""
+    k = int(np.searchsorted(marks, start))
+    return int(marks[k]) if k < len(marks) else n
+
+
+def _parse_progressive(data: bytes):
+    if len(data) < 4 or data[0] != 0xFF or data[1] != 0xD8:
+        raise UnsupportedJpeg("not a JPEG stream")
+    a = np.frombuffer(data, dtype=np.uint8)
+    ff = np.flatnonzero(a[:-1] == 0xFF)
+    nx = a[ff + 1]
+    marks = ff[(nx != 0) & ~((nx >= 0xD0) & (nx <= 0xD7))]
+    pos, n = 2, len(data)
+    qt, ht, comps, H, W, dri = {}, {}, None, 0, 0, 0
+    adobe_transform = None
+    scans, al = [], None                              # al[c][k]: the point transform coefficient k of component c stands at, -1 = not seen
+    while pos + 4 <= n:
+        if data[pos] != 0xFF:
+            raise UnsupportedJpeg("marker expected")
+        while pos < n and data[pos] == 0xFF:
+            pos += 1
+        m = data[pos]
+        pos += 1
+        if m == 0xD9:
+            break
+        if m == 0x01 or 0xD0 <= m <= 0xD7:
+            continue
+        L = _u16(data, pos)
+        seg = data[pos + 2:pos + L]
+        if m == 0xDB:
+            p = 0
+            while p < len(seg):
+                pq, tq = seg[p] >> 4, seg[p] & 15
+                p += 1
+                if pq:
+                    vals = [_u16(seg, p + 2 * i) for i in range(64)]
+                    p += 128
+                else:
+                    vals = list(seg[p:p + 64])
+                    p += 64
+                t = np.zeros(64, dtype=np.int32)
+                t[ZIGZAG] = vals
+                qt[tq] = t
+        elif m == 0xC2:
+            if comps is not None:
+                raise UnsupportedJpeg("second frame header")
+            if seg[0] != 8:
+                raise UnsupportedJpeg("sample precision is not 8 bits")
+            H, W, nc = _u16(seg, 1), _u16(seg, 3), seg[5]
+            comps = [dict(id=seg[6 + 3 * i], h=seg[7 + 3 * i] >> 4, v=seg[7 + 3 * i] & 15, tq=seg[8 + 3 * i]) for i in range(nc)]
+            if H == 0 or W == 0:
+                raise UnsupportedJpeg("frame without a size (DNL)")
+            if nc == 1:
+                comps[0]["h"] = comps[0]["v"] = 1
+            elif nc == 3:
+                c0 = comps[0]
+                if not (comps[1]["h"] == comps[2]["h"] == comps[1]["v"] == comps[2]["v"] == 1 and
+                        (c0["h"], c0["v"]) in ((1, 1), (2, 1), (2, 2))):
+                    raise UnsupportedJpeg("chroma sampling other than 4:4:4 / 4:2:2 / 4:2:0")
+            else:
+                raise UnsupportedJpeg(f"{nc} components")
+            al = [[-1] * 64 for _ in comps]
+        elif 0xC0 <= m <= 0xCF and m not in (0xC4, 0xC8, 0xCC):
+            raise UnsupportedJpeg(f"SOF{m - 0xC0}: not a progressive Huffman file")
+        elif m == 0xC4:
+            p = 0
+            while p < len(seg):
+                tc, th = seg[p] >> 4, seg[p] & 15
+                counts = list(seg[p + 1:p + 17])
+                ns = sum(counts)
+                if tc > 1 or th > 3 or ns > 256 or p + 17 + ns > len(seg):
+                    raise UnsupportedJpeg("bad Huffman table")
+                ht[(tc, th)] = (counts, list(seg[p + 17:p + 17 + ns]))
+                p += 17 + ns
+        elif m == 0xDD:
+            dri = _u16(seg, 0)
+        elif m == 0xEE and len(seg) >= 12 and bytes(seg[:5]) == b"Adobe":
+            adobe_transform = seg[11]
+        elif m == 0xDA:
+            if comps is None:
+                raise UnsupportedJpeg("scan before frame header")
+            if len(comps) == 3 and (adobe_transform == 0 or [c["id"] for c in comps] == [82, 71, 66]):
+                raise UnsupportedJpeg("3-component file stored as RGB, not YCbCr (Adobe transform 0 / component ids R,G,B)")
+            if len(scans) >= MAX_SCANS:
+                raise UnsupportedJpeg(f"more than {MAX_SCANS} scans")
+            ns = seg[0]
+            if not 1 <= ns <= len(comps) or len(seg) != 4 + 2 * ns:
+                raise UnsupportedJpeg("bad scan header")
+            ids = [c["id"] for c in comps]
+            sc = [ids.index(seg[1 + 2 * i]) for i in range(ns)]
+            if sorted(set(sc)) != sc:
+                raise UnsupportedJpeg("scan components out of frame order")
+            if ns == 2:
+                raise UnsupportedJpeg("scan of two components")       # (legal, but no encoder writes it: its MCU is not the frame's)
+            td = [seg[2 + 2 * i] >> 4 for i in range(ns)]
+            ta = [seg[2 + 2 * i] & 15 for i in range(ns)]
+            Ss, Se, Ah, Al = seg[1 + 2 * ns], seg[2 + 2 * ns], seg[3 + 2 * ns] >> 4, seg[3 + 2 * ns] & 15
+            if Ss == 0:
+                if Se != 0:
+                    raise UnsupportedJpeg("DC and AC coefficients in one progressive scan")
+            elif ns != 1:
+                raise UnsupportedJpeg("AC scan of more than one component")
+            elif not Ss <= Se <= 63:
+                raise UnsupportedJpeg("bad spectral selection")
+            if Al > 13 or (Ah and Al != Ah - 1):
+                raise UnsupportedJpeg("bad successive approximation")
+            for c in sc:
+                if Ss and al[c][0] < 0:
+                    raise UnsupportedJpeg("AC scan before the component's first DC scan")
+                for k in range(Ss, Se + 1):
+                    if (Ah == 0 and al[c][k] >= 0) or (Ah and al[c][k] != Ah):
+                        raise UnsupportedJpeg(f"coefficient {k} of component {c}: Ah = {Ah} where the previous Al is {al[c][k]}")
+                    al[c][k] = Al
+                if "q" not in comps[c]:
+                    if comps[c]["tq"] not in qt:
+                        raise UnsupportedJpeg("missing table")
+                    comps[c]["q"] = qt[comps[c]["tq"]].copy()
+            kind = (1 if Ah == 0 else 2) if Ss == 0 else (3 if Ah == 0 else 4)
+            used = [] if kind == 2 else (sorted(set(td)) if kind == 1 else sorted(set(ta)))
+            tc = 0 if kind == 1 else 1
+            if len(used) > 2:
+                raise UnsupportedJpeg("more than two Huffman tables of one class in one scan")
+            snap = {}
+            for slot, th in enumerate(used):
+                if th > 3 or (tc, th) not in ht:
+                    raise UnsupportedJpeg("missing table")
+                snap[(tc, slot)] = ht[(tc, th)]
+            start = pos + L
+            end = _scan_end(marks, start, n)
+            scans.append(dict(comps=sc, td=[used.index(t) if kind == 1 else 0 for t in td],
+                              ta=[used.index(t) if kind >= 3 else 0 for t in ta], Ss=Ss, Se=Se, Ah=Ah, Al=Al, kind=kind, start=start,
+                              end=end, dri=dri, ht=snap))
+            pos = end
+            continue
+        pos += L
+    if comps is None or not scans:
+        raise UnsupportedJpeg("no scan")
+    if any(x != 0 for row in al for x in row):
+        raise UnsupportedJpeg("incomplete progressive file: some coefficient never reaches Al = 0")
+    return dict(H=H, W=W, comps=comps, scans=scans)
+
+
+def _scan_tables(ht, qtabs):
+    """A JpegTables entry from {(class, slot): (counts, symbols)} and {tq: table}; its key for sharing by content."""
+    t = JpegTables()
+    for (tc, slot), (counts, symbols) in ht.items():
+        if sum(counts) > 256 or len(symbols) != sum(counts):
+            raise UnsupportedJpeg("bad Huffman table")
+        t.counts[tc * 2 + slot][:] = counts
+        t.vals[tc * 2 + slot][:len(symbols)] = symbols
+    for tq, q in qtabs.items():
+        t.quant[tq][:] = q.tolist()
+    key = (tuple(sorted((k, tuple(c), tuple(v)) for k, (c, v) in ht.items())), tuple(sorted((k, q.tobytes()) for k, q in qtabs.items())))
+    return t, key
+
+
+def _restart_segments(scan, dri, nunits):
+    """[(first byte, bytes, first unit, units)] of the restart intervals of one scan's entropy-coded bytes."""
+    starts, ends = [0], []
+    if dri:
+        ff = np.flatnonzero(scan[:-1] == 0xFF)
+        rst = ff[(scan[ff + 1] >= 0xD0) & (scan[ff + 1] <= 0xD7)]
+        starts += [int(p) + 2 for p in rst]
+        ends = [int(p) for p in rst]
+    ends.append(len(scan))
+    out = []
+    for k, (s0, s1) in enumerate(zip(starts, ends)):
+        u0 = k * dri if dri else 0
+        if u0 >= nunits:
+            break
+        out.append((s0, s1 - s0, u0, min(dri, nunits - u0) if dri else nunits))
+    return out
+
+
+def is_progressive(data: bytes):
+    """True where `parse_progressive`, not `parse`, is the parser to try: the first SOFn marker of the file is SOF2."""
+    pos, n = 2, len(data)
+    while pos + 4 <= n and data[pos] == 0xFF:
+        while pos < n and data[pos] == 0xFF:
+            pos += 1
+        m = data[pos]
+        pos += 1
+        if 0xC0 <= m <= 0xCF and m not in (0xC4, 0xC8, 0xCC):
+            return m == 0xC2
+        if m in (0xD9, 0xDA):
+            return False
+        if not (m == 0x01 or 0xD0 <= m <= 0xD7):
+            pos += _u16(data, pos)
+    return False
+
+
+def pack_scans(files):
+    """Any mix of baseline and progressive files -> (data, JpegImage[], JpegTables[], JpegScan[], JpegSegment[], groups, sizes,
+    totals) for `pnp_jpeg_decode_scans`.  Images, coefficient / plane / RGB offsets and totals as `pack_batch`.  A baseline
+    file is one scan of kind 'sequential'; a progressive file has one JpegScan per SOS, each with the JpegTables entry of its
+    own Huffman snapshot (the image's own entry holds the quantisation tables).  One restart interval of one scan is one
+    segment; its mcu0 / nmcu count the scan's units (MCUs, or blocks of a one-component scan).  Segments are ordered baseline
+    first, then by (scan ordinal, kind, image): `groups` is an int32 array [n, 4] of (first segment, segments, kind, ordinal),
+    one kernel launch each, and totals['base_segments'] the number of baseline segments in front."""
+    n = len(files)
+    imgs = (JpegImage * n)()
+    tab_index, tab_list = {}, []
+    scans, segs = [], []                              # segs: (ordinal, kind, image, scan index, byte_off, raw, unit0, units)
+    chunks, data_off = [], 0
+    coef = plane = rgb = 0
+    max_blocks = max_pixels = 0
+    sizes = []
+
+    def table(ht, qtabs):
+        t, key = _scan_tables(ht, qtabs)
+        if key not in tab_index:
+            tab_index[key] = len(tab_list)
+            tab_list.append(t)
+        return tab_index[key]
+
+    for i, f in enumerate(files):
+        prog = is_progressive(f)
+        j = parse_progressive(f) if prog else parse(f)
+        comps = j["comps"]
+        hmax = max(c["h"] for c in comps)
+        vmax = max(c["v"] for c in comps)
+        mcux = -(-j["W"] // (8 * hmax))
+        mcuy = -(-j["H"] // (8 * vmax))
+        lo, hi = (j["scans"][0]["start"], max(s["end"] for s in j["scans"])) if prog else (j["scan_start"], j["scan_end"])
+        raw = np.frombuffer(f, dtype=np.uint8, count=hi - lo, offset=lo)
+        im = imgs[i]
+        im.data_off, im.data_len = data_off, len(raw)
+        im.H, im.W, im.ncomp, im.hmax, im.vmax, im.mcux, im.mcuy = j["H"], j["W"], len(comps), hmax, vmax, mcux, mcuy
+        blocks = 0
+        for ci, c in enumerate(comps):
+            im.h[ci], im.v[ci], im.tq[ci] = c["h"], c["v"], (ci if prog else c["tq"])
+            im.td[ci], im.ta[ci] = (0, 0) if prog else (c["td"], c["ta"])
+            im.bx[ci], im.by[ci] = mcux * c["h"], mcuy * c["v"]
+            nb = im.bx[ci] * im.by[ci]
+            im.coef_off[ci], im.plane_off[ci] = coef, plane
+            coef += nb * 64
+            plane += nb * 64
+            blocks += nb
+        im.rgb_off = rgb
+        rgb += j["H"] * j["W"] * 3
+        sizes.append((j["H"], j["W"]))
+        max_blocks = max(max_blocks, blocks)
+        max_pixels = max(max_pixels, j["H"] * j["W"])
+        if prog:
+            im.tab = table({}, {ci: c["q"] for ci, c in enumerate(comps)})       # (quantisation latched per component: slot = component)
+            file_scans = j["scans"]
+        else:
+            key = _table_key(j)
+            if ("base", key) not in tab_index:
+                tab_index[("base", key)] = len(tab_list)
+                t = JpegTables()
+                _fill_tables(t, j)
+                tab_list.append(t)
+            im.tab = tab_index[("base", key)]
+            file_scans = [dict(comps=list(range(len(comps))), td=[c["td"] for c in comps], ta=[c["ta"] for c in comps], Ss=0, Se=63,
+                               Ah=0, Al=0, kind=0, start=lo, end=hi, dri=j["dri"], ht=None)]
+        for o, s in enumerate(file_scans):
+            sc = JpegScan()
+            sc.image, sc.kind, sc.ordinal, sc.ncomp = i, s["kind"], o, len(s["comps"])
+            for q, ci in enumerate(s["comps"]):
+                sc.comp[q], sc.td[q], sc.ta[q] = ci, s["td"][q], s["ta"][q]
+            sc.ss, sc.se, sc.ah, sc.al = s["Ss"], s["Se"], s["Ah"], s["Al"]
+            sc.tab = im.tab if s["ht"] is None else table(s["ht"], {})
+            if len(s["comps"]) == 1 and s["kind"]:
+                c = comps[s["comps"][0]]
+                sc.bw = -(-(-(-j["W"] * c["h"] // hmax)) // 8)
+                sc.bh = -(-(-(-j["H"] * c["v"] // vmax)) // 8)
+            else:
+                sc.bw, sc.bh = mcux, mcuy
+            sc.nunits = sc.bw * sc.bh
+            body = raw[s["start"] - lo:s["end"] - lo]
+            for s0, ln, u0, nu in _restart_segments(body, s["dri"], sc.nunits):
+                segs.append((o if s["kind"] else -1, s["kind"], i, len(scans), s["start"] - lo + s0, ln, u0, nu))
+            scans.append(sc)
+        chunks.append(raw)
+        pad = (-len(raw)) % 16
+        if pad:
+            chunks.append(np.zeros(pad, dtype=np.uint8))
+        data_off += len(raw) + pad
+    segs.sort(key=lambda g: g[:3])                    # (stable: the restart intervals of a scan stay in order)
+    sg = (JpegSegment * len(segs))()
+    groups, clean = [], 0
+    for k, (o, kind, i, si, off, ln, u0, nu) in enumerate(segs):
+        g = sg[k]
+        cap = ((ln + 15) & ~15) + 32
+        g.byte_off, g.clean_off, g.image, g.mcu0, g.nmcu, g.raw_len, g.clean_cap, g.scan = off, clean, i, u0, nu, ln, cap, si
+        g.sub_bits = max(128, (-(-ln * 8 // SUBSEQUENCES) + 31) & ~31)
+        clean += cap
+        if kind:
+            if groups and groups[-1][2:] == [kind, o]:
+                groups[-1][1] += 1
+            else:
+                groups.append([k, 1, kind, o])
+    tabs = (JpegTables * len(tab_list))(*tab_list)
+    sc_arr = (JpegScan * len(scans))(*scans)
+    data = np.concatenate(chunks) if chunks else np.zeros(16, dtype=np.uint8)
+    totals = dict(coef_elems=coef, plane_bytes=plane, rgb_bytes=rgb, clean_bytes=clean, max_blocks=max_blocks, max_pixels=max_pixels,
+                  base_segments=sum(1 for g in segs if g[1] == 0))
+    return data, imgs, tabs, sc_arr, sg, np.asarray(groups, dtype=np.int32).reshape(-1, 4), sizes, totals
 
 
 # ---------------------------------------------------------------------------------------------------------- encoder, host half

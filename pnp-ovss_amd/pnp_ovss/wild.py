@@ -59,12 +59,13 @@ def _load(image):
     return np.ascontiguousarray(a)
 
 
-def decode_images(images, ids):
+def decode_images(images, ids, device_progressive=None):
     """-> list of (H, W, 3) uint8 images, device tensors where the device decoded them (datasets._Base._decode_on_device: the
-    batch decode of the dataset drivers, with its Pillow fall-back for files the device decoder does not cover)."""
+    batch decode of the dataset drivers, with its Pillow fall-back for files the device decoder does not cover).
+    device_progressive: progressive files on the device (True) or with Pillow (False); None: the datasets' default."""
     from .datasets import _Base
     items = [(None, i, _load(im), None) for i, im in zip(ids, images)]
-    return [it[2] for it in _Base._decode_on_device(None, items)]
+    return [it[2] for it in _Base._decode_on_device(None, items, device_progressive)]
 
 
 RESERVE_PIXELS, RESERVE_CHANNELS = 640 * 640, 24       # post-processing workspace of the first call on a model, unless it needs more
@@ -107,7 +108,7 @@ def segment_in_the_wild(model, args, images, class_names, ids=None, overlays=Tru
         raise RuntimeError("pnp_ovss.wild.segment_in_the_wild needs a HIP device (no CPU fallback)")
     m = model.module if hasattr(model, "module") else model
     bs = int(getattr(args, "batch_size", 0) or 0) or int(m._engine.max_batch if getattr(m, "_engine", None) is not None else 8)
-    rgb = decode_images(images, ids)
+    rgb = decode_images(images, ids, getattr(args, "device_progressive", None))
     seg = _segmenter(model, args, max(int(x.shape[0]) * int(x.shape[1]) for x in rgb), max(len(n) for n in class_names) + 1)
     out = []
     for o in range(0, len(rgb), bs):

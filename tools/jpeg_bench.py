@@ -3,6 +3,13 @@
     python tools/jpeg_bench.py [--images 35] [--size 375x500] [--quality 90] [--reps 5] [--out gpurun_out/jpeg_bench.json]
     python tools/jpeg_bench.py --encode [--images 35] [--size 375x500] [--enc_quality 75] [--out profiles/jpeg_encode.json]
 
+    python tools/jpeg_bench.py --progressive [--images 35] [--size 375x500] [--enc_quality 75] [--reps 30] [--out profiles/jpeg_progressive.json]
+
+--progressive: the same images as Pillow's default PROGRESSIVE files (10 scans) through the scan-by-scan decoder
+(pnp_jpeg_decode_scans): the batch between HIP events and end to end (hip.jpeg_decode_batch), per scan kind the kernel time and
+the synchronisation rounds per segment, Pillow on one host thread for the same files, and the baseline files of the same images
+through the baseline device decoder.  Its `device_faster` decides where the datasets send progressive files by default.
+
 --encode: the other direction -- the same images, already on the device, through hip.jpeg_encode_batch (pnp_jpeg_encode: warm,
 HIP events around the device work; the wall time of the whole call with its read-back and marker writing beside it) against
 `Image.fromarray(rgb).save(buf, "JPEG", quality=q)` on one host thread.
@@ -82,6 +89,85 @@ def encode_leg(a, H, W, rng):
             f.write(line + "\n")
 
 
+def progressive_leg(a, H, W, rng):
+    from PIL import Image
+    import torch
+    from pnp_ovss import hip, jpeg as J
+    imgs = [synth_photo(rng, H, W) for _ in range(a.images)]
+
+    def save(im, **kw):
+        b = io.BytesIO()
+        Image.fromarray(im).save(b, "JPEG", quality=a.enc_quality, **kw)
+        return b.getvalue()
+
+    def pil_one(f):
+        return np.asarray(Image.open(io.BytesIO(f)).convert("RGB"))
+
+    def wall(fn):
+        fn()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(a.reps):
+            fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / a.reps * 1e3
+    prog, base = [save(im, progressive=True) for im in imgs], [save(im) for im in imgs]
+    ref = [pil_one(f) for f in prog]
+    t_pil = {}
+    for name, files in (("progressive", prog), ("baseline", base)):
+        t0 = time.perf_counter()
+        for _ in range(a.reps):
+            for f in files:
+                pil_one(f)
+        t_pil[name] = (time.perf_counter() - t0) / a.reps * 1e3
+    exact = all(np.array_equal(o.cpu().numpy(), r) for o, r in zip(hip.jpeg_decode_batch(prog), ref))
+    t_total = wall(lambda: hip.jpeg_decode_batch(prog))
+    t_base = wall(lambda: hip.jpeg_decode_batch(base))
+    t0 = time.perf_counter()
+    for _ in range(a.reps):
+        J.pack_scans(prog)
+    t_pack = (time.perf_counter() - t0) / a.reps * 1e3
+    ctx = hip.jpeg_scans_upload(prog)
+    hip.jpeg_scans_run(ctx)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    ev_ms = []
+    for _ in range(a.reps):                                                # the device work only
+        torch.cuda.synchronize()
+        e0.record()
+        hip.jpeg_scans_run(ctx)
+        e1.record()
+        torch.cuda.synchronize()
+        ev_ms.append(e0.elapsed_time(e1))
+    ctx = hip.jpeg_scans_upload(prog, profile=True)                        # one launch group at a time between events
+    per_kind = {k: [] for k in J.SCAN_KINDS[1:]}
+    for _ in range(a.reps):
+        hip.jpeg_scans_run(ctx)
+        for k, name in enumerate(J.SCAN_KINDS[1:], 1):
+            per_kind[name].append(float(ctx["group_ms"][ctx["groups"][:, 2] == k].sum()))
+    rounds = ctx["d_rounds"].cpu().numpy()
+    kinds = np.array([ctx["scans"][g.scan].kind for g in ctx["segs"]])
+    kind_ms = {name: float(np.median(v)) for name, v in per_kind.items()}
+    total_kind = sum(kind_ms.values())
+    stats = {name: dict(kernel_ms=kind_ms[name], share_of_scan_kernels=kind_ms[name] / total_kind, segments=int((kinds == k).sum()),
+                        rounds_min=int(rounds[kinds == k].min()), rounds_median=float(np.median(rounds[kinds == k])),
+                        rounds_max=int(rounds[kinds == k].max()))
+             for k, name in enumerate(J.SCAN_KINDS[1:], 1)}
+    rec = dict(images=a.images, size=[H, W], quality=a.enc_quality, reps=a.reps, script="Pillow default (10 scans)",
+               jpeg_bytes=dict(progressive=sum(len(f) for f in prog), baseline=sum(len(f) for f in base)),
+               bit_exact_vs_pillow=bool(exact), pillow_1thread_ms=t_pil["progressive"], pillow_1thread_baseline_files_ms=t_pil["baseline"],
+               device_events_ms=float(np.median(ev_ms)), device_end_to_end_ms=t_total, host_pack_ms=t_pack,
+               device_baseline_files_end_to_end_ms=t_base, scan_kinds=stats,
+               device_faster=bool(t_total < t_pil["progressive"]),
+               note="device_events_ms: one pnp_jpeg_decode_scans call on an uploaded batch between two events; device_end_to_end_ms: "
+                    "hip.jpeg_decode_batch with the marker walk, packing, uploads and the error read-back; scan_kinds: kernel time per "
+                    "kind with one synchronisation per launch group, rounds over the restart segments of that kind")
+    line = json.dumps(rec)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
 def main():
     from PIL import Image
     import torch
@@ -95,11 +181,14 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--encode", action="store_true", help="measure the device encoder against Pillow's instead of the decoder")
     ap.add_argument("--enc_quality", type=int, default=75)
+    ap.add_argument("--progressive", action="store_true", help="measure the scan-by-scan decode of progressive files (quality: --enc_quality)")
     a = ap.parse_args()
     H, W = map(int, a.size.split("x"))
     rng = np.random.default_rng(0)
     if a.encode:
         return encode_leg(a, H, W, rng)
+    if a.progressive:
+        return progressive_leg(a, H, W, rng)
     files = []
     for _ in range(a.images):
         b = io.BytesIO()
