@@ -524,6 +524,30 @@ int pnp_jpeg_encode(const uint8_t* d_rgb, const pnp_jpeg_enc_image* h_images, in
                     uint8_t* d_out, int32_t* d_out_len, int32_t* d_err, void* d_ws, int64_t ws_bytes, int64_t* ws_need,
                     void* stream);
 
+/* Label maps as 8-bit PNG files: the zlib stream of the IDAT chunk for a batch of uint8 label maps of any sizes, concatenated
+ * in d_labels as pnp_remap_hist leaves them.  The host adds the chunk framing and its CRC-32 (pnp_ovss/png.py).  The bytes are
+ * fixed by the format, not by a library: header 78 01; one deflate block with the fixed Huffman code (BFINAL = 1, BTYPE = 01);
+ * end-of-block; zero bits to a whole byte; Adler-32 of the filtered stream, big-endian.  Per row the filter is Up (2) when the
+ * Up-filtered row has fewer changes between neighbouring bytes than the raw row, None (0) otherwise; the W + 1 bytes of a row,
+ * filter byte included, are cut into maximal runs of equal bytes, and a run of byte b and length r is: literal b, then
+ * (r - 1) / 258 matches of length 258 at distance 1, then for t = (r - 1) % 258 one match of length t when t >= 3, t literals
+ * otherwise (csrc/png_enc.hip; tests/_png_refs.py restates it).  h_images: HOST array of n_images descriptors.  Image i's
+ * stream, zlib header and Adler-32 included, goes to d_out + out_off and its length to d_out_len[i]; an image whose stream
+ * would exceed out_cap gets d_out_len[i] = -1, sets *d_err = 1 and has nothing written, the other images are unaffected
+ * (*d_err is 0 otherwise).  No stream exceeds 2 + ceil((10 + 9 H (W + 1)) / 8) + 4 bytes.  d_ws: workspace of at least
+ * *ws_need bytes, 256-byte aligned; a call with d_ws = NULL only computes *ws_need for these descriptors.  At most 2^31 / 9
+ * bytes of filtered stream (the sum of H (W + 1)) per call, PNP_ERR_ARG beyond: bit offsets are int32.  The argument checks
+ * run before any device is touched.  Stateless; nothing is read back to the host. */
+typedef struct pnp_png_image {
+    int64_t labels_off;         /* byte offset of the label map in d_labels (H*W, row-major uint8) */
+    int64_t out_off;            /* byte offset of its stream in d_out */
+    int32_t H, W;               /* 1..65535 */
+    int32_t out_cap;            /* bytes reserved at out_off, >= 0 */
+    int32_t pad;
+} pnp_png_image;
+int pnp_png_encode(const uint8_t* d_labels, const pnp_png_image* h_images, int32_t n_images, uint8_t* d_out, int32_t* d_out_len,
+                   int32_t* d_err, void* d_ws, int64_t ws_bytes, int64_t* ws_need, void* stream);
+
 /* ---- introspection (tests / profiling) --------------------------------------------------- */
 /* Named internal device buffers: "image_embeds" (fp32 B*N*D), "text_hidden" (fp32 B*L*H: last_hidden_state of the most recent
  * text pass, multimodal or text-only), "maps" (fp32 post-process maps), "crf_q", "P", "dP", "crf_M" (int32 [2][B+1] lattice id

@@ -20,6 +20,8 @@ Multi-rank (the reference: DDP-constructor broadcast PnP.py:1218, 
 `--in_the_wild` (the COCO driver's branch, PnPc.py:351-384): every {home_dir}/In_the_wild/{id}.jpeg|.jpg with the class names of
 `--wild_classes FILE.json` -> {save_path}/0519_Segmentation/BLIP_N_drop_{id}_{postprocess}.jpeg (colour overlay) + {id}.npy (label
 map); no ground truth, no histogram (pnp_ovss.wild).  `--save_vis` writes the same overlay for every image of a dataset run.
+`--save_png` writes the label maps as 8-bit PNG files with a class palette (`--png_palette voc|overlay|grey`), deflate-encoded
+on the GPU: {save_path}/label_png/{img_id}.png in a dataset run, {save_path}/0519_Segmentation/{id}.png in the wild.
 
 Device work happens in libpnp_hip.so via pnp_ovss.model.Segmenter; this file is host orchestration.
 """
@@ -101,6 +103,13 @@ def get_args_parser():
                    help="write a colour overlay of every image's final label map, rendered and JPEG-encoded on the GPU, as "
                         "{save_path}/0519_Segmentation/BLIP_N_drop_{id}_{postprocess}.jpeg (the reference's Draw_Segmentation_map; "
                         "colours are stable per class id).  Rank-local files, no collective.  Costs one read-back per batch")
+    p.add_argument("--save_png", action="store_true",
+                   help="write every image's final label map as an 8-bit PNG file, deflate-encoded on the GPU: a dataset run "
+                        "writes {save_path}/label_png/{img_id}.png, --in_the_wild {save_path}/0519_Segmentation/{id}.png beside the "
+                        ".npy.  Rank-local files, no collective.  Costs one read-back per batch")
+    p.add_argument("--png_palette", default="voc", choices=["voc", "overlay", "grey"],
+                   help="--save_png: indexed files with the PASCAL VOC colormap (default) or the overlay's class colours, or "
+                        "8-bit greyscale files without a palette")
     p.add_argument("--synthetic_images", default=70, type=int)
     p.add_argument("--max_batches", default=0, type=int)
     return p
@@ -277,6 +286,14 @@ def main(rank, world_size, args):
             with open(wild.vis_file_name(args.save_path, branch, i, args.postprocess), "wb") as fh:
                 fh.write(f)
 
+    def save_png(img_ids, maps):
+        """--save_png: the label maps of a launch as 8-bit PNG files, encoded on the device (hip.png_encode_batch)."""
+        from pnp_ovss import hip
+        os.makedirs(f"{args.save_path}/label_png", exist_ok=True)
+        for i, f in zip(img_ids, hip.png_encode_batch(maps, args.png_palette)):
+            with open(f"{args.save_path}/label_png/{i}.png", "wb") as fh:
+                fh.write(f)
+
     if args.pipelines > 1:
         # P replicas (model + Segmenter + stream + host thread) consume the batch stream; each batch still runs the whole
         # path on one replica, into that replica's own pair of confusion matrices (bench.py --pipelines is the same scheme)
@@ -314,6 +331,8 @@ def main(rank, world_size, args):
                                 keep_labels(batch["img_ids"], ln if ln is not None else l1)      # (dict stores of distinct keys: no lock)
                             if args.save_vis:
                                 save_vis(batch["img_ids"], *((ln, "N_drop") if ln is not None else (l1, "1_drop")), prep)
+                            if args.save_png:
+                                save_png(batch["img_ids"], ln if ln is not None else l1)
                             ring[2].record()
                             last = finish((batch["img_ids"], layer, head, l1 is not None, ln is not None, ring))
                         with lock:
@@ -352,6 +371,8 @@ def main(rank, world_size, args):
                 keep_labels(batch["img_ids"], ln if ln is not None else l1)
             if args.save_vis:
                 save_vis(batch["img_ids"], *((ln, "N_drop") if ln is not None else (l1, "1_drop")), prep)
+            if args.save_png:
+                save_png(batch["img_ids"], ln if ln is not None else l1)
             ring[2].record()
             job = (batch["img_ids"], layer, head, l1 is not None, ln is not None, ring)
             if pending is not None:

@@ -118,6 +118,7 @@ def load_library():
         "pnp_jpeg_decode_scans": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, i64, vp, vp, vp, i32, i32, vp, vp, vp, vp]),
         "pnp_overlay_labels": (i32, [vp, vp, vp, i32, vp, C.c_double, vp, vp]),
         "pnp_jpeg_encode": (i32, [vp, vp, i32, vp, vp, vp, vp, vp, i64, C.POINTER(i64), vp]),
+        "pnp_png_encode": (i32, [vp, vp, i32, vp, vp, vp, vp, i64, C.POINTER(i64), vp]),
         "pnp_op_split": (i32, [vp, vp, vp, i64, vp]),
         "pnp_op_gemm_x3": (i32, [vp, vp, i32, vp, vp, i32, i32, i32, i32, vp, i32, vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, vp]),
         "pnp_op_gemm_x3a": (i32, [vp, i32, vp, vp, i32, i32, i32, i32, vp, vp, i32, vp, i32, i32, vp, i32, vp]),
@@ -179,7 +180,7 @@ EXPORTED = ["pnp_create", "pnp_create_shared", "pnp_destroy", "pnp_last_error", 
             "pnp_streamk_status", "pnp_text_forward_text", "pnp_project_normalize", "pnp_itc_similarity",
             "pnp_op_text_self_attn", "pnp_op_text_self_attn_bwd", "pnp_op_layernorm_ex", "pnp_op_layernorm_bwd",
             "pnp_op_text_embed", "pnp_op_itm_head", "pnp_op_itm_grad_seed", "pnp_op_patchify", "pnp_op_cls_rows",
-            "pnp_op_gemm_args", "pnp_op_gemm_plan", "pnp_overlay_labels", "pnp_jpeg_encode", "pnp_jpeg_decode_scans",
+            "pnp_op_gemm_args", "pnp_op_gemm_plan", "pnp_overlay_labels", "pnp_jpeg_encode", "pnp_png_encode", "pnp_jpeg_decode_scans",
             "pnp_crf_create", "pnp_crf_destroy", "pnp_crf_allocated_bytes", "pnp_crf_last_error", "pnp_crf_set_batch",
             "pnp_crf_infer", "pnp_crf_set_batch_aniso", "pnp_crf_set_compat", "pnp_crf_start", "pnp_crf_step", "pnp_crf_read",
             "pnp_crf_kl", "pnp_crf_create_terms", "pnp_crf_set_batch_terms", "pnp_crf_set_term_compat", "pnp_crf_infer_terms",
@@ -499,6 +500,105 @@ def jpeg_encode_batch(images, quality=75, device=None):
             if todo and worst:
                 raise RuntimeError("pnp_jpeg_encode: a scan exceeded its worst-case bound")
             worst = True                           # (rare: noise-like content at a high quality) once more with the bound no input exceeds
+    return files
+
+
+class PnpPngImage(C.Structure):
+    _fields_ = [("labels_off", C.c_int64), ("out_off", C.c_int64), ("H", C.c_int32), ("W", C.c_int32), ("out_cap", C.c_int32),
+                ("pad", C.c_int32)]
+
+
+def _concat_labels(label_maps, dev):
+    """(H, W) label maps, device tensors or numpy arrays -> (one flat uint8 device tensor, [(H, W)])."""
+    sizes = []
+    for m in label_maps:
+        if m.ndim != 2:
+            raise ValueError(f"a label map is (H, W), not {tuple(m.shape)}")
+        sizes.append((int(m.shape[0]), int(m.shape[1])))
+    if all(isinstance(m, torch.Tensor) and m.is_cuda for m in label_maps):
+        flat = torch.cat([m.reshape(-1) for m in label_maps]).to(torch.uint8) if len(label_maps) > 1 else \
+            label_maps[0].contiguous().reshape(-1).to(torch.uint8)
+    else:
+        flat = torch.from_numpy(np.concatenate([np.ascontiguousarray(m.cpu().numpy() if isinstance(m, torch.Tensor) else m).astype(np.uint8)
+                                                .reshape(-1) for m in label_maps])).to(dev)
+    return flat, sizes
+
+
+def png_encode_streams(label_maps, capacities=None, out=None, device=None):
+    """pnp_png_encode for one batch: the zlib streams (header and Adler-32 included) of the IDAT chunks of `label_maps` ((H, W)
+    uint8 device tensors or numpy arrays).  capacities: bytes reserved per image (default png.stream_capacity, which no stream
+    exceeds); out: a uint8 device tensor to write into (default: a new one), image i's stream starts at offsets[i] = sum of
+    the capacities before it.  Returns (out, offsets, lengths, err): lengths[i] = -1 and err = 1 when image i did not fit its
+    capacity -- nothing of it is written then, the other images are."""
+    if not torch.cuda.is_available():
+        raise RuntimeError("pnp_ovss.hip.png_encode_streams needs a HIP device (no CPU fallback)")
+    from . import png as P
+    lib = load_library()
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    B = len(label_maps)
+    labels, sizes = _concat_labels(label_maps, dev)
+    caps = [P.stream_capacity(h, w) for h, w in sizes] if capacities is None else [int(c) for c in capacities]
+    if len(caps) != B:
+        raise ValueError("one capacity per image")
+    desc = (PnpPngImage * B)()
+    offsets, lo, oo = [], 0, 0
+    for i, ((h, w), c) in enumerate(zip(sizes, caps)):
+        desc[i] = PnpPngImage(lo, oo, h, w, c, 0)
+        offsets.append(oo)
+        lo += h * w
+        oo += c
+    if out is None:
+        out = torch.empty(oo, dtype=torch.uint8, device=dev)
+    elif not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() >= oo):
+        raise ValueError(f"out: a contiguous uint8 device tensor of at least {oo} bytes")
+    need = C.c_int64()
+    r = lib.pnp_png_encode(None, desc, B, None, None, None, None, 0, C.byref(need), None)
+    if r != 0:
+        raise RuntimeError(f"pnp_png_encode refused the batch ({r}): image sizes 1..{P.MAX_SIDE}, at most {P.MAX_STREAM_BYTES} "
+                           f"bytes of H * (W + 1) per call")
+    ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+    d_len = torch.empty(B, dtype=torch.int32, device=dev)
+    d_err = torch.empty(1, dtype=torch.int32, device=dev)
+    r = lib.pnp_png_encode(labels.data_ptr(), desc, B, out.data_ptr(), d_len.data_ptr(), d_err.data_ptr(), ws.data_ptr(), need.value,
+                           None, torch.cuda.current_stream().cuda_stream)
+    if r != 0:
+        raise RuntimeError(f"pnp_png_encode failed ({r})")
+    lens = [int(v) for v in d_len.cpu()]           # (synchronises: the workspace and the inputs may go after this)
+    return out, offsets, lens, int(d_err.item())
+
+
+def png_encode_batch(label_maps, palette="voc", device=None):
+    """A batch of (H, W) uint8 label maps (device tensors or numpy arrays, any sizes) as 8-bit PNG files, deflate-encoded on the
+    device: returns the files as a list of bytes.  palette: "voc" (the PASCAL VOC colormap), "overlay" (the colours
+    pnp_ovss.vis gives each class) or a (256, 3) uint8 array -> indexed files (colour type 3); None or "grey" -> 8-bit grey
+    (colour type 0).  The device writes the zlib streams (pnp_png_encode: per-row None / Up filter, runs as distance-1 matches, the
+    fixed Huffman code), the host the chunks around them (pnp_ovss.png.encode_chunks); only the finished streams cross to the
+    host, in one copy per group."""
+    from . import png as P
+    label_maps = list(label_maps)
+    if not label_maps:
+        return []
+    pal = P.resolve_palette(palette)
+    files = [None] * len(label_maps)
+    groups, cur, n = [], [], 0
+    for i, m in enumerate(label_maps):             # split at the per-call limit on filtered-stream bytes
+        e = int(m.shape[0]) * (int(m.shape[1]) + 1)
+        if cur and n + e > P.MAX_STREAM_BYTES:
+            groups.append(cur)
+            cur, n = [], 0
+        cur.append(i)
+        n += e
+    groups.append(cur)
+    for grp in groups:
+        maps = [label_maps[i] for i in grp]
+        out, offs, lens, err = png_encode_streams(maps, device=device)
+        if err or min(lens) < 0:
+            raise RuntimeError("pnp_png_encode: a stream exceeded its worst-case bound")
+        flat = torch.cat([out[o:o + n_] for o, n_ in zip(offs, lens)]).cpu().numpy().tobytes()
+        o = 0
+        for i, m, n_ in zip(grp, maps, lens):
+            files[i] = P.encode_chunks(int(m.shape[0]), int(m.shape[1]), flat[o:o + n_], pal)
+            o += n_
     return files
 
 

@@ -6,7 +6,8 @@ Rules (those of the COCO-Object driver, as pnp_ovss.model.Segmenter implements t
 "A picture of " + " ".join(names) (:384); Scale_0_1 on both branches; the 1-drop branch only when drop_iter < 3; always a
 background channel.  The label remap is the identity: label = position of the name in the image's list + 1, 0 = background.
 Images are decoded on the device (hip.jpeg_decode_batch, Pillow for the files it does not cover) and resized there
-(hip.preprocess_images); the overlays are rendered and JPEG-encoded there too (pnp_ovss.vis)."""
+(hip.preprocess_images); the overlays are rendered and JPEG-encoded there too (pnp_ovss.vis), and so are the label maps' PNG
+files (hip.png_encode_batch)."""
 import collections
 import glob
 import json
@@ -14,9 +15,10 @@ import os
 
 import numpy as np
 
-WildResult = collections.namedtuple("WildResult", "id labels jpeg branch")
+WildResult = collections.namedtuple("WildResult", "id labels jpeg branch png", defaults=(None,))
 WildResult.__doc__ = """id; labels: uint8 (H, W) numpy label map; jpeg: the overlay file's bytes (None without overlays);
-branch: "N_drop", or "1_drop" when the N-drop branch did not run (drop_iter 1)."""
+branch: "N_drop", or "1_drop" when the N-drop branch did not run (drop_iter 1); png: the label map as an 8-bit PNG file's bytes
+(None unless asked for)."""
 
 MAX_CLASSES = 255          # uint8 label maps, 0 = background
 
@@ -92,12 +94,14 @@ def _segmenter(model, args, pixels, channels):
     return seg
 
 
-def segment_in_the_wild(model, args, images, class_names, ids=None, overlays=True):
+def segment_in_the_wild(model, args, images, class_names, ids=None, overlays=True, png=False, png_palette="voc"):
     """images: JPEG bytes, file paths or (H, W, 3) uint8 arrays; class_names: one list of names per image.  args: the drivers'
     namespace -- img_size, drop_iter, max_att_block_num, prune_att_head, threshold, postprocess; optional batch_size (default:
     the engine's max_batch), crf_chunk.  Returns one WildResult per image: the uint8 label
     map of the N-drop branch (of the 1-drop branch when drop_iter is 1) and, with overlays=True, its colour overlay as JPEG
-    bytes.  Overlay colours are stable per label (pnp_ovss.vis), not ranked per image as in the reference."""
+    bytes.  Overlay colours are stable per label (pnp_ovss.vis), not ranked per image as in the reference.  png=True adds the
+    label map as an 8-bit PNG file (r.png), deflate-encoded on the device; png_palette: "voc", "overlay", a (256, 3) uint8
+    array, or None / "grey" for a greyscale file (hip.png_encode_batch)."""
     ids = check_inputs(images, class_names, ids)
     images, class_names = list(images), [list(n) for n in class_names]
     if not images:
@@ -120,8 +124,9 @@ def segment_in_the_wild(model, args, images, class_names, ids=None, overlays=Tru
         files = [None] * len(org)
         if overlays:
             files = vis.encode_overlays(maps, prep["rgb"], prep["sizes"])
-        for i, lab, f in zip(ids[o:o + bs], maps, files):
-            out.append(WildResult(i, lab.cpu().numpy().astype(np.uint8), f, branch))
+        pngs = hip.png_encode_batch(maps, png_palette) if png else [None] * len(org)
+        for i, lab, f, pf in zip(ids[o:o + bs], maps, files, pngs):
+            out.append(WildResult(i, lab.cpu().numpy().astype(np.uint8), f, branch, pf))
     return out
 
 
@@ -152,7 +157,8 @@ def load_wild_classes(path, ids):
 
 def run_cli(rank, world_size, args):
     """`--in_the_wild` of the command line: every image of {home_dir}/In_the_wild with the class names of --wild_classes ->
-    {save_path}/0519_Segmentation/BLIP_N_drop_{id}_{postprocess}.jpeg (the overlay) and {id}.npy (the label map) beside it.
+    {save_path}/0519_Segmentation/BLIP_N_drop_{id}_{postprocess}.jpeg (the overlay) and {id}.npy (the label map) beside it;
+    with --save_png also {id}.png, the label map as an 8-bit PNG file with the palette of --png_palette.
     Ranks take every world_size-th image and write their own files; no collective, no histogram directories."""
     import torch
     from lavis.models import load_model_and_preprocess
@@ -172,11 +178,16 @@ def run_cli(rank, world_size, args):
         stash_layer=args.max_att_block_num - 1, mode=args.dtype, checkpoint=args.checkpoint, vocab=args.vocab,
         max_text_len=min(512, max(64, 8 + 6 * max(len(n) for n in names))))
     os.makedirs(f"{args.save_path}/0519_Segmentation", exist_ok=True)
-    res = segment_in_the_wild(model, args, [found[k][1] for k in mine], [names[k] for k in mine], [ids[k] for k in mine])
+    save_png = bool(getattr(args, "save_png", False))
+    res = segment_in_the_wild(model, args, [found[k][1] for k in mine], [names[k] for k in mine], [ids[k] for k in mine],
+                              png=save_png, png_palette=getattr(args, "png_palette", "voc"))
     for r in res:
         with open(vis_file_name(args.save_path, r.branch, r.id, args.postprocess), "wb") as f:
             f.write(r.jpeg)
         np.save(f"{args.save_path}/0519_Segmentation/{r.id}.npy", r.labels)
+        if save_png:
+            with open(f"{args.save_path}/0519_Segmentation/{r.id}.png", "wb") as f:
+                f.write(r.png)
     print(json.dumps({"in_the_wild": True, "rank": rank, "images": len(res), "branch": res[0].branch if res else None,
                       "out": f"{args.save_path}/0519_Segmentation"}), flush=True)
     return res
