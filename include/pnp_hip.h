@@ -252,7 +252,8 @@ int pnp_crf_infer(pnp_crf* c, int32_t iters, float pos_w, float bi_w, float* d_q
  *
  * pnp_crf_set_batch_aniso: pnp_crf_set_batch with one width per feature axis -- Gaussian features (x / pos_xy[0],
  * y / pos_xy[1]), bilateral (x / bi_xy[0], y / bi_xy[1], r / bi_rgb[0], g / bi_rgb[1], b / bi_rgb[2]).  Equal widths build the
- * lattices of pnp_crf_set_batch bit for bit.  The Gaussian lattice is kept while the sizes and BOTH its widths stay the same. */
+ * lattices of pnp_crf_set_batch bit for bit.  The Gaussian lattice is kept while the sizes and BOTH its widths stay the same.
+ * Synchronises as pnp_crf_set_batch does. */
 int pnp_crf_set_batch_aniso(pnp_crf* c, const pnp_crf_batch* batch, const float pos_xy[2], const float bi_xy[2], const float bi_rgb[3],
                             void* stream);
 /* Label compatibility of term 0 (Gaussian) or 1 (bilateral), as MESSAGE WEIGHTS, used as given: with msg_t[k] the term's
@@ -711,7 +712,9 @@ int pnp_op_cast(int32_t to_bf16, const float* d_in, void* d_out, int64_t n, void
  * bits [begin_bit, end_bit) into d_keys_out / d_vals_out, equal keys keeping their input order; the input arrays are
  * overwritten.  h_seg_off (HOST array of n_seg + 1 ascending item offsets from 0 to n, n_seg <= 64; NULL = one segment):
  * the items of a segment are sorted among themselves and stay in its range (the images of a batch).
- * pnp_op_scan_i32: d_out[i] = sum of d_in[0..i] (inclusive) or d_in[0..i-1] (exclusive); in place allowed. */
+ * pnp_op_scan_i32: d_out[i] = sum of d_in[0..i] (inclusive) or d_in[0..i-1] (exclusive); in place allowed.
+ * Both operator forms allocate their scratch per call and synchronise the stream before they free it: they hold the host
+ * until the stream has drained (the lattice build itself runs the same kernels in the solver's workspace and does not). */
 int pnp_op_sort_pairs(uint64_t* d_keys_in, uint64_t* d_keys_out, uint32_t* d_vals_in, uint32_t* d_vals_out, int64_t n,
                       int32_t begin_bit, int32_t end_bit, const size_t* h_seg_off, int32_t n_seg, void* stream);
 int pnp_op_scan_i32(const int32_t* d_in, int32_t* d_out, int64_t n, int32_t inclusive, void* stream);

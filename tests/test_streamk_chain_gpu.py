@@ -30,6 +30,7 @@ import pytest
 torch = pytest.importorskip("torch")
 
 import _gemm_refs as R          # noqa: E402
+from _stream_gate import BLOCKER_MS, _runs_beside, blocker_cycles          # noqa: E402, F401  (the blocker and the queue probe: shared with test_stream_order_gpu.py)
 from test_hip_parity import _x3_prepare, streamk_forced          # noqa: E402, F401  (the fixture: pnp_set_tuning("streamk", 2), restored to 1)
 
 pytestmark = pytest.mark.gpu
@@ -38,46 +39,11 @@ pytestmark = pytest.mark.gpu
 # ragged, N % 4 == 0 and even (every epilogue accepts it; token columns: 442 + 70 tokens of two images)
 SHAPE = (300, 512, 256)
 RING = ("bias_f32", "resid_f32", "gelu_split", "plain_split", "tokcols_f32")
-BLOCKER_MS = 100.0
 
 CASES = [(RING[i], RING[(i + 1) % 5]) for i in range(5)]                    # each epilogue once as X and once as Y
 CASES += [(RING[(i + 1) % 5], RING[i]) for i in range(5)]                   # the ring reversed
 CASES += [("bias_f32", "bias_f32")]                                        # same epilogue: ordered by a per-epilogue chain as well
 CASES += [("resid_f32", "gelu_split", "tokcols_f32")]                      # three streams: fc2 | fc1 | cross-K/V of three pipelines
-
-
-@pytest.fixture(scope="module")
-def blocker_cycles():
-    """torch.cuda._sleep cycle count of a ~100 ms kernel: two counts timed with events, scaled linearly."""
-    def ms(cycles):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        torch.cuda._sleep(cycles)
-        b.record()
-        b.synchronize()
-        return a.elapsed_time(b)
-    ms(100_000)                                                             # first launch: module load
-    c1, c2 = 1_000_000, 5_000_000
-    t1, t2 = ms(c1), ms(c2)
-    assert t2 > t1 > 0, (t1, t2)
-    cycles = int(c2 + (BLOCKER_MS - t2) * (c2 - c1) / (t2 - t1))
-    assert cycles > 0, (t1, t2)
-    return cycles
-
-
-def _runs_beside(blocked, other, cycles, tick):
-    """Does a tiny kernel on `other` complete while a blocker of `cycles` holds `blocked`?"""
-    blk, free = torch.cuda.Event(), torch.cuda.Event()
-    with torch.cuda.stream(blocked):
-        torch.cuda._sleep(cycles)
-        blk.record()
-    with torch.cuda.stream(other):
-        tick.add_(1)
-        free.record()
-    free.synchronize()
-    beside = not blk.query()
-    torch.cuda.synchronize()
-    return beside
 
 
 @pytest.fixture(scope="module")
